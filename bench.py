@@ -20,7 +20,9 @@ global seeds 1000 + index, no per-step communication, one RCCL gather of the uin
 Everything is resident in HBM when the timed region starts (synthetic fp16 weights in the checkpoint's state-dict schema, seeded
 N(0,1) conditioning; the text encoder is outside the path).  Weights are generated on rank 0 and broadcast over RCCL.
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+A plain run sets up, warms up, times --steps jobs, writes the last timed job's images with --dump-outputs DIR (dump_outputs) and
+prints ONE JSON line on rank 0 with the contract fields; `roofline`, `cpu_baseline` and the re-timings under `config` are null.
+With --full it then also measures them:
   "roofline":     the implicit-GEMM MFMA kernel family's achieved TFLOP/s vs the 2.5 PFLOP/s dense fp16 peak — per-launch HIP events
                   on the launch stream in a separate profiled pass of the same job; "traffic" = HBM bytes per launch of that family
                   from two rocprofv3 PMC passes (FETCH_SIZE, then WRITE_SIZE; kernel trace only) of one job of THIS workload, taken by
@@ -93,7 +95,17 @@ def parse():
     ap.add_argument("--cpu-baseline-budget", type=float, default=185.0, help="seconds of CPU timing the baseline may spend (it adapts its repetitions)")
     ap.add_argument("--cpu-baseline-timeout", type=float, default=330.0, help="hard wall limit of the baseline child process")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="(internal) run the CPU baseline alone and print its JSON")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("SDMI_BENCH_FULL") == "1",
+                    help="after the timed steps, also measure everything the headline figure does not need: the roofline block (with its PMC "
+                         "passes), the drop-in, every-row-computed and accuracy-mode re-timings and the CPU baseline (the --no-* flags above "
+                         "drop single legs).  Off by default; SDMI_BENCH_FULL=1 turns it on for every bench.py call of a measurement script")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float32, at most 64 MB: dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.pmc_traffic and not args.full:
+        ap.error("--pmc-traffic feeds the roofline block, which only a --full run measures")
     cfg = dict(CONFIGS[args.config])
     args.model = args.model or cfg["model"]
     args.size = args.size or cfg["size"]
@@ -265,8 +277,8 @@ def pmc_traffic(args):
 def pmc_child_args(argv):
     """The command line of the one-job child a PMC pass profiles: this run's workload flags, without the flags that shape the timed
     region or start further children."""
-    drop_with_value = ("--steps", "--warmup", "--gpus", "--cpu-baseline-budget", "--cpu-baseline-timeout", "--pmc-timeout")
-    drop_flags = ("--pmc-traffic", "--no-pmc-traffic", "--verify-shards", "--no-cpu-baseline", "--no-roofline", "--no-dropin")
+    drop_with_value = ("--steps", "--warmup", "--gpus", "--cpu-baseline-budget", "--cpu-baseline-timeout", "--pmc-timeout", "--dump-outputs")
+    drop_flags = ("--pmc-traffic", "--no-pmc-traffic", "--verify-shards", "--no-cpu-baseline", "--no-roofline", "--no-dropin", "--full")
     child, skip = [], False
     for a in argv:
         if skip:
@@ -544,6 +556,26 @@ def cpu_baseline_isolated(args):
                 "sample": f"CPU baseline stopped at the {args.cpu_baseline_timeout:.0f} s wall limit ({time.time() - t0:.0f} s) on this host"}
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir, cap_bytes=DUMP_CAP_BYTES):
+    """--dump-outputs: what a caller of the timed path receives from its last step — the job's uint8 images [n, H, W, 3] (the whole
+    global batch on rank 0; a hires job's at the upscaled size) — as out_dir/images.npy in float32.  When that exceeds cap_bytes, a
+    fixed sample of half the cap is written instead as images_sample.npy: the elements at np.random.default_rng(0).choice(size, k,
+    replace=False) in ascending order of flat index, the same positions in every run of the same arguments.  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    images = np.stack([np.asarray(im) for im in res.images]).astype(np.float32)
+    if images.nbytes <= cap_bytes:
+        np.save(os.path.join(out_dir, "images.npy"), images)
+        return {"images": list(images.shape)}
+    k = cap_bytes // 2 // images.itemsize
+    idx = np.sort(np.random.default_rng(0).choice(images.size, k, replace=False))
+    np.save(os.path.join(out_dir, "images_sample.npy"), images.reshape(-1)[idx])
+    return {"images_sample": [k]}
+
+
 def main():
     args = parse()
     if args.cpu_baseline_only:
@@ -583,10 +615,13 @@ def main():
     coll0 = par.COLLECTIVES["job"]
     t0 = time.time()
     for _ in range(args.steps):
-        run_once()
+        last = run_once()
     torch.cuda.synchronize(); par.barrier()
     elapsed = par.max_over_ranks(time.time() - t0, device=torch.device("cuda", local_rank))
     collectives_per_job = (par.COLLECTIVES["job"] - coll0) / max(args.steps, 1)      # data-path collectives inside the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)
+    del last
 
     shard_check = None
     if args.verify_shards and world > 1:
@@ -603,7 +638,7 @@ def main():
                     bad.append(r)
             shard_check = "ok" if not bad and len(whole.images) == args.batch * world else f"MISMATCH on the slices of ranks {bad}"
         par.barrier()
-    if args.pmc_traffic is None:                           # default: measured for the headline workload wherever the profiler exists
+    if args.pmc_traffic is None and args.full:             # default: measured for the headline workload wherever the profiler exists
         import shutil
         # (not when this process is itself being profiled: the children would inherit the outer tool's environment)
         profiled = any(k in os.environ for k in ("HSA_TOOLS_LIB", "ROCP_TOOL_LIBRARIES", "ROCPROFILER_LIBRARY_CTOR")) or \
@@ -615,14 +650,14 @@ def main():
         except Exception as ex:                                # never lose the bench line to the profiler
             print(f"bench.py: --pmc-traffic failed: {type(ex).__name__}: {ex}", file=sys.stderr)
     roof, kernels = (None, None)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         if world > 1:                                  # profile this rank's slice alone (no collective inside the profiled pass)
             run_local, _ = make_job(args, model, 0, 1, local_only=True)
             roof, kernels = roofline_block(args, run_local)
         else:
             roof, kernels = roofline_block(args, run_once)
     dropin = dropin_auto = None
-    if rank == 0 and world == 1 and not args.no_dropin and not (args.hires or args.img2img) and args.sampler == "Euler a":
+    if rank == 0 and world == 1 and args.full and not args.no_dropin and not (args.hires or args.img2img) and args.sampler == "Euler a":
         try:
             dropin = round(dropin_path(args, model, jobs=min(3, max(1, args.steps))), 4)
         except Exception as ex:                                # the drop-in stand-in must never cost the bench line
@@ -632,7 +667,7 @@ def main():
         except Exception as ex:
             dropin_auto = f"failed: {type(ex).__name__}: {ex}"
     per_row = None
-    if rank == 0 and world == 1 and not args.no_dropin:
+    if rank == 0 and world == 1 and args.full and not args.no_dropin:
         # transparency leg: the same job with the CFG denoiser's common-subexpression options off — every UNet row computed on its own, as the
         # reference does (engine.CFG_PAIRS: the layers in front of the first cross-attention run for both halves of the [cond | uncond] batch)
         eng_mod = importlib.import_module(PKG + ".engine")
@@ -651,7 +686,7 @@ def main():
         finally:
             eng_mod.CFG_PAIRS = prev_pairs
     acc_ips = None
-    if rank == 0 and world == 1 and not args.no_dropin:
+    if rank == 0 and world == 1 and args.full and not args.no_dropin:
         # the accuracy mode (engine option "residual_fp32": every tensor that is not a matrix-core operand with ~22 bits — the
         # configuration that meets north_star's <= 1e-3 per forward) on the same job
         shared_mod = importlib.import_module(PKG + ".shared")
@@ -670,7 +705,7 @@ def main():
             shared_mod.opts.sdmi_accuracy_mode = False
             model.set_accuracy_mode(False)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_isolated(args)
     par.barrier()
     if rank != 0:

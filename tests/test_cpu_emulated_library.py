@@ -67,15 +67,16 @@ BENCH_SMALLEST = ["--model", "tiny", "--size", "64", "--sampler-steps", "2", "--
 
 
 @pytest.fixture(scope="module")
-def emulated_runs(hostemu_lib):
-    """smoke(), bench.py on one rank and bench.py on two gloo ranks, started together (four processes) and collected once."""
+def emulated_runs(hostemu_lib, tmp_path_factory):
+    """smoke(), bench.py --full on one rank and a plain bench.py on two gloo ranks, started together (four processes) and collected once."""
     import socket
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     procs = {"smoke": _run_emulated(["-c", "import __graft_entry__ as g; g.smoke(); print('smoke ok')"], hostemu_lib),
-             "bench1": _run_emulated(["bench.py", "--batch", "1"] + BENCH_SMALLEST, hostemu_lib)}
-    args = ["bench.py", "--gpus", "2", "--batch", "2", "--no-roofline", "--no-cpu-baseline", "--verify-shards"] + BENCH_SMALLEST
+             "bench1": _run_emulated(["bench.py", "--full", "--batch", "1"] + BENCH_SMALLEST, hostemu_lib)}
+    dump = str(tmp_path_factory.mktemp("bench_dump"))
+    args = ["bench.py", "--gpus", "2", "--batch", "2", "--verify-shards", "--dump-outputs", dump] + BENCH_SMALLEST
     env = {"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "WORLD_SIZE": "2", "LOCAL_WORLD_SIZE": "2", "SDMI_DIST_BACKEND": "gloo", "LOCAL_RANK": "0"}
     for r in range(2):
         procs[f"rank{r}"] = _run_emulated(args, hostemu_lib, dict(env, RANK=str(r)))
@@ -83,6 +84,7 @@ def emulated_runs(hostemu_lib):
     for name, pr in procs.items():
         out, err = pr.communicate(timeout=900)
         res[name] = (pr.returncode, out.decode(errors="replace"), err.decode(errors="replace")[-3000:])
+    res["dump"] = dump
     return res
 
 
@@ -93,7 +95,7 @@ def test_smoke_entry_on_the_emulated_library(emulated_runs):
 
 
 def test_bench_py_end_to_end_on_the_emulated_library(emulated_runs):
-    """bench.py itself, one rank, tiny model: the timed loop, the per-launch profile behind the roofline block (launch names from the
+    """bench.py --full itself, one rank, tiny model: the timed loop, the per-launch profile behind the roofline block (launch names from the
     emulation's profiler stand-in; its times are host time and mean nothing), the CPU-baseline leg, the one JSON line of the contract."""
     import json
     rc, out, err = emulated_runs["bench1"]
@@ -121,3 +123,19 @@ def test_bench_py_two_ranks_over_gloo_on_the_emulated_library(emulated_runs):
     assert line["config"]["shard_check"] == "ok", line["config"]["shard_check"]
     assert line["config"]["weights_broadcast_ms"] > 0 and line["value"] > 0
     assert not [ln for ln in out1.splitlines() if ln.startswith("{")]           # only rank 0 prints the line
+
+
+def test_plain_bench_py_measures_only_the_timed_steps_and_dumps_the_last_job(emulated_runs):
+    """A run without --full: no roofline block, CPU baseline or re-timing in the line, and --dump-outputs leaves the last timed job's
+    gathered uint8 images (the whole global batch, on rank 0) as float32 images.npy."""
+    import json
+    import numpy as np
+    rc0, out0, err0 = emulated_runs["rank0"]
+    assert rc0 == 0, err0
+    line = json.loads([ln for ln in out0.splitlines() if ln.startswith("{")][-1])
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["ms_per_step"] > 0 and line["steps"] == 1
+    assert line["config"]["dropin_images_per_s"] is None and line["config"]["accuracy_mode_images_per_s"] is None
+    assert sorted(os.listdir(emulated_runs["dump"])) == ["images.npy"]
+    images = np.load(os.path.join(emulated_runs["dump"], "images.npy"))
+    assert images.dtype == np.float32 and images.ndim == 4 and images.shape[0] == 4 and images.shape[3] == 3     # (the tiny VAE upsamples 2x)
+    assert np.array_equal(images, np.round(images)) and images.min() >= 0 and images.max() <= 255 and images.std() > 0

@@ -1127,11 +1127,43 @@ def test_bench_pmc_child_command_line(monkeypatch):
     assert args.pmc_traffic is None                       # resolved in main(): on for the named c1 workload where rocprofv3 exists
     monkeypatch.setattr(sys, "argv", ["bench.py", "--no-pmc-traffic"])
     assert bench.parse().pmc_traffic is False
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--pmc-traffic"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--pmc-traffic"])
     assert bench.parse().pmc_traffic is True
     path = os.path.join(ROOT, "gpurun_out", "pmc_traffic.json")
     if not os.path.exists(path):
         assert bench.pmc_traffic(args) == (None, None)
+
+
+def test_bench_full_flag_and_the_output_dump(monkeypatch, tmp_path):
+    """Everything besides the timed steps is behind --full (the PMC passes included: asking for them alone is an error), --steps is the
+    number of timed jobs, and --dump-outputs writes the last job's uint8 images as float32 — whole below the cap, above it a seeded sample
+    of fixed positions, so that two runs of the same arguments compare element for element."""
+    monkeypatch.syspath_prepend(ROOT)
+    monkeypatch.delenv("SDMI_BENCH_FULL", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    bench = importlib.import_module("bench")
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "7", "--dump-outputs", str(tmp_path)])
+    args = bench.parse()
+    assert args.full and args.steps == 7 and args.dump_outputs == str(tmp_path)
+    for bad in (["--pmc-traffic"], ["--steps", "0"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse()
+    assert "--full" not in bench.pmc_child_args(["--full", "--dump-outputs", "d", "--config", "c2"])
+    assert "--dump-outputs" not in bench.pmc_child_args(["--full", "--dump-outputs", "d", "--config", "c2"])
+
+    rng = np.random.default_rng(3)
+    res = types.SimpleNamespace(images=[rng.integers(0, 256, (16, 16, 3), dtype=np.uint8) for _ in range(3)])
+    assert bench.dump_outputs(res, str(tmp_path / "whole")) == {"images": [3, 16, 16, 3]}
+    whole = np.load(tmp_path / "whole" / "images.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, np.stack(res.images).astype(np.float32))
+    cap = whole.nbytes // 2
+    for d in ("a", "b"):
+        assert bench.dump_outputs(res, str(tmp_path / d), cap_bytes=cap) == {"images_sample": [cap // 2 // 4]}
+    a, b = np.load(tmp_path / "a" / "images_sample.npy"), np.load(tmp_path / "b" / "images_sample.npy")
+    assert a.dtype == np.float32 and a.nbytes <= cap and np.array_equal(a, b)
+    assert os.listdir(tmp_path / "a") == ["images_sample.npy"] and np.isin(a, whole).all()
 
 
 def test_restart_plan_matches_the_pinned_oracle_restatement():

@@ -3,11 +3,12 @@
 #   tag    prefix of the summaries written under profiles/ (r05, ...)
 #   what   suite    the whole GPU suite with SDMI_PARITY_FULL=1 (or the tests selected by the third argument)
 #          close    suite + __graft_entry__.smoke() + the driver's bench command (python bench.py --gpus 1 --steps 20 --warmup 5)
-#          c1       smoke, the default bench line (CPU baseline, same-run PMC traffic), rocprofv3 --kernel-trace --stats and the
+#          c1       smoke, the --full bench line (CPU baseline, same-run PMC traffic), rocprofv3 --kernel-trace --stats and the
 #                   MFMA-utilisation PMC pass of the C1 job, summaries through tools/summarize_profiles.py
 #          stats    the rocprofv3 kernel-trace stats of the C1 job only
-#          configs  bench line (+ PMC traffic) and rocprofv3 stats of c2 / c3 / c4a / c4b
+#          configs  --full bench line (+ PMC traffic) and rocprofv3 stats of c2 / c3 / c4a / c4b
 #          micro    the C-ABI-only checks (conv_check, ring_check, hipblaslt_yardstick) and the torch-free forward profile (fwd_ab.py)
+# (c1 and configs export SDMI_BENCH_FULL=1: every bench.py call of theirs runs as bench.py --full)
 # (rounds 2-4 ran these steps from per-round copies of this script; their outputs are the profiles/r0N_* files.)
 export TMPDIR=/tmp
 REPO=$(pwd)
@@ -38,6 +39,7 @@ case "$WHAT" in
   stats)
     stats; python tools/summarize_profiles.py $TAG > gpurun_out/summarize.log 2>&1; tail -3 gpurun_out/summarize.log; trim ;;
   c1)
+    export SDMI_BENCH_FULL=1
     smoke
     timeout 900 python bench.py > gpurun_out/bench_default.log 2>&1
     echo "bench rc=$?" >> gpurun_out/bench_default.log; tail -2 gpurun_out/bench_default.log | cut -c1-2500
@@ -47,6 +49,7 @@ case "$WHAT" in
     echo "pmc mfma rc=$?" >> gpurun_out/prof_pmc_mfma.log
     python tools/summarize_profiles.py $TAG > gpurun_out/summarize.log 2>&1; tail -2 gpurun_out/summarize.log; trim ;;
   configs)
+    export SDMI_BENCH_FULL=1
     for c in c2 c3 c4a c4b; do
       timeout 1500 python bench.py --config $c --steps 2 --warmup 1 --no-cpu-baseline --pmc-traffic > gpurun_out/bench_$c.log 2>&1
       echo "bench rc=$?" >> gpurun_out/bench_$c.log; tail -2 gpurun_out/bench_$c.log | cut -c1-400

@@ -2,6 +2,7 @@
 # round-2 measurement pass: bench line (with cpu baseline) + rocprofv3 kernel-trace stats + PMC (HBM traffic, MFMA) passes of the SAME
 # workload, then the summaries under profiles/ and a second bench line that carries the measured traffic.
 export TMPDIR=/tmp
+export SDMI_BENCH_FULL=1          # every bench.py call below runs as bench.py --full (roofline, PMC traffic, CPU baseline)
 REPO=$(pwd)
 mkdir -p gpurun_out
 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; tail -1 gpurun_out/smoke.log
