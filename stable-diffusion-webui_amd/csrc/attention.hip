@@ -62,14 +62,20 @@ __device__ __forceinline__ float tree_max(const f16v (&sc)[NKB]) {
 //      half-wave max exchange is one v_permlane32_swap instead of a ds_bpermute round trip; 160 VGPRs, 3 workgroups per CU.
 //      Same products in the same order per accumulator: bit-identical to 0 and 5 (tests/test_gpu_ops.py).
 //  10..14, 18  (-DSDMI_ATTN_PARTS builds only, tools/gpu/attn_parts.py) 5 with one component removed / 15 with section timers
+// FOLD forms: the softmax scale c = scale * log2(e) is split as c = 2^e * fr, fr in [1, 2).  Q is multiplied by 2^e — EXACT in fp16, where
+// rounding Q * c to fp16 put a relative 2^-11 of every product q_i k_i into the score: 3.9e-3 on a query row that meets one key of 6x
+// the usual norm (tests/test_gpu_ops.py::test_attention_role_offset_kernel, per-row assertion) — and fr multiplies the accumulator in
+// front of exp2 (one v_pk_mul_f32 per two scores where the unfolded forms have a v_pk_fma_f32; the shift bookkeeping stays folded).
+__device__ __forceinline__ float fold_p2(float c) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, c) & 0x7F800000u); }
+
 template <int D, int KVT, int VAR = 0>
 __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR == 18) ? 3 : (VAR == 5 || VAR >= 10) ? 4 : D <= 80 ? 2 : 1)) void attn_mfma_kernel(AttnP p) {
     constexpr bool LAZY_RESCALE = VAR >= 5;
     constexpr bool PREF = VAR == 15 || VAR == 16 || VAR == 17 || VAR == 18;
     // 17 = 15 with the softmax scale and shift folded into the S^T MFMA (head sizes with a spare contraction column: d = 40 -> 48), as in
-    // attn_pp_kernel's FOLD form: Q is multiplied by scale * log2(e) when its fragments are loaded, K's padding column holds 1.0 and Q's
-    // padding element -shift, so the accumulators ARE s * c - shift and exp2 applies to them directly: the 16 v_pk_fma_f32 per tile and
-    // the per-tile alpha bookkeeping disappear (20 of the 92 VALU instructions of a tile).  shift is an fp16 number >= every score seen
+    // attn_pp_kernel's FOLD form: Q is multiplied by the power-of-two part of scale * log2(e) when its fragments are loaded (fold_p2), K's
+    // padding column holds 1.0 and Q's padding element -shift, so the accumulators ARE s * 2^e - shift and exp2 applies to fr times them:
+    // the per-tile alpha bookkeeping disappears and the 16 v_pk_fma_f32 per tile become 16 v_pk_mul_f32.  shift is an fp16 number >= every score seen
     // so far (P <= 1); it is raised — scores re-based, O rescaled, Q's padding element rewritten — only when a tile's maximum exceeds it.
     constexpr bool FOLD = VAR == 17 && ((D + 15) / 16 * 16) > D;
     constexpr bool TREEMAX = VAR == 16;      // 16 = 15 with the tile maximum taken as a v_max3 tree (serial depth 4 instead of 16)
@@ -135,7 +141,7 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
             if (qok && d < D) v = *reinterpret_cast<const h8*>(qptr + d);
             if constexpr (FOLD) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] * p.scale_log2);
+                for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] * fold_p2(p.scale_log2));      // exact: a power of two
             }
             qf[dc] = v;
         }
@@ -294,7 +300,9 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
         h8 pb[NKB][2];
         long long tc = 0;
         if constexpr (FOLD) {
-            // the accumulators are s * c - shift already
+            // the accumulators are t = s * 2^e - shift already; the exponent is fr * t
+            const float fr = p.scale_log2 / fold_p2(p.scale_log2);
+            const f2v fr2 = {fr, fr};
             float mx = -INFINITY;
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
@@ -305,7 +313,7 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
             mx = fmaxf(mlo, mhi);
             // per query; the first tile always sets the shift (it may be negative); later tiles raise it only when a score exceeds it by
             // more than tau (AttnP::tau: P <= 2^tau until then)
-            const bool up = t == 0 || mx > fmaxf(p.tau, 0.f);
+            const bool up = t == 0 || mx * fr > fmaxf(p.tau, 0.f);
             if (__builtin_amdgcn_ballot_w64(up) != 0) {
                 asm volatile("");                                 // a real (wave-uniform) branch: rare after the first few tiles
                 // new shift = the smallest fp16 number >= shift + mx (both halves of the wave compute the same value for a query)
@@ -320,7 +328,7 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
                 }
                 const float delta = up ? f - shift : 0.f;         // exact: both are fp16 numbers
                 if (up) shift = f;
-                const float alpha = __builtin_amdgcn_exp2f(-delta);
+                const float alpha = __builtin_amdgcn_exp2f(-delta * fr);
 #pragma unroll
                 for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
@@ -335,8 +343,9 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
-                    pb[kb][r >> 3][r & 7] = (half_t)__builtin_amdgcn_exp2f(sc[kb][r]);
-                    pb[kb][r >> 3][(r & 7) + 1] = (half_t)__builtin_amdgcn_exp2f(sc[kb][r + 1]);
+                    const f2v y = f2v{sc[kb][r], sc[kb][r + 1]} * fr2;               // v_pk_mul_f32
+                    pb[kb][r >> 3][r & 7] = (half_t)__builtin_amdgcn_exp2f(y.x);
+                    pb[kb][r >> 3][(r & 7) + 1] = (half_t)__builtin_amdgcn_exp2f(y.y);
                 }
         } else {
         float mx = -INFINITY;
@@ -474,7 +483,7 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
 // its first read and overwritten two sections or more after its last (schedule in the body).
 //
 // FOLD (head sizes with a spare contraction column, d = 40 -> 48): the softmax shift costs no VALU.  Q is multiplied by
-// scale * log2(e) when its fragments are loaded (one fp16 rounding of q * c instead of q), K's padding column holds 1.0 and Q's padding
+// the power-of-two part of scale * log2(e) when its fragments are loaded (exact: fold_p2), K's padding column holds 1.0 and Q's padding
 // element holds -shift, so the S^T MFMA itself delivers s * c - shift: the 16 v_pk_fma_f32 per tile (a fifth of the VALU section; the
 // most expensive VALU form beside another wave's MFMAs, profiles/r02_valu_rates.txt) disappear and exp2 is applied to the accumulators
 // directly.  The shift is an fp16 number (softmax is invariant to it as long as O, the denominator and P use the same one); it is
@@ -545,7 +554,7 @@ __global__ __launch_bounds__(NG * 256, NG) void attn_pp_kernel(AttnP p) {
             if (qok && d < D) v = *reinterpret_cast<const h8*>(qptr + d);
             if constexpr (FOLD) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = (half_t)((float)v[j] * p.scale_log2);
+                for (int j = 0; j < 8; ++j) v[j] = (half_t)((float)v[j] * fold_p2(p.scale_log2));      // exact: a power of two
             }
             qf[dc] = v;
         }
@@ -680,6 +689,8 @@ __global__ __launch_bounds__(NG * 256, NG) void attn_pp_kernel(AttnP p) {
     float shift = FOLD ? 0.f : -1e30f;
     f2v l_run = {0.f, 0.f};
     const f2v sl2 = {p.scale_log2, p.scale_log2};
+    [[maybe_unused]] const float fr = p.scale_log2 / fold_p2(p.scale_log2);      // FOLD: the accumulators are t = s * 2^e - shift, the exponent fr * t
+    [[maybe_unused]] const f2v fr2 = {fr, fr};
     h8 pb[NKB][2];
     h8 kaf[NDC][NKB], vaf[NDB][NKB][2];
 
@@ -718,7 +729,7 @@ __global__ __launch_bounds__(NG * 256, NG) void attn_pp_kernel(AttnP p) {
                 const float delta = ns - shift;               // exact: both are fp16 numbers
                 shift = ns;
                 if (t > 0) {
-                    const float alpha = __builtin_amdgcn_exp2f(-delta);
+                    const float alpha = __builtin_amdgcn_exp2f(-delta * fr);
 #pragma unroll
                     for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -753,7 +764,8 @@ __global__ __launch_bounds__(NG * 256, NG) void attn_pp_kernel(AttnP p) {
             for (int r = 0; r < 16; r += 2) {
                 f2v e;
                 if constexpr (FOLD) {
-                    e = f2v{__builtin_amdgcn_exp2f(sc[kb][r]), __builtin_amdgcn_exp2f(sc[kb][r + 1])};
+                    const f2v y = f2v{sc[kb][r], sc[kb][r + 1]} * fr2;               // v_pk_mul_f32
+                    e = f2v{__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)};
                 } else {
                     const f2v s2 = {sc[kb][r], sc[kb][r + 1]};
                     const f2v y = __builtin_elementwise_fma(s2, sl2, mneg);

@@ -107,8 +107,8 @@ struct GemmP {
     int splitk_steps;     // BK-steps per slice
     long long* dbg;       // tuning only: per-wave section timers of the ping-pong kernel (sdmi_debug_set gemm_dbg_lo/hi)
     // GroupNorm statistics of the OUTPUT tensor from this launch's epilogue (drops the consumer's statistics pass): per
-    // (image, row chunk = this tile's BM rows, group) the sum and sum of squares of the fp16-rounded outputs, written to
-    // stats_out[((b * stats_nchunk + chunk) * (N / stats_cpg) + g) * 2 + {0, 1}] — the layout gn_apply's prologue reduces.
+    // (image, row chunk = this tile's BM rows, group) the mean and the centred sum of squares (M2) of the fp16-rounded outputs, written to
+    // stats_out[((b * stats_nchunk + chunk) * (N / stats_cpg) + g) * 2 + {0, 1}] — the layout gn_apply's prologue merges.
     // Deterministic: registers -> 16-lane shuffle tree -> LDS -> one thread per group, all in fixed order.
     float* stats_out;
     int stats_cpg;        // channels per group of the consumer's GroupNorm
@@ -231,7 +231,7 @@ int launch_rowchain_ff(const half_t* x, half_t* out, const float* gamma, const f
                        long rows, int C, int hidden, float eps, hipStream_t s);
 
 // ---- norms ------------------------------------------------------------------------------------------------
-// pre_nchunk > 0: `ws` already holds partial sums [B][pre_nchunk][groups][2] (written by the producing GEMM): skip the statistics pass
+// pre_nchunk > 0: `ws` already holds (mean, M2) [B][pre_nchunk][groups][2] of HW / pre_nchunk rows each (written by the producing GEMM): skip the statistics pass
 // x0_lo / x1_lo (engine option "residual_fp32"): the lo parts when the inputs are (hi, lo) fp16 pairs of the carried stream
 int launch_groupnorm(const half_t* x0, const half_t* x1, int c0, int c1, const float* gamma, const float* beta,
                      half_t* out, int B, int HW, int groups, float eps, bool silu, float* ws, hipStream_t s, int pre_nchunk = 0,

@@ -84,13 +84,47 @@ __device__ __forceinline__ void swap16(h4& x, h4& y) {
 }
 __device__ __forceinline__ h8 join8(h4 lo, h4 hi) { return h8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}; }
 
+// GroupNorm statistics of a STATS epilogue, without ever forming sum(x^2) / n - mean^2 (norm.hip's note).  A lane keeps, for each of its 4
+// channels, the sums of (v - k) and (v - k)^2 over its TM rows around k = its first row's value.  gn_cols_of_wave turns them into the
+// (mean, M2) of the lane's rows and merges the 16 lanes that share the channels (equal counts: mean = (a + b) / 2,
+// M2 = M2a + M2b + (b - a)^2 * count / 2) -> per wave and channel over its 16 TM rows.  gn_group_of_tile: one thread per group,
+// over the group's WR x cpg slots in a fixed order: the mean of the slot means, then M2 = sum of M2_slot + rows * (mean_slot - mean)^2.
+// Every tile is full (launch_gemm's admission rule: rows_per_batch % BM == 0), so the counts are the geometry's.
+__device__ __forceinline__ void gn_cols_of_wave(f4& sv, f4& qv, const f4& kv, int tm) {
+    const float inv = 1.0f / (float)tm;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { const float a = sv[r]; sv[r] = fmaf(a, inv, kv[r]); qv[r] = fmaxf(qv[r] - a * a * inv, 0.f); }
+    float half_cnt = 0.5f * (float)tm;
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float d = __shfl_xor(sv[r], off) - sv[r], qb = __shfl_xor(qv[r], off);
+            sv[r] = fmaf(0.5f, d, sv[r]);
+            qv[r] = (qv[r] + qb) + d * d * half_cnt;
+        }
+        half_cnt *= 2.f;
+    }
+}
+__device__ __forceinline__ void gn_group_of_tile(const float* cs, const float* cq, int wrn, int bn, int c_lo, int cpg, float rows, float* dst) {
+    const float pv = cs[c_lo];
+    float a = 0.f;
+    for (int w = 0; w < wrn; ++w)
+        for (int c = c_lo; c < c_lo + cpg; ++c) a += cs[w * bn + c] - pv;
+    const float mean = pv + a / (float)(wrn * cpg);
+    float q = 0.f;
+    for (int w = 0; w < wrn; ++w)
+        for (int c = c_lo; c < c_lo + cpg; ++c) { const float d = cs[w * bn + c] - mean; q += fmaf(rows * d, d, cq[w * bn + c]); }
+    dst[0] = mean; dst[1] = q;
+}
+
 // (hi, lo) stream tensors (EP_HILO, engine option "residual_fp32"): the epilogue of a launch whose output and / or residual is a pair of
 // fp16 tensors, x = hi + lo (GemmP).  A SEPARATE region, entered from gemm_epilogue behind one block-uniform branch, so that the default
 // path's code and register allocation stay what they were (round 6: the same handling written into the default path's loops cost the
 // 256x320 instantiations 40-155 VGPR spills).  Row-tile pairs in the 16-byte layout (swap16), column tile outer so that the
 // GroupNorm-statistics form keeps 8 live sums, the (hi, lo) residual of pair a + 1 requested before pair a is converted and stored.
 // v = alpha * acc + bias_scale * bias [+ rowbias] [+ resid_hi + resid_lo];  hi = fp16(v), lo = fp16(v - hi);  STATS: per (image, row
-// chunk, group) sums of hi + lo — what the consumer's GroupNorm reads — in gemm_epilogue's layout and (fixed) order.
+// chunk, group) mean and centred sum of squares of hi + lo — what the consumer's GroupNorm reads — in gemm_epilogue's layout and (fixed) order.
 template <int TM, int TN, int WTM, int WTN, int WR_, int BN_, bool STATS>
 __device__ __forceinline__ void gemm_epilogue_hilo(const GemmP& p, f4 (&acc)[TM][TN], int m0, int n0, int wr, int wc, int lane, long z,
                                                    char* smem) {
@@ -200,7 +234,7 @@ __device__ __forceinline__ void gemm_epilogue_hilo(const GemmP& p, f4 (&acc)[TM]
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const f4 bb = col_bias(j);
-        f4 sv = {0.f, 0.f, 0.f, 0.f}, qv = {0.f, 0.f, 0.f, 0.f};
+        f4 sv = {0.f, 0.f, 0.f, 0.f}, qv = {0.f, 0.f, 0.f, 0.f}, kv = {0.f, 0.f, 0.f, 0.f};
         h8 rh = p.resid ? ld(p.resid, 0, j) : z8, rl = rlo ? ld(rlo, 0, j) : z8;
 #pragma unroll
         for (int a = 0; a < TM / 2; ++a) {
@@ -212,25 +246,22 @@ __device__ __forceinline__ void gemm_epilogue_hilo(const GemmP& p, f4 (&acc)[TM]
             f4 vx, vy;
             h4 ox, oy, lx, ly;
             cell(a, j, bb, ch, cl, vx, vy, ox, oy, lx, ly);
-            const bool okx = mrow + 2 * a * 16 < p.M, oky = mrow + (2 * a + 1) * 16 < p.M;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float f = okx ? (float)ox[r] + (float)lx[r] : 0.f;
+                if (a == 0) kv[r] = (float)ox[r] + (float)lx[r];
+                const float f = ((float)ox[r] + (float)lx[r]) - kv[r];
                 sv[r] += f;
                 qv[r] = fmaf(f, f, qv[r]);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float f = oky ? (float)oy[r] + (float)ly[r] : 0.f;
+                const float f = ((float)oy[r] + (float)ly[r]) - kv[r];
                 sv[r] += f;
                 qv[r] = fmaf(f, f, qv[r]);
             }
             store(a, j, ox, oy, lx, ly);
         }
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { sv[r] += __shfl_xor(sv[r], off); qv[r] += __shfl_xor(qv[r], off); }
+        gn_cols_of_wave(sv, qv, kv, TM);
         if ((lane & 15) == 0) {
             const int c = wc * WTN + j * 16 + (lane >> 4) * 4;
             *reinterpret_cast<f4*>(cs + wr * BN_ + c) = sv;
@@ -240,14 +271,10 @@ __device__ __forceinline__ void gemm_epilogue_hilo(const GemmP& p, f4 (&acc)[TM]
     __syncthreads();
     const int tid = threadIdx.x, cpg = p.stats_cpg, ngl = BN_ / cpg;
     if (tid < ngl) {
-        float a = 0.f, q = 0.f;
-        for (int w = 0; w < WR_; ++w)
-            for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) { a += cs[w * BN_ + c]; q += cq[w * BN_ + c]; }
         const int b = m0 / p.rows_per_batch;                 // (a tile lies inside one image: launch_gemm's admission rule)
         const int chunk = (m0 - b * p.rows_per_batch) / (TM * 16 * WR_);
         const int G = p.N / cpg, g = n0 / cpg + tid;
-        float* dst = p.stats_out + (((long)b * p.stats_nchunk + chunk) * G + g) * 2;
-        dst[0] = a; dst[1] = q;
+        gn_group_of_tile(cs, cq, WR_, BN_, tid * cpg, cpg, (float)(TM * 16), p.stats_out + (((long)b * p.stats_nchunk + chunk) * G + g) * 2);
     }
 }
 
@@ -391,9 +418,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f4 (&acc)[TM][TN],
         // an optional [B][N] row bias and an optional residual).  Column tile OUTER, row tile inner: the lane's column sums over
         // its TM rows are then 8 live values (one column tile at a time) instead of 8 x TN next to the accumulators, and the
         // residual pipeline is a 4-deep ring of 8-byte loads.  After each column tile: 16-lane shuffle tree over the rows of the
-        // wave (lanes sharing lane >> 4 own the same 4 channels), LDS [WR][BN] per wave row; at the end one thread per group adds
-        // its WR x cpg slots in a fixed order and writes (sum, sum of squares) for (image, row chunk, group).
-        // The sums are taken from the fp16-ROUNDED outputs: exactly what gn_stats would have read back.
+        // wave (lanes sharing lane >> 4 own the same 4 channels), LDS [WR][BN] per wave row; at the end one thread per group merges
+        // its WR x cpg slots in a fixed order and writes (mean, centred sum of squares) for (image, row chunk, group)
+        // (gn_cols_of_wave / gn_group_of_tile).
+        // The statistics are taken from the fp16-ROUNDED outputs: exactly what gn_stats would have read back.
         float* cs = reinterpret_cast<float*>(smem);          // [WR_][BN_] sums, then [WR_][BN_] sums of squares
         float* cq = cs + WR_ * BN_;
         __syncthreads();                                     // every wave is done reading the operand tiles that lived here
@@ -412,7 +440,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f4 (&acc)[TM][TN],
                 for (int r = 0; r < 4; ++r) bb[r] *= p.bias_scale;
             }
             if (p.rowbias) bb += *reinterpret_cast<const f4*>(p.rowbias + (long)b * p.ldrb + n);
-            f4 sv = {0.f, 0.f, 0.f, 0.f}, qv = {0.f, 0.f, 0.f, 0.f};
+            f4 sv = {0.f, 0.f, 0.f, 0.f}, qv = {0.f, 0.f, 0.f, 0.f}, kv = {0.f, 0.f, 0.f, 0.f};
             if constexpr (TM % 2 == 0) {
                 if (wide) {
                     // row-tile pairs, residual and output in the 16-byte layout (swap16); the sums are taken in the accumulator
@@ -441,18 +469,18 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f4 (&acc)[TM][TN],
                             for (int r = 0; r < 4; ++r) { vx[r] += (float)rx[r]; vy[r] += (float)ry[r]; }
                         }
                         h4 ox, oy;
-                        const bool okx = mrow + 2 * a * 16 < p.M, oky = mrow + (2 * a + 1) * 16 < p.M;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             ox[r] = (half_t)vx[r];
-                            const float f = okx ? (float)ox[r] : 0.f;
+                            if (a == 0) kv[r] = (float)ox[r];
+                            const float f = (float)ox[r] - kv[r];
                             sv[r] += f;
                             qv[r] = fmaf(f, f, qv[r]);
                         }
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             oy[r] = (half_t)vy[r];
-                            const float f = oky ? (float)oy[r] : 0.f;
+                            const float f = (float)oy[r] - kv[r];
                             sv[r] += f;
                             qv[r] = fmaf(f, f, qv[r]);
                         }
@@ -487,7 +515,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f4 (&acc)[TM][TN],
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         o[r] = (half_t)v[r];
-                        const float f = (float)o[r];
+                        if (i == 0) kv[r] = (float)o[r];
+                        const float f = (float)o[r] - kv[r];
                         sv[r] += f;
                         qv[r] = fmaf(f, f, qv[r]);
                     }
@@ -495,10 +524,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f4 (&acc)[TM][TN],
                 }
             }
             }
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { sv[r] += __shfl_xor(sv[r], off); qv[r] += __shfl_xor(qv[r], off); }
+            gn_cols_of_wave(sv, qv, kv, TM);
             if ((lane & 15) == 0) {
                 const int c = wc * WTN + j * 16 + (lane >> 4) * 4;
                 *reinterpret_cast<f4*>(cs + wr * BN_ + c) = sv;
@@ -508,13 +534,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f4 (&acc)[TM][TN],
         __syncthreads();
         const int tid = threadIdx.x, cpg = p.stats_cpg, ngl = BN_ / cpg;
         if (tid < ngl) {
-            float a = 0.f, q = 0.f;
-            for (int w = 0; w < WR_; ++w)
-                for (int c = tid * cpg; c < (tid + 1) * cpg; ++c) { a += cs[w * BN_ + c]; q += cq[w * BN_ + c]; }
             const int chunk = (m0 - b * p.rows_per_batch) / (TM * 16 * WR_);
             const int G = p.N / cpg, g = n0 / cpg + tid;
-            float* dst = p.stats_out + (((long)b * p.stats_nchunk + chunk) * G + g) * 2;
-            dst[0] = a; dst[1] = q;
+            gn_group_of_tile(cs, cq, WR_, BN_, tid * cpg, cpg, (float)(TM * 16), p.stats_out + (((long)b * p.stats_nchunk + chunk) * G + g) * 2);
         }
         return;
     }

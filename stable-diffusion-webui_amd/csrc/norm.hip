@@ -4,13 +4,16 @@
 // (/root/reference/modules/sd_hijack.py:69), and — by reading TWO channel-concatenated sources and writing one tensor —
 // the torch.cat of UNet skip connections (/root/reference/modules/sd_hijack_unet.py:10-33).  Both kernels are HBM-bound:
 // every access is a 16-byte (8 x fp16) vector, rows are read fully coalesced, and the statistics pass writes only
-// per-(image, chunk, group) partial sums (no atomics => bit-reproducible).
+// per-(image, chunk, group) partial statistics (no atomics => bit-reproducible).
 //   pass 1  gn_stats : grid (chunks, B); a block owns `rows` pixels x all channels; thread t keeps per-channel
 //                      sum / sum-of-squares of its 8-channel vector in registers, stores them in its own LDS slot
-//                      (one writer per slot), then 1 thread per group reduces its channels in a fixed order
-//                      -> partial[b][chunk][g] = (sum, sumsq)
-//   pass 2  gn_apply : grid (blocks, B); prologue reduces the partials to mean / rstd per group in LDS, then a
+//                      (one writer per slot), then 8 lanes per group reduce its channels in a fixed order
+//                      -> partial[b][chunk][g] = (mean, M2) of the chunk's elements of the group, M2 = sum (x - mean)^2
+//   pass 2  gn_apply : grid (blocks, B); prologue merges the chunks' (mean, M2) in chunk order (Chan et al.: the element count
+//                      of a chunk follows from the geometry) to mean / rstd per group in LDS, then a
 //                      grid-stride elementwise pass y = silu((x - mean) * rstd * gamma + beta).
+// No pass forms sum(x^2) / n - mean^2: that difference loses (mean / std)^2 of the fp32 mantissa, 1e-2 of the output at a group
+// whose mean is 300 standard deviations.  Every sum of squares is taken around a value of the data itself.
 // LayerNorm: one wave per token row, row held in registers, two-pass (mean, then centred variance) in fp32.
 #include "common.h"
 #include "prof.h"
@@ -46,10 +49,21 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* x0, const h
             if (c < c0) { src = x0; cc = c; ld = c0; } else { src = x1; cc = c - c0; ld = c1; }
             const half_t* base = src + (long)b * HW * ld + cc;
             [[maybe_unused]] const half_t* lbase = HILO ? (c < c0 ? l0 : l1) + (long)b * HW * ld + cc : nullptr;
-            float a[8], q[8];
+            // sums of (x - k) and (x - k)^2 around the thread's FIRST value k of the channel: k lies inside the data, so the sum of
+            // squares carries the spread and not the offset
+            float a[8], q[8], k[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { a[e] = 0.f; q[e] = 0.f; }
+            for (int e = 0; e < 8; ++e) { a[e] = 0.f; q[e] = 0.f; k[e] = 0.f; }
             int pix = p_begin + tr;
+            const int n_t = pix < p_end ? (p_end - pix + R - 1) / R : 0;        // pixels this thread reads
+            if (pix < p_end) {
+                const h8 v = *reinterpret_cast<const h8*>(base + (long)pix * ld);
+                h8 lv = {0, 0, 0, 0, 0, 0, 0, 0};
+                if constexpr (HILO) lv = *reinterpret_cast<const h8*>(lbase + (long)pix * ld);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) k[e] = HILO ? (float)v[e] + (float)lv[e] : (float)v[e];
+                pix += R;
+            }
             // 4 independent 16-byte loads in flight per thread (the pass is pure streaming: latency must be covered by ILP)
             for (; pix + 3 * R < p_end; pix += 4 * R) {
                 h8 v[4];
@@ -60,7 +74,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* x0, const h
                     h8 lv = {0, 0, 0, 0, 0, 0, 0, 0};
                     if constexpr (HILO) lv = *reinterpret_cast<const h8*>(lbase + (long)(pix + u * R) * ld);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { const float f = HILO ? (float)v[u][e] + (float)lv[e] : (float)v[u][e]; a[e] += f; q[e] = fmaf(f, f, q[e]); }
+                    for (int e = 0; e < 8; ++e) { const float f = (HILO ? (float)v[u][e] + (float)lv[e] : (float)v[u][e]) - k[e]; a[e] += f; q[e] = fmaf(f, f, q[e]); }
                 }
             }
             for (; pix < p_end; pix += R) {
@@ -68,28 +82,53 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* x0, const h
                 h8 lv = {0, 0, 0, 0, 0, 0, 0, 0};
                 if constexpr (HILO) lv = *reinterpret_cast<const h8*>(lbase + (long)pix * ld);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { const float f = HILO ? (float)v[e] + (float)lv[e] : (float)v[e]; a[e] += f; q[e] = fmaf(f, f, q[e]); }
+                for (int e = 0; e < 8; ++e) { const float f = (HILO ? (float)v[e] + (float)lv[e] : (float)v[e]) - k[e]; a[e] += f; q[e] = fmaf(f, f, q[e]); }
             }
+            // -> (mean, M2) of the thread's n_t values of each channel; one writer per slot
+            const float inv = n_t > 0 ? 1.0f / (float)n_t : 0.f;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { s_sum[tr * C + c + e] = a[e]; s_sq[tr * C + c + e] = q[e]; }   // one writer per slot
+            for (int e = 0; e < 8; ++e) { s_sum[tr * C + c + e] = fmaf(a[e], inv, k[e]); s_sq[tr * C + c + e] = fmaxf(q[e] - a[e] * a[e] * inv, 0.f); }
         }
     }
     __syncthreads();
     {
-        // 8 lanes per group walk the group's R x cpg LDS slots in a fixed order, then an 8-lane shuffle tree (deterministic)
+        // 8 lanes per group walk the group's R x cpg LDS slots in a fixed order, then an 8-lane shuffle tree (deterministic) — twice:
+        // the mean of the slot means (weighted by the slots' pixel counts, around the first slot's mean), then
+        // M2 = sum over slots of M2_slot + count_slot * (mean_slot - mean)^2, the exact decomposition of the centred sum of squares
         const int g = tid >> 3, l8 = tid & 7;
         const int cpg = C / groups, n = R * cpg;
-        float a = 0.f, q = 0.f;
+        const int np = max(p_end - p_begin, 0);                // pixels of this chunk (an image whose rows do not fill the last chunks: 0)
+        const float pv = g < groups ? s_sum[g * cpg] : 0.f;
+        float a = 0.f;
         if (g < groups)
             for (int i = l8; i < n; i += 8) {
                 const int r = i / cpg, c = g * cpg + (i - r * cpg);
-                a += s_sum[r * C + c]; q += s_sq[r * C + c];
+                a = fmaf((float)max((np - r + R - 1) / R, 0), s_sum[r * C + c] - pv, a);
             }
-        for (int off = 4; off > 0; off >>= 1) { a += __shfl_xor(a, off); q += __shfl_xor(q, off); }
+        for (int off = 4; off > 0; off >>= 1) a += __shfl_xor(a, off);
+        const float mean = np > 0 ? pv + a / ((float)np * (float)cpg) : 0.f;
+        float q = 0.f;
+        if (g < groups)
+            for (int i = l8; i < n; i += 8) {
+                const int r = i / cpg, c = g * cpg + (i - r * cpg);
+                const float d = s_sum[r * C + c] - mean;
+                q += fmaf((float)max((np - r + R - 1) / R, 0) * d, d, s_sq[r * C + c]);
+            }
+        for (int off = 4; off > 0; off >>= 1) q += __shfl_xor(q, off);
         if (g < groups && l8 == 0) {
             float* dst = partial + (((long)b * nchunk + chunk) * groups + g) * 2;
-            dst[0] = a; dst[1] = q;
+            dst[0] = mean; dst[1] = np > 0 ? q : 0.f;
         }
+    }
+}
+
+// Two sets of (count, mean, M2) into one (Chan, Golub, LeVeque 1979); an empty second set changes nothing.
+__device__ __forceinline__ void gn_merge(float& n, float& mean, float& m2, float nb, float mb, float qb) {
+    if (nb > 0.f) {
+        const float r = nb / (n + nb), d = mb - mean;
+        mean = fmaf(d, r, mean);
+        m2 = (m2 + qb) + d * d * n * r;
+        n += nb;
     }
 }
 
@@ -99,7 +138,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* x0, const h
 // (profiles/r05_copy_rate.txt).  The per-channel tables live in dynamic LDS (2 C floats) so that small-C launches keep their occupancy.
 template <bool HILO = false, int U = 8>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* x0, const half_t* x1, int c0, int c1, int HW,
-                                                       int groups, int nchunk, const float* partial,
+                                                       int groups, int nchunk, int chunk_rows, int chunk_period, const float* partial,
                                                        const float* gamma, const float* beta, half_t* out, float eps,
                                                        int silu, const half_t* l0 = nullptr, const half_t* l1 = nullptr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];         // [C] scale | [C] shift (floats)
@@ -149,21 +188,24 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* x0, const h
     };
     request();
     {
-        // 8 threads per group reduce the chunk partials in a fixed order (deterministic), then an 8-lane shuffle tree
+        // 8 threads per group merge the chunks' (mean, M2) in a fixed order (deterministic), then an 8-lane shuffle tree of merges.
+        // Chunk ch holds the rows [j * chunk_rows, (j + 1) * chunk_rows) of HW, j = ch % chunk_period (banded images: chunk_period chunks
+        // per band of HW rows, every band's chunks side by side; otherwise chunk_period = nchunk).
         const int g = tid >> 3, l8 = tid & 7;
-        float a = 0.f, q = 0.f;
+        float n = 0.f, mean = 0.f, m2 = 0.f;
         if (g < groups)
             for (int ch = l8; ch < nchunk; ch += 8) {
                 const float* src = partial + (((long)b * nchunk + ch) * groups + g) * 2;
-                a += src[0]; q += src[1];
+                const int j = ch % chunk_period;
+                gn_merge(n, mean, m2, (float)(max(min(chunk_rows, HW - j * chunk_rows), 0) * cpg), src[0], src[1]);
             }
-        for (int off = 4; off > 0; off >>= 1) { a += __shfl_xor(a, off); q += __shfl_xor(q, off); }
+        for (int off = 4; off > 0; off >>= 1) {
+            const float nb = __shfl_xor(n, off), mb = __shfl_xor(mean, off), qb = __shfl_xor(m2, off);
+            gn_merge(n, mean, m2, nb, mb, qb);
+        }
         if (g < groups && l8 == 0) {
-            const float n = (float)cpg * (float)HW;
-            const float mean = a / n;
-            const float var = fmaxf(q / n - mean * mean, 0.f);
             s_mean[g] = mean;
-            s_rstd[g] = rsqrtf(var + eps);
+            s_rstd[g] = rsqrtf(m2 / n + eps);
         }
     }
     __syncthreads();
@@ -298,8 +340,8 @@ static inline int gn_chunks(int B, int HW) {
 
 // Images beyond the 32-bit offsets of the kernels (HW * C >= 2^31 elements or HW >= 2^24 pixels: a 4096 x 4096 VAE decode at 128 channels)
 // are normalised in `nb` equal bands of rows (nb a power of two dividing HW): per (image, band) one statistics launch over the band as if it
-// were an image of its own, the partial sums of all bands of an image side by side in the workspace and scaled by 1 / nb (exact: a power
-// of two), so that the apply launches — again one per (image, band), each reducing ALL of the image's partials with the band's pixel count —
+// were an image of its own, the chunk statistics of all bands of an image side by side in the workspace, so that the apply launches — again
+// one per (image, band), each merging ALL of the image's chunks (gn_apply_kernel's chunk_period) —
 // normalise with the image's mean and variance.  Host-side only: the kernels are the ones every other tensor runs.
 // g_gn_band_elems (tests): the element limit that triggers banding, so the path runs on small tensors too.
 long g_gn_band_elems = 0;
@@ -340,7 +382,6 @@ static int groupnorm_banded(const half_t* x0, const half_t* x1, int c0, int c1, 
                                groups, rows, ws + b * per_image + (long)k * nchunk_b * groups * 2, nullptr, nullptr);
             SDMI_CHECK_HIP(hipGetLastError());
         }
-    if (launch_axpby(ws, ws, 1.0f / (float)nb, nullptr, 0.f, (int64_t)B * per_image, s)) return 1;
     const long nvec = (long)HWb * (C / 8);
     const long trips = std::max<long>(1, cdiv(nvec, 2048L * 2048));
     int blocks = (int)std::max<long>(1, cdiv(nvec, 2048 * trips));
@@ -350,7 +391,7 @@ static int groupnorm_banded(const half_t* x0, const half_t* x1, int c0, int c1, 
         for (int k = 0; k < nb; ++k) {
             const long row0 = (long)b * HW + (long)k * HWb;
             hipLaunchKernelGGL((gn_apply_kernel<false, 8>), dim3(blocks, 1), dim3(256), smem, s, x0 + row0 * c0, x1 ? x1 + row0 * c1 : nullptr, c0, c1,
-                               HWb, groups, nchunk, ws + b * per_image, gamma, beta, out + row0 * C, eps, silu ? 1 : 0, nullptr, nullptr);
+                               HWb, groups, nchunk, rows, nchunk_b, ws + b * per_image, gamma, beta, out + row0 * C, eps, silu ? 1 : 0, nullptr, nullptr);
             SDMI_CHECK_HIP(hipGetLastError());
         }
     return 0;
@@ -410,10 +451,10 @@ int launch_groupnorm(const half_t* x0, const half_t* x1, int c0, int c1, const f
     if (g_gn_apply_blocks > 0) blocks = g_gn_apply_blocks;       // tests: several trips per thread on a small tensor
     const size_t smem = (size_t)2 * C * sizeof(float);
     if (hilo)
-        hipLaunchKernelGGL((gn_apply_kernel<true, 4>), dim3(blocks, B), dim3(256), smem, s, x0, x1, c0, c1, HW, groups, nchunk, ws, gamma,
+        hipLaunchKernelGGL((gn_apply_kernel<true, 4>), dim3(blocks, B), dim3(256), smem, s, x0, x1, c0, c1, HW, groups, nchunk, rows, nchunk, ws, gamma,
                            beta, out, eps, silu ? 1 : 0, x0_lo, x1_lo);
     else
-        hipLaunchKernelGGL((gn_apply_kernel<false, 8>), dim3(blocks, B), dim3(256), smem, s, x0, x1, c0, c1, HW, groups, nchunk, ws, gamma,
+        hipLaunchKernelGGL((gn_apply_kernel<false, 8>), dim3(blocks, B), dim3(256), smem, s, x0, x1, c0, c1, HW, groups, nchunk, rows, nchunk, ws, gamma,
                            beta, out, eps, silu ? 1 : 0, nullptr, nullptr);
     SDMI_CHECK_HIP(hipGetLastError());
     return 0;

@@ -36,3 +36,40 @@ def usable_cpus(cap=32):
     except Exception:
         n = os.cpu_count() or 1
     return max(1, min(cap, n))
+
+
+def worst_slice_rel_l2(got, ref, keep_dims, min_elems=64):
+    """-> (worst, index): the largest ||got - ref|| / ||ref|| over the slices indexed by the dimensions `keep_dims` (every other dimension
+    is reduced), in float64, and the index of that slice along the kept dimensions.  One global rel_l2 cannot see a single wrong row of a
+    large tensor; this can.  Slices of fewer than `min_elems` elements are pooled with their neighbours along the LAST kept dimension (whole
+    runs of ceil(min_elems / size) consecutive indices, a remainder joining the last run; a dimension too short for that is pooled whole and
+    the pooling goes on along the kept dimension before it): the error of a 40-element slice fluctuates too much to be capped tightly.
+    The index of a pooled slice is that of its first member."""
+    got = torch.as_tensor(got).double()
+    ref = torch.as_tensor(ref).double()
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    keep = [d % ref.ndim for d in keep_dims]
+    assert len(set(keep)) == len(keep) and keep
+    rest = [d for d in range(ref.ndim) if d not in keep]
+    kshape = [ref.shape[d] for d in keep]
+    err2 = ((got - ref) ** 2).permute(keep + rest).reshape(kshape + [-1]).sum(-1)
+    ref2 = (ref ** 2).permute(keep + rest).reshape(kshape + [-1]).sum(-1)
+    size = ref.numel() // max(1, err2.numel())
+    step = [1] * len(keep)                                     # index scale per kept dimension after pooling
+    d = len(keep) - 1
+    while size < min_elems and d >= 0:
+        length = err2.shape[d]
+        run = min(length, -(-min_elems // size))
+        groups = length // run
+
+        def pool(t):
+            t = t.movedim(d, -1)
+            main = t[..., :groups * run].reshape(t.shape[:-1] + (groups, run)).sum(-1)
+            main[..., -1] += t[..., groups * run:].sum(-1)
+            return main.movedim(-1, d)
+        err2, ref2 = pool(err2), pool(ref2)
+        step[d], size, d = run, size * run, d - 1
+    ratio = (err2 / (ref2 + 1e-60)).sqrt()
+    flat = int(ratio.argmax())
+    idx = np.unravel_index(flat, tuple(ratio.shape))
+    return float(ratio.flatten()[flat]), tuple(int(i) * s for i, s in zip(idx, step))

@@ -1638,3 +1638,99 @@ def test_img2img_pil_front_end_fill_only_masked_and_overlay(dev, tiny):
         processing.process_images(processing.StableDiffusionProcessingImg2Img(
             sd_model=tiny["model"], c=cond, uc=uncond, seed=77, batch_size=2, steps=4, cfg_scale=4.0, width=W, height=H, sampler_name="Euler a",
             denoising_strength=0.6, init_images=[base]))
+
+
+# ------------------------------------------------------------------------------------------------------------
+# a checkpoint whose biases put GroupNorm inputs far off zero
+# ------------------------------------------------------------------------------------------------------------
+OFFSET_BIAS = 20.0            # per-group bias offset; sized from the oracle alone (the precondition asserted below)
+VAE_OFFSET_DECODE_MEASURED = 2.616e-03      # engine decode vs fp32 oracle decode on this checkpoint, MI355X (profiles/gn_offset_groups.md)
+
+
+def _offset_heavy_state_dict(schema, ucfg, vcfg):
+    """schema.synthetic_state_dict with one offset of +-OFFSET_BIAS per group of 1/32 of the channels added to the ResBlock conv and
+    embedding biases, conv_in, and the VAE decoder's conv biases: what trained checkpoints have and 0.02 * randn biases do not."""
+    import re
+    sd = schema.synthetic_state_dict(ucfg, vcfg, dtype=torch.float16)
+    hit = 0
+    for i, key in enumerate(sorted(sd)):
+        if not key.endswith(".bias") or sd[key].numel() % 32:
+            continue
+        unet = key.startswith("model.diffusion_model.") and (re.search(r"\.(in_layers\.2|out_layers\.3|emb_layers\.1)\.bias$", key)
+                                                              or key.endswith("input_blocks.0.0.bias"))
+        vae = key.startswith("first_stage_model.decoder.") and re.search(r"(conv1|conv2|conv_in|upsample\.conv|nin_shortcut)\.bias$", key)
+        if unet or vae:
+            sign = torch.where(seeded((32,), 1000 + i) >= 0, 1.0, -1.0)
+            sd[key] = (sd[key].float() + (sign * OFFSET_BIAS).repeat_interleave(sd[key].numel() // 32)).half()
+            hit += 1
+    assert hit >= 30, hit
+    return sd
+
+
+def test_offset_heavy_checkpoint_unet_and_vae_vs_oracle(dev):
+    """Model-level twin of tests/test_gpu_ops.py::test_groupnorm_offset_dominated_groups_vs_fp64: every synthetic checkpoint has biases of
+    0.02 * randn, so no model test ever normalised a group whose mean is large against its spread.  Here the biases carry per-group
+    offsets; hooks on the fp32 oracle assert the precondition (a GroupNorm input with |group mean| / std >= 100 in the UNet and in the
+    VAE decoder), the engine's per-launch profile asserts that the two-launch form and the epilogue-statistics form both ran, and then
+      * the UNet forward, default mode and `residual_fp32`, against the fp32 oracle: within 1.25 x the distance that the ENGINE'S ROUNDING
+        PATTERN EMULATED ON THE ORACLE (tests/emu_engine_rounding.py: fp32 arithmetic, an fp16 rounding wherever the engine stores a
+        tensor) has from the same oracle on the same weights and inputs — a reference-side prediction, computed here;
+      * the VAE decode against the oracle decode: within 1.25 x the measured distance, VAE_OFFSET_DECODE_MEASURED (the rounding-pattern
+        emulation covers the UNet only; the figure so far comes from the host-emulated kernels, whose fp32 arithmetic is the source's).
+    A variance that cancels (sum x^2 / n - mean^2 in fp32) shows here as a distance the rounding pattern does not explain."""
+    import ctypes
+    import json
+    from emu_engine_rounding import Emu
+    from oracle import pipeline as opipe, unet as ou, vae as ov
+    schema, lib = sub("schema"), sub("_lib")
+    ucfg, vcfg = schema.tiny_unet(), schema.tiny_vae()
+    sd = _offset_heavy_state_dict(schema, ucfg, vcfg)
+    om = opipe.OracleModel(sd, ou.tiny_config(), ov.tiny_vae_config())
+    ratios = {}
+
+    def hook(name):
+        def pre(m, inp):
+            g = inp[0].reshape(inp[0].shape[0], m.num_groups, -1).double()
+            ratios[name] = float((g.mean(-1).abs() / g.std(-1)).max())
+        return pre
+    handles = [m.register_forward_pre_hook(hook(p + n)) for p, net in (("unet.", om.unet), ("vae.", om.vae)) for n, m in net.named_modules()
+               if isinstance(m, torch.nn.GroupNorm)]
+    x, t, ctx = seeded((2, 4, 32, 32), 1), torch.tensor([999.0, 37.5]), seeded((2, 77, 64), 2).half().float()
+    z = seeded((1, 4, 32, 32), 5) * 0.8
+    with torch.no_grad():
+        ref = om.unet(x.half().float(), t, ctx)
+        ref32 = om.unet(x, t, ctx)                             # the accuracy mode hands conv_in the fp32 latent as a (hi, lo) pair
+        vref = om.vae.decode_first_stage(z)
+        for h_ in handles:
+            h_.remove()
+        e_emu = rel_l2(Emu(om.unet, stream_fp32=False)(x, t, ctx), ref)
+        e_emu_acc = rel_l2(Emu(om.unet, stream_fp32=True, skip_fp32=True, h1_fp32=True, xin_fp32=True)(x, t, ctx), ref32)
+    worst = {p: max(v for k, v in ratios.items() if k.startswith(p)) for p in ("unet.", "vae.")}
+    assert worst["unet."] >= 100 and worst["vae."] >= 100, worst
+
+    model = sub("sd_models").SdModel(sd, ucfg, vcfg, device=0)
+    eng = model.engine
+
+    def profiled(fn):
+        lib.check(lib.lib.sdmi_profile_begin(), "profile_begin")
+        out = fn()
+        torch.cuda.synchronize()
+        buf = ctypes.create_string_buffer(1 << 21)
+        lib.check(lib.lib.sdmi_profile_end(buf, len(buf)), "profile_end")
+        return out, [k["name"] for k in json.loads(buf.value.decode())["kernels"]]
+    got, names = profiled(lambda: eng.unet_forward(x.to(dev), t.to(dev), ctx.to(dev)).cpu())
+    vgot, vnames = profiled(lambda: model.decode_first_stage(z.to(dev)).cpu())
+    for path, nm in (("unet", names), ("vae", vnames)):
+        assert any(n.startswith("groupnorm_silu B") for n in nm) and any(n.startswith("groupnorm_silu_apply B") for n in nm), (path, sorted(set(nm)))
+    eng.set_option("residual_fp32", 1)
+    try:
+        acc = eng.unet_forward(x.to(dev), t.to(dev), ctx.to(dev)).cpu()
+    finally:
+        eng.set_option("residual_fp32", 0)
+    e, e_acc, e_vae = rel_l2(got, ref), rel_l2(acc, ref32), rel_l2(vgot, vref)
+    print(f"[offset checkpoint] worst |group mean| / std: unet {worst['unet.']:.0f}, vae {worst['vae.']:.0f}; unet default {e:.3e} (pattern emulated "
+          f"{e_emu:.3e}), residual_fp32 {e_acc:.3e} (pattern emulated {e_emu_acc:.3e}); vae decode {e_vae:.3e}")
+    assert torch.isfinite(got).all() and torch.isfinite(acc).all() and torch.isfinite(vgot).all()
+    assert e <= 1.25 * e_emu, (e, e_emu)
+    assert e_acc <= 1.25 * e_emu_acc, (e_acc, e_emu_acc)
+    assert e_vae <= 1.25 * VAE_OFFSET_DECODE_MEASURED, e_vae
