@@ -6,7 +6,9 @@ The webui's default GPU configuration is ``model.half()`` under ``torch.autocast
 ``.type(x.dtype)``); residual adds, SiLU, GELU and the GEGLU product run on fp16 tensors; the split-attention forward keeps the
 score matrix and the softmax output in ``q.dtype`` (modules/sd_hijack_optimizations.py:262-268: ``s2 = s1.softmax(dim=-1,
 dtype=q.dtype)``).  ``fp16_storage(net)`` reproduces exactly that rounding pattern on the fp32 oracle modules: arithmetic stays
-fp32 (= fp32 accumulation), every tensor a GPU kernel would *write* is rounded to binary16.
+fp32 (= fp32 accumulation), every tensor a GPU kernel would *write* is rounded to binary16.  Loaded hypernetworks
+(``oracle.unet.LOADED_HYPERNETWORKS``) are modules inside the same autocast region, applied to the fp16 attention context
+(modules/hypernetworks/hypernetwork.py:358-379), and round the same way.
 
 Used by the C1 parity tests to measure how far the reference's fp16 path itself sits from its fp32 CPU path — the yardstick the
 engine's own distance is compared with (profiles/r02_parity.json).
@@ -19,6 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from oracle import hypernetwork as ohn
 from oracle import unet as ou
 from oracle import vae as ov
 
@@ -37,7 +40,10 @@ def _res_forward(self, x, emb):
 def _attn_forward(self, x, context=None):
     h = self.heads
     context = x if context is None else context
-    q, k, v = self.to_q(x), self.to_k(context), self.to_v(context)
+    context_k = context_v = context
+    if ou.LOADED_HYPERNETWORKS:                                 # (their modules round like the network's own: _hn_forward + the leaf hooks)
+        context_k, context_v = ohn.apply_hypernetworks(ou.LOADED_HYPERNETWORKS, context)
+    q, k, v = self.to_q(x), self.to_k(context_k), self.to_v(context_v)
     b, n, _ = q.shape
     split = lambda t: t.reshape(b, t.shape[1], h, -1).permute(0, 2, 1, 3).reshape(b * h, t.shape[1], -1)
     q, k, v = split(q), split(k), split(v)
@@ -46,6 +52,12 @@ def _attn_forward(self, x, context=None):
     out = r16(torch.einsum('bij,bjd->bid', attn, v))
     out = out.reshape(b, h, n, -1).permute(0, 2, 1, 3).reshape(b, n, -1)
     return self.to_out(out)
+
+
+def _hn_forward(self, x):
+    # the hypernetwork modules run on the fp16 context inside the same autocast region: every Linear stores an fp16 result (leaf hooks),
+    # the activations, the product with the multiplier and the sum with x are fp16 tensor arithmetic
+    return r16(x + r16(self.linear(x) * self.multiplier))
 
 
 def _geglu_forward(self, x):
@@ -110,7 +122,7 @@ def _vae_decoder_forward(self, z):
 
 _PATCHES = [(ou.ResBlock, _res_forward), (ou.CrossAttention, _attn_forward), (ou.GEGLU, _geglu_forward),
             (ou.BasicTransformerBlock, _tblock_forward), (ou.SpatialTransformer, _st_forward),
-            (ov.ResnetBlock, _vae_res_forward), (ov.AttnBlock, _vae_attn_forward), (ov.Decoder, _vae_decoder_forward)]
+            (ohn.HypernetworkModule, _hn_forward), (ov.ResnetBlock, _vae_res_forward), (ov.AttnBlock, _vae_attn_forward), (ov.Decoder, _vae_decoder_forward)]
 _LEAVES = (nn.Conv2d, nn.Linear, nn.GroupNorm, nn.LayerNorm, nn.SiLU)
 
 
@@ -126,6 +138,10 @@ def fp16_storage(net: nn.Module):
         for m in net.modules():
             if isinstance(m, _LEAVES):
                 handles.append(m.register_forward_hook(lambda mod, inp, out: r16(out)))
+        for hn in ou.LOADED_HYPERNETWORKS:                      # Linear, activation (any of hypernetwork.ACT), LayerNorm: every leaf stores fp16
+            for pair in hn.layers.values():
+                for m in (leaf for mod in pair for leaf in mod.modules() if not list(leaf.children())):
+                    handles.append(m.register_forward_hook(lambda mod, inp, out: r16(out)))
         yield net
     finally:
         for h in handles:

@@ -1734,3 +1734,181 @@ def test_offset_heavy_checkpoint_unet_and_vae_vs_oracle(dev):
     assert e <= 1.25 * e_emu, (e, e_emu)
     assert e_acc <= 1.25 * e_emu_acc, (e_acc, e_emu_acc)
     assert e_vae <= 1.25 * VAE_OFFSET_DECODE_MEASURED, e_vae
+
+
+# ------------------------------------------------------------------------------------------------------------
+# teacher-forced per-block parity (tests/teacher_forcing.py): the oracle's module N runs on the engine's own tap of block N - 1
+# ------------------------------------------------------------------------------------------------------------
+TF_T = [999.0, 37.5, 500.25]                    # the first two for B = 2; the ragged B = 3 case adds the third
+
+
+def _traced(eng, fn):
+    """fn() under engine option "trace" -> (its result, {tap name: NCHW fp32 on the CPU})."""
+    eng.set_option("trace", 1)
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+        taps = {k: v.float().cpu() for k, v in eng.taps().items()}
+    finally:
+        eng.set_option("trace", 0)
+    return out.float().cpu(), taps
+
+
+def _tf_summary(net, rows, label):
+    """One line per kind of segment: what profiles/teacher_forced_blocks.md records."""
+    import teacher_forcing as tf
+    kinds = {}
+    for r in rows:
+        kinds.setdefault(tf.segment_kind(net, r["block"]), []).append(r)
+    for kind, rs in sorted(kinds.items()):
+        ratio = [r["engine"] / r["yard"] for r in rs]
+        worst = max(max(r[s][0] for s, _ in tf.SLICINGS) / r["yard"] for r in rs)
+        print(f"[teacher_forced summary] {label} | {kind} | n {len(rs)} | engine {min(r['engine'] for r in rs):.2e}-{max(r['engine'] for r in rs):.2e} "
+              f"| ratio {min(ratio):.2f}-{max(ratio):.2f} | worst slice {worst:.2f}")
+
+
+def _teacher_forced_unet(dev, eng, net, x, t, ctx, y=None, label="unet"):
+    """One traced engine forward, then every tap — and the output, as the tap of the module `out` — against the oracle module that
+    produces it, run on the engine's previous tap: each segment within 1.25 x its own fp16 yardstick, per tensor and per slice."""
+    import teacher_forcing as tf
+    x, ctx = x.half().float(), ctx.half().float()
+    y = None if y is None else y.half().float()
+    got, taps = _traced(eng, lambda: eng.unet_forward(x.to(dev), t.to(dev), ctx.to(dev), None if y is None else y.to(dev)))
+    assert torch.isfinite(got).all()
+    taps["out"] = got
+    assert set(taps) == set(tf.unet_tap_names(net)), sorted(set(taps) ^ set(tf.unet_tap_names(net)))
+    rows = tf.segment_errors(net, lambda n: n(x, t, ctx, y), taps)
+    _tf_summary(net, rows, label)
+    tf.assert_segments(rows, label)
+    return rows
+
+
+TF_TINY_OPTIONS = {"default": {}, "ln_fold1": {"ln_fold": (1, 0)}, "ln_fold2": {"ln_fold": (2, 0)}, "force_generic": {"force_generic": (1, 0)},
+                   "no_glds": {"glds": (0, 1)}, "tiling": {"tiling": (1, 0)}}          # option: (value, value to restore)
+
+
+@pytest.mark.parametrize("case", list(TF_TINY_OPTIONS))
+def test_teacher_forced_tiny_unet_options(dev, tiny, case):
+    """The tiny UNet, 16x16 latent, B = 2, under each engine option that changes which launches a block is made of."""
+    import copy
+    eng, net = tiny["model"].engine, tiny["oracle"].unet
+    opts = TF_TINY_OPTIONS[case]
+    if case == "tiling":                                       # (as test_tiling_circular_padding_unet_and_vae_vs_oracle builds its oracle)
+        net = copy.deepcopy(net)
+        for layer in net.modules():
+            if type(layer) == torch.nn.Conv2d:
+                layer.padding_mode = "circular"
+                layer._reversed_padding_repeated_twice = torch.nn.modules.utils._reverse_repeat_tuple(layer.padding, 2)
+    for k, (v, _) in opts.items():
+        eng.set_option(k, v)
+    try:
+        _teacher_forced_unet(dev, eng, net, seeded((2, 4, 16, 16), 301), torch.tensor(TF_T[:2]), seeded((2, 77, 64), 302), label="tiny/" + case)
+    finally:
+        for k, (_, v0) in opts.items():
+            eng.set_option(k, v0)
+
+
+def test_teacher_forced_tiny_unet_ragged(dev, tiny):
+    """12x20 latent, B = 3: HW = 240 (60 at the second level) is no multiple of 64 — V^T gets zero-filled padding columns, the last
+    query and key tiles are ragged, and 64-row GEMM tiles straddle images."""
+    _teacher_forced_unet(dev, tiny["model"].engine, tiny["oracle"].unet, seeded((3, 4, 12, 20), 303), torch.tensor(TF_T), seeded((3, 77, 64), 304),
+                         label="tiny/ragged")
+
+
+def test_teacher_forced_unet_320_wide_with_and_without_the_row_chain(dev):
+    """model_channels = 320, 8 heads: d = 40 / 80 heads, 10-channel groups, the 320-column tiles, and at level 0 (C = 320, HW = 256) the
+    row-chain feed-forward — asserted from the per-launch profile: it ran with the default `fuse_rows` and did not with `fuse_rows` = 0.
+    Then `ln_fold` = 1: the three LayerNorms of every block inside the GEMMs that read them."""
+    import ctypes
+    import json
+    from oracle import unet as ou
+    schema, lib = sub("schema"), sub("_lib")
+    kw = dict(model_channels=320, num_heads=8, num_head_channels=-1, context_dim=768)
+    cfg = schema.tiny_unet(**kw)
+    sd = schema.synthetic_state_dict(cfg, None, dtype=torch.float16)
+    net = ou.build_unet(ou.tiny_config(**kw), sd)
+    eng = sub("engine").Engine(0)
+    eng.load_unet(cfg, sd)
+    x, t, ctx = seeded((2, 4, 16, 16), 305), torch.tensor(TF_T[:2]), seeded((2, 77, 768), 306)
+
+    def profiled(label):
+        lib.check(lib.lib.sdmi_profile_begin(), "profile_begin")
+        try:
+            _teacher_forced_unet(dev, eng, net, x, t, ctx, label=label)
+        finally:
+            buf = ctypes.create_string_buffer(1 << 21)
+            lib.check(lib.lib.sdmi_profile_end(buf, len(buf)), "profile_end")
+        return {k["name"]: k["launches"] for k in json.loads(buf.value.decode())["kernels"]}       # (one entry per launch name)
+    try:
+        names = profiled("wide320/fuse_rows_default")
+        assert any(n.startswith("rowchain_ff") for n in names), sorted(set(names))
+        eng.set_option("fuse_rows", 0)
+        names = profiled("wide320/fuse_rows_0")
+        assert names and not any(n.startswith("rowchain_ff") for n in names), sorted(set(names))
+        eng.set_option("fuse_rows", 2)
+        # `ln_fold` at these widths (d = 40 / 80 heads behind the folded q|k and V^T GEMMs).  Level 1 only: at the row counts a test can
+        # afford, no GEMM tile that leaves LayerNorm row sums in its epilogue is chosen — measured here and on the tiny model, `ln_fold` = 2
+        # makes the launches of `ln_fold` = 1, all 21 statistics launches included — so a second run would repeat the first.
+        eng.set_option("ln_fold", 1)
+        names = profiled("wide320/ln_fold1")
+        assert any(" ln" in n for n in names), sorted(names)
+        assert sum(k for n, k in names.items() if n.startswith("ln_rowstats")) == 3 * 7, names
+    finally:
+        eng.close()
+
+
+def test_teacher_forced_sdxl_shaped_unet(dev):
+    """The configuration of test_sdxl_shaped_unet_vs_oracle: Linear proj_in / proj_out, transformer depth 2 and 3 (block k + 1 reads
+    block k's output), no attention at level 0, vector conditioning y -> label_emb."""
+    from oracle import unet as ou
+    schema = sub("schema")
+    kw = dict(model_channels=64, channel_mult=(1, 2, 4), num_res_blocks=2, attention_resolutions=(2, 4), num_heads=-1,
+              num_head_channels=64, transformer_depth=(1, 2, 3), context_dim=128, use_linear_in_transformer=True,
+              adm_in_channels=192)
+    cfg = schema.UNetConfig(**kw)
+    sd = schema.synthetic_state_dict(cfg, None, dtype=torch.float16)
+    net = ou.build_unet(ou.UNetConfig(**kw), sd)
+    eng = sub("engine").Engine(0)
+    eng.load_unet(cfg, sd)
+    try:
+        _teacher_forced_unet(dev, eng, net, seeded((2, 4, 16, 16), 307), torch.tensor(TF_T[:2]), seeded((2, 77, 128), 308), seeded((2, 192), 309),
+                             label="sdxl_shaped")
+    finally:
+        eng.close()
+
+
+def test_teacher_forced_tiny_unet_with_hypernetworks(dev, tiny):
+    """The set-up of test_hypernetworks_in_engine_vs_oracle: with modules for the self-attention widths loaded, q and k are projected
+    separately (`ldq = ldk = C`) from the normalised tokens and their transformed copy, and the cached cross-attention K / V^T come
+    from the transformed text context."""
+    from oracle import hypernetwork as ohn, unet as ou
+    hn_mod = sub("hypernetwork")
+    model, om = tiny["model"], tiny["oracle"]
+    a = _hn_state([64, 128], [1, 2, 1], "relu", False, False, None, 7000, "hn_a")
+    b = _hn_state([64], [1, 2, 2, 1], "swish", True, True, [0, 0.3, 0.3, 0], 7100, "hn_b")
+    try:
+        hn_mod.load_hypernetworks(model, [a, b], [0.8, 0.5])
+        ou.LOADED_HYPERNETWORKS[:] = [ohn.Hypernetwork(a, 0.8), ohn.Hypernetwork(b, 0.5)]
+        _teacher_forced_unet(dev, model.engine, om.unet, seeded((2, 4, 16, 16), 310), torch.tensor(TF_T[:2]), seeded((2, 77, 64), 311),
+                             label="tiny/hypernetworks")
+    finally:
+        ou.LOADED_HYPERNETWORKS[:] = []
+        hn_mod.load_hypernetworks(model, [], [])
+
+
+@pytest.mark.parametrize("hw", [(16, 16), (12, 20)], ids=["16x16", "12x20"])
+def test_teacher_forced_tiny_vae_decode(dev, tiny, hw):
+    """The `decoder.*` taps of one decode (and the image, as the tap of `decoder.conv_out`) against the oracle VAE's modules of the same
+    names; 12x20: HW = 240 in the attention block, 960 after the upsampling."""
+    import teacher_forcing as tf
+    model, vae = tiny["model"], tiny["oracle"].vae
+    z = (seeded((2, 4) + hw, 312) * 0.8).half().float()
+    got, taps = _traced(model.engine, lambda: model.decode_first_stage(z.to(dev)))
+    assert torch.isfinite(got).all()
+    taps["decoder.conv_out"] = got
+    expected = set(tf.vae_tap_names(vae))
+    assert set(taps) == expected, sorted(set(taps) ^ expected)
+    label = "vae/%dx%d" % hw
+    rows = tf.segment_errors(vae, lambda n: n.decode_first_stage(z), taps)
+    _tf_summary(vae, rows, label)
+    tf.assert_segments(rows, label)
