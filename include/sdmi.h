@@ -439,6 +439,56 @@ int sdmi_clip_finalize(sdmi_engine* e, int slot);
 int sdmi_clip_forward(sdmi_engine* e, int slot, const void* tokens_i32, const void* inputs_embeds_f32_or_null, int B, int L,
                       int skip, int apply_final_ln, void* out_f32, void* pooled_f32_or_null, void* stream);
 
+/* ---- RRDBNet upscalers (ESRGAN / Real-ESRGAN) ------------------------------------------------------------------------------------ */
+
+/* One launch of the RRDBNet 3x3 conv (csrc/rrdb.hip): stride 1, pad 1, fp16 NHWC, fp32 accumulation.  Replaces one
+ * `lrelu(convK(torch.cat((x, x1, ...), 1)))` / `x5 * 0.2 + x` line of ResidualDenseBlock.forward (basicsr/archs/rrdbnet_arch.py, the
+ * webui's modules/esrgan_model.py loads the same network through spandrel): the concat is a channel PREFIX of one 192-wide buffer. */
+enum {
+    SDMI_RRDB_EP_NONE = 0,   /* acc + bias */
+    SDMI_RRDB_EP_LRELU = 1,  /* LeakyReLU(0.2) */
+    SDMI_RRDB_EP_RES1 = 2,   /* alpha * v + r1                  (RDB exit x5 * 0.2 + x; alpha = 1: feat + conv_body(...)) */
+    SDMI_RRDB_EP_RES2 = 3    /* beta * (alpha * v + r1) + r2    (third RDB of an RRDB: also the RRDB's out * 0.2 + x) */
+};
+enum {
+    SDMI_RRDB_ST_F16 = 0,       /* fp16 NHWC rows of stride ldo, `out` already offset to the first output channel */
+    SDMI_RRDB_ST_F32_NCHW = 1,  /* fp32 [B][n_real][H][W] */
+    SDMI_RRDB_ST_U8_HWC = 2     /* uint8 [B][H][W][n_real] = round_half_even(clamp(v, 0, 1) * 255): modules/upscaler_utils.py */
+};
+typedef struct sdmi_rrdb_desc {
+    const void* in;        /* fp16 NHWC, row stride lda >= cin; with up = 1 the (H/2) x (W/2) tensor (nearest x2 fused into the gather) */
+    const void* w;         /* fp16 [nout][9][cin] (sdmi_pack_conv_weight with O_pad = nout, I_pad = cin) */
+    const void* bias;      /* fp32 [nout] or NULL */
+    const void* r1;        /* fp16 residual rows (nout channels) of stride ldr1 / ldr2, or NULL */
+    const void* r2;
+    void* out;
+    int32_t B, H, W;       /* output grid */
+    int32_t cin;           /* multiple of 32, <= 192 */
+    int32_t lda, up;
+    int32_t nout;          /* 32 or 64 */
+    int32_t n_real;        /* channels stored, <= nout (conv_last: 3) */
+    int32_t ldo, ldr1, ldr2;
+    int32_t ep, store;
+    float alpha, beta;
+} sdmi_rrdb_desc;
+int sdmi_rrdb_conv(const sdmi_rrdb_desc* d, void* stream);
+
+/* A whole RRDBNet held by an engine (scratch from the engine's arena).  Replaces the model call inside upscale_without_tiling
+ * (modules/upscaler_utils.py:44-60, reached from UpscalerESRGAN.do_upscale, modules/esrgan_model.py:36-48, and
+ * UpscalerRealESRGAN.do_upscale, modules/realesrgan_model.py:36-69) run on the image whole (ESRGAN_tile = 0).
+ * blob: host fp32, for every conv in checkpoint order (conv_first, body.{i}.rdb{1..3}.conv{1..5}, conv_body, conv_up1, conv_up2,
+ * conv_hr, conv_last) the OIHW weight followed by the bias; sdmi_esrgan_blob_floats gives its length.  num_feat = 64, growth = 32.
+ * in_ch / scale: 3 / 4, 12 / 2 or 48 / 1 (the x2 / x1 models pixel-unshuffle by 2 / 4 in front of conv_first).  NULL on error. */
+typedef struct sdmi_esrgan sdmi_esrgan;
+int64_t sdmi_esrgan_blob_floats(int num_block, int in_ch);
+sdmi_esrgan* sdmi_esrgan_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, int num_block, int in_ch, int scale);
+void sdmi_esrgan_destroy(sdmi_esrgan* h);
+/* arena bytes a run on B images of H x W needs (the caller refuses inputs that cannot fit) */
+int64_t sdmi_esrgan_scratch_bytes(sdmi_esrgan* h, int B, int H, int W);
+/* in: RGB, uint8 HWC [B][H][W][3] (in_u8 = 1; divided by 255 on the way in) or fp32 NCHW [B][3][H][W] in [0, 1] (device memory).
+ * out: fp32 NCHW [B][3][H s][W s], or (out_u8 = 1) uint8 HWC [B][H s][W s][3] with the reference's clamp / x255 / np.round. */
+int sdmi_esrgan_run(sdmi_esrgan* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@ F16, F32 = 0, 1
 EP_OUT_F32, EP_GEGLU, EP_NCHW, EP_BIAS_ROW = 1, 2, 4, 8
 EP_TRANSPOSE = 64
 EP_WRAP = 128
+RRDB_EP_NONE, RRDB_EP_LRELU, RRDB_EP_RES1, RRDB_EP_RES2 = 0, 1, 2, 3
+RRDB_ST_F16, RRDB_ST_F32_NCHW, RRDB_ST_U8_HWC = 0, 1, 2
 
 
 class SdmiError(RuntimeError):
@@ -33,6 +35,15 @@ class ConvDesc(C.Structure):
         ("a_bs", C.c_int64), ("w_bs", C.c_int64), ("o_bs", C.c_int64), ("r_bs", C.c_int64),
         ("force_generic", C.c_int32), ("reserved", C.c_int32),
         ("splitk_workspace", C.c_void_p), ("splitk_workspace_bytes", C.c_int64),
+    ]
+
+
+class RrdbDesc(C.Structure):
+    _fields_ = [
+        ("in_", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("r1", C.c_void_p), ("r2", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("cin", C.c_int32), ("lda", C.c_int32), ("up", C.c_int32),
+        ("nout", C.c_int32), ("n_real", C.c_int32), ("ldo", C.c_int32), ("ldr1", C.c_int32), ("ldr2", C.c_int32),
+        ("ep", C.c_int32), ("store", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float),
     ]
 
 
@@ -148,6 +159,12 @@ _SIGS = {
     "sdmi_engine_tap_count": (_i, [_vp]),
     "sdmi_engine_tap_info": (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(C.c_int64)]),
     "sdmi_engine_tap_read": (_i, [_vp, _i, _vp, _vp]),
+    "sdmi_rrdb_conv": (_i, [C.POINTER(RrdbDesc), _vp]),
+    "sdmi_esrgan_blob_floats": (_i64, [_i, _i]),
+    "sdmi_esrgan_create": (_vp, [_vp, _vp, _i64, _i, _i, _i]),
+    "sdmi_esrgan_destroy": (None, [_vp]),
+    "sdmi_esrgan_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
+    "sdmi_esrgan_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)       # AttributeError here == the .so does not export a declared symbol

@@ -26,6 +26,10 @@ int engine_hypernet_act(sdmi_engine* e, int dim, int which, int act);
 int engine_hypernet_layernorm(sdmi_engine* e, int dim, int which, const void* g, const void* b, int dtype, int n, int on_device);
 int engine_unet_update_vector(sdmi_engine* e, const char* key, const void* data, int dtype, int64_t n, int on_device);
 int engine_set_context(sdmi_engine* e, const void* ctx, int dtype, int Bn, int L, hipStream_t s, bool conditional = false);
+int64_t esrgan_blob_floats(int num_block, int in_ch);
+int esrgan_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_block, int in_ch, int scale, sdmi_esrgan** out);
+int64_t esrgan_scratch_bytes(const sdmi_esrgan* n, int B, int H, int W);
+int esrgan_run(sdmi_esrgan* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
 }  // namespace sdmi
 
 using namespace sdmi;
@@ -570,6 +574,42 @@ int sdmi_vae_decode(sdmi_engine* e, const void* z, int io_dtype, void* out, int 
 int sdmi_vae_encode(sdmi_engine* e, const void* x, int io_dtype, void* out, int B, int H, int W, void* stream) {
     API_GUARD_BEGIN
     return vae_encode(e, x, io_dtype, (float*)out, B, H, W, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_rrdb_conv(const sdmi_rrdb_desc* d, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(d, "null descriptor");
+    RrdbP p{};
+    p.in = (const half_t*)d->in; p.w = (const half_t*)d->w; p.bias = (const float*)d->bias;
+    p.r1 = (const half_t*)d->r1; p.r2 = (const half_t*)d->r2; p.out = d->out;
+    p.B = d->B; p.H = d->H; p.W = d->W; p.cin = d->cin; p.lda = d->lda; p.up = d->up;
+    p.ldo = d->ldo; p.n_real = d->n_real; p.ldr1 = d->ldr1; p.ldr2 = d->ldr2; p.ep = d->ep; p.store = d->store;
+    p.alpha = d->alpha; p.beta = d->beta;
+    return launch_rrdb_conv(p, d->nout, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int64_t sdmi_esrgan_blob_floats(int num_block, int in_ch) { return esrgan_blob_floats(num_block, in_ch); }
+
+sdmi_esrgan* sdmi_esrgan_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, int num_block, int in_ch, int scale) {
+    try {
+        sdmi_esrgan* n = nullptr;
+        if (esrgan_create(e, (const float*)blob_f32, blob_floats, num_block, in_ch, scale, &n) != 0) return nullptr;
+        return n;
+    } catch (const std::exception& ex) {
+        set_error(std::string("exception: ") + ex.what());
+        return nullptr;
+    }
+}
+
+void sdmi_esrgan_destroy(sdmi_esrgan* h) { delete h; }
+
+int64_t sdmi_esrgan_scratch_bytes(sdmi_esrgan* h, int B, int H, int W) { return esrgan_scratch_bytes(h, B, H, W); }
+
+int sdmi_esrgan_run(sdmi_esrgan* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
+    API_GUARD_BEGIN
+    return esrgan_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
     API_GUARD_END
 }
 

@@ -230,6 +230,30 @@ int launch_rowchain_ff_pack(const half_t* w1, const float* b1, const half_t* w2,
 int launch_rowchain_ff(const half_t* x, half_t* out, const float* gamma, const float* beta, const void* packs, const float* bias_out,
                        long rows, int C, int hidden, float eps, hipStream_t s);
 
+// ---- RRDBNet 3x3 conv (rrdb.hip) -----------------------------------------------------------------------------
+enum { RRDB_EP_NONE = 0, RRDB_EP_LRELU = 1,      // v = acc + bias;  LeakyReLU(0.2)(v)
+       RRDB_EP_RES1 = 2,                         // alpha * v + r1                   (RDB exit x5 * 0.2 + x; alpha = 1: feat + conv_body)
+       RRDB_EP_RES2 = 3 };                       // beta * (alpha * v + r1) + r2     (third RDB of an RRDB: also closes the RRDB residual)
+enum { RRDB_ST_F16 = 0, RRDB_ST_F32_NCHW = 1, RRDB_ST_U8_HWC = 2 };
+struct RrdbP {
+    const half_t* in;      // NHWC rows of stride lda; the first cin channels are read.  With up: the (H/2) x (W/2) low-resolution tensor
+    const half_t* w;       // [NOUT][9][cin] fp16 (launch_pack_conv_weight layout), row stride ldw (0 = 9 * cin)
+    const float* bias;     // [NOUT] or null
+    const half_t* r1;      // residual rows of stride ldr1 / ldr2 (NOUT channels each)
+    const half_t* r2;
+    void* out;             // already offset to the first output channel: fp16 rows of stride ldo | fp32 [B][n_real][H][W] | uint8 [B][H][W][n_real]
+    const half_t* zero;    // set by the launcher
+    int B, H, W;           // OUTPUT grid
+    int cin, lda, ldw, up;
+    int ldo, n_real, ldr1, ldr2;
+    int ep, store;
+    float alpha, beta;
+    long long M;           // set by the launcher: B * H * W
+};
+int launch_rrdb_conv(const RrdbP& p, int nout, hipStream_t s);
+// RGB image (uint8 HWC / 255, or fp32 NCHW) -> pixel-unshuffle by f -> NHWC fp16 rows of cpad channels (zero padded)
+int launch_rrdb_input(const void* in, int u8, half_t* out, int B, int C, int H, int W, int f, int cpad, hipStream_t s);
+
 // ---- norms ------------------------------------------------------------------------------------------------
 // pre_nchunk > 0: `ws` already holds (mean, M2) [B][pre_nchunk][groups][2] of HW / pre_nchunk rows each (written by the producing GEMM): skip the statistics pass
 // x0_lo / x1_lo (engine option "residual_fp32"): the lo parts when the inputs are (hi, lo) fp16 pairs of the carried stream

@@ -1965,7 +1965,145 @@ int engine_set_context(sdmi_engine* e, const void* ctx, int dtype, int Bn, int L
     return unet_set_context(e, ctx, dtype, Bn, L, s, conditional);
 }
 
+
+// ------------------------------------------------------------------------------------------------------------
+// RRDBNet upscalers (ESRGAN / Real-ESRGAN): BasicSR's RRDBNet.forward (basicsr/archs/rrdbnet_arch.py) as rrdb_conv launches
+// ------------------------------------------------------------------------------------------------------------
+// blob: fp32, for every conv in checkpoint order (conv_first, body.{i}.rdb{1..3}.conv{1..5}, conv_body, conv_up1, conv_up2, conv_hr,
+// conv_last) the OIHW weight followed by the bias.
+int64_t esrgan_blob_floats(int num_block, int in_ch) {
+    auto conv = [](int64_t o, int64_t i) { return o * i * 9 + o; };
+    int64_t n = conv(64, in_ch);
+    for (int k = 0; k < 5; ++k) n += (int64_t)num_block * 3 * conv(k < 4 ? 32 : 64, 64 + 32 * k);
+    return n + 4 * conv(64, 64) + conv(3, 64);
+}
+
+int esrgan_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_block, int in_ch, int scale, sdmi_esrgan** out) {
+    SDMI_REQUIRE(e && blob && out, "null argument");
+    SDMI_REQUIRE(num_block >= 1 && num_block <= 64, "num_block");
+    SDMI_REQUIRE((scale == 4 && in_ch == 3) || (scale == 2 && in_ch == 12) || (scale == 1 && in_ch == 48),
+                 "RRDBNet: scale 4 / 2 / 1 with 3 / 12 / 48 input channels (pixel-unshuffle in front of conv_first)");
+    SDMI_REQUIRE(blob_floats == esrgan_blob_floats(num_block, in_ch), "weight blob size does not match num_block / in_ch");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    std::unique_ptr<sdmi_esrgan> net(new sdmi_esrgan);
+    net->e = e; net->num_block = num_block; net->in_ch = in_ch; net->scale = scale; net->unshuffle = 4 / scale;
+    net->cin0 = rup(in_ch, 32);
+    float* dblob = nullptr;
+    SDMI_CHECK_HIP(hipMalloc((void**)&dblob, blob_floats * sizeof(float)));
+    struct Free { float* p; ~Free() { (void)hipFree(p); } } guard{dblob};
+    SDMI_CHECK_HIP(hipMemcpy(dblob, blob, blob_floats * sizeof(float), hipMemcpyHostToDevice));
+    int64_t off = 0;
+    auto pack = [&](sdmi_esrgan::Conv* c, int O, int I) -> int {
+        c->cin = rup(I, 32); c->nout = O <= 32 ? 32 : 64; c->n_real = O;
+        const size_t wb = (size_t)c->nout * 9 * c->cin * sizeof(half_t), bb = (size_t)c->nout * sizeof(float);
+        SDMI_CHECK_HIP(hipMalloc((void**)&c->w, std::max<size_t>(wb, 256)));
+        net->owned.push_back(c->w);
+        SDMI_CHECK_HIP(hipMalloc((void**)&c->b, 256));
+        net->owned.push_back(c->b);
+        TRY(launch_pack_conv_weight(dblob + off, 1, c->w, O, I, 3, 3, c->nout, c->cin, 0, nullptr));
+        off += (int64_t)O * I * 9;
+        SDMI_CHECK_HIP(hipMemset(c->b, 0, bb));
+        SDMI_CHECK_HIP(hipMemcpy(c->b, dblob + off, (size_t)O * sizeof(float), hipMemcpyDeviceToDevice));
+        off += O;
+        return 0;
+    };
+    TRY(pack(&net->first, 64, in_ch));
+    net->rdb.resize((size_t)num_block * 15);
+    for (int i = 0; i < num_block * 3; ++i)
+        for (int k = 0; k < 5; ++k) TRY(pack(&net->rdb[(size_t)i * 5 + k], k < 4 ? 32 : 64, 64 + 32 * k));
+    TRY(pack(&net->body, 64, 64));
+    TRY(pack(&net->up1, 64, 64));
+    TRY(pack(&net->up2, 64, 64));
+    TRY(pack(&net->hr, 64, 64));
+    TRY(pack(&net->last, 3, 64));
+    SDMI_CHECK_HIP(hipDeviceSynchronize());
+    *out = net.release();
+    return 0;
+}
+
+namespace {
+struct EsrganBufs { half_t *in, *x[3], *feat, *trunk, *u1, *u2, *u3; };
+// the arena layout of one run (pure host arithmetic): M low-resolution pixels
+EsrganBufs esrgan_take(Arena& ar, const sdmi_esrgan& n, size_t M) {
+    EsrganBufs b;
+    ar.reset();
+    b.in = (half_t*)ar.take(M * n.cin0 * sizeof(half_t));
+    for (int i = 0; i < 3; ++i) b.x[i] = (half_t*)ar.take(M * 192 * sizeof(half_t));
+    b.feat = (half_t*)ar.take(M * 64 * sizeof(half_t));
+    b.trunk = (half_t*)ar.take(M * 64 * sizeof(half_t));
+    b.u1 = (half_t*)ar.take(4 * M * 64 * sizeof(half_t));
+    b.u2 = (half_t*)ar.take(16 * M * 64 * sizeof(half_t));
+    b.u3 = (half_t*)ar.take(16 * M * 64 * sizeof(half_t));
+    return b;
+}
+}  // namespace
+
+int64_t esrgan_scratch_bytes(const sdmi_esrgan* n, int B, int H, int W) {
+    if (!n || B <= 0 || H <= 0 || W <= 0) return 0;
+    Arena ar;
+    ar.dry = true;
+    esrgan_take(ar, *n, (size_t)B * (H / n->unshuffle) * (W / n->unshuffle));
+    return (int64_t)ar.high;
+}
+
+// in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
+// out: [B][3][H s][W s] fp32 NCHW, or (out_u8) uint8 HWC [B][H s][W s][3] = round_half_even(clamp(y, 0, 1) * 255).
+int esrgan_run(sdmi_esrgan* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s) {
+    SDMI_REQUIRE(n && in && out, "null argument");
+    sdmi_engine* e = n->e;
+    const int f = n->unshuffle;
+    SDMI_REQUIRE(B > 0 && H > 0 && W > 0 && H % f == 0 && W % f == 0, "image sides must be multiples of the model's pixel-unshuffle factor");
+    const int h = H / f, w = W / f;
+    SDMI_REQUIRE((long long)B * h * w * 16 < (1ll << 31) - 256, "image too large: B*H*W*16 output pixels must stay below 2^31");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    const size_t M = (size_t)B * h * w;
+    e->arena.dry = true; e->arena.high = 0;
+    esrgan_take(e->arena, *n, M);
+    e->arena.dry = false;
+    TRY(ensure_arena(e, e->arena.high, s));
+    const EsrganBufs b = esrgan_take(e->arena, *n, M);
+
+    auto conv = [&](const sdmi_esrgan::Conv& c, const half_t* src, int lda, int hh, int ww, int up, void* dst, int ldo, int ep,
+                    float alpha = 1.f, const half_t* r1 = nullptr, int ldr1 = 0, float beta = 1.f, const half_t* r2 = nullptr, int ldr2 = 0,
+                    int store = RRDB_ST_F16) -> int {
+        RrdbP p{};
+        p.in = src; p.w = c.w; p.bias = c.b; p.r1 = r1; p.r2 = r2; p.out = dst;
+        p.B = B; p.H = hh; p.W = ww; p.cin = c.cin; p.lda = lda; p.up = up;
+        p.ldo = ldo; p.n_real = c.n_real; p.ldr1 = ldr1; p.ldr2 = ldr2; p.ep = ep; p.store = store; p.alpha = alpha; p.beta = beta;
+        return launch_rrdb_conv(p, c.nout, s);
+    };
+
+    TRY(launch_rrdb_input(in, in_u8, b.in, B, 3, H, W, f, n->cin0, s));
+    // conv_first twice (K = 288: 0.4 % of the network's work): once into `feat`, the trunk's skip tensor that conv_body's epilogue adds,
+    // once into channels 0..63 of the first dense buffer.  conv_body cannot read that skip from x[0]: the third RDB of every RRDB writes
+    // its result over x[0], so by then x[0] holds the body's output, not conv_first's.
+    TRY(conv(n->first, b.in, n->cin0, h, w, 0, b.feat, 64, RRDB_EP_NONE));
+    TRY(conv(n->first, b.in, n->cin0, h, w, 0, b.x[0], 192, RRDB_EP_NONE));
+    // Dense blocks on three rotating 192-wide buffers: RDB j of an RRDB reads x[j] and writes channels 0..63 of x[(j + 1) % 3], so the
+    // third one lands on x[0] — the RRDB's own input, which its epilogue reads as r2 (same element, same lane, before the store).
+    for (int i = 0; i < n->num_block; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const sdmi_esrgan::Conv* c = &n->rdb[((size_t)i * 3 + j) * 5];
+            half_t* src = b.x[j];
+            half_t* dst = b.x[(j + 1) % 3];
+            for (int k = 0; k < 4; ++k) TRY(conv(c[k], src, 192, h, w, 0, src + 64 + 32 * k, 192, RRDB_EP_LRELU));
+            if (j < 2) TRY(conv(c[4], src, 192, h, w, 0, dst, 192, RRDB_EP_RES1, 0.2f, src, 192));
+            else TRY(conv(c[4], src, 192, h, w, 0, dst, 192, RRDB_EP_RES2, 0.2f, src, 192, 0.2f, dst, 192));
+        }
+    TRY(conv(n->body, b.x[0], 192, h, w, 0, b.trunk, 64, RRDB_EP_RES1, 1.f, b.feat, 64));
+    TRY(conv(n->up1, b.trunk, 64, 2 * h, 2 * w, 1, b.u1, 64, RRDB_EP_LRELU));
+    TRY(conv(n->up2, b.u1, 64, 4 * h, 4 * w, 1, b.u2, 64, RRDB_EP_LRELU));
+    TRY(conv(n->hr, b.u2, 64, 4 * h, 4 * w, 0, b.u3, 64, RRDB_EP_LRELU));
+    TRY(conv(n->last, b.u3, 64, 4 * h, 4 * w, 0, out, 0, RRDB_EP_NONE, 1.f, nullptr, 0, 1.f, nullptr, 0,
+             out_u8 ? RRDB_ST_U8_HWC : RRDB_ST_F32_NCHW));
+    return 0;
+}
+
 }  // namespace sdmi
+
+sdmi_esrgan::~sdmi_esrgan() {
+    for (void* p : owned) (void)hipFree(p);
+}
 
 sdmi_engine::~sdmi_engine() {
     (void)hipSetDevice(device);
@@ -1985,3 +2123,9 @@ sdmi_engine::~sdmi_engine() {
     for (hipEvent_t ev : ev_join) (void)hipEventDestroy(ev);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
 }
+
+// The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units; there the RRDBNet
+// kernel file travels inside this one.  The GPU build compiles rrdb.hip on its own (build.sh).
+#ifndef __HIP__
+#include "rrdb.hip"
+#endif

@@ -242,3 +242,17 @@ struct sdmi_engine {
 
     ~sdmi_engine();
 };
+
+// RRDBNet upscaler (ESRGAN / Real-ESRGAN): packed weights of the rrdb_conv launches (rrdb.hip).  Activations come from the owning
+// engine's arena, like the VAE's; the net itself is immutable after sdmi_esrgan_create.
+struct sdmi_esrgan {
+    struct Conv { half_t* w = nullptr; float* b = nullptr; int cin = 0, nout = 0, n_real = 0; };
+    sdmi_engine* e = nullptr;
+    int num_block = 0, in_ch = 0, scale = 0;
+    int unshuffle = 1;                        // 4 / scale: pixel-unshuffle factor in front of conv_first (x2: 2, x1: 4)
+    int cin0 = 0;                             // conv_first's input channels (3 / 12 / 48) padded to 32 / 32 / 64
+    Conv first, body, up1, up2, hr, last;
+    std::vector<Conv> rdb;                    // num_block x 3 x 5, in checkpoint order
+    std::vector<void*> owned;
+    ~sdmi_esrgan();
+};

@@ -254,3 +254,66 @@ def image_to_u8(img: torch.Tensor) -> torch.Tensor:
     out = torch.empty((b, h, w, c), dtype=torch.uint8, device=img.device)
     check(lib.sdmi_image_to_u8(ptr(img), ptr(out), b, c, h, w, stream_ptr()), "sdmi_image_to_u8")
     return out
+
+
+def pack_rrdb_weight(w: torch.Tensor, nout: Optional[int] = None) -> torch.Tensor:
+    """OIHW 3x3 weight -> fp16 [nout][9][cin] for rrdb_conv: output channels zero-padded to nout (32 or 64; conv_last: 3 -> 32), input
+    channels to a multiple of 32 (conv_first: 3 / 12 / 48 -> 32 / 32 / 64)."""
+    _lib.require_device()
+    w = w.contiguous()
+    o, i, kh, kw = w.shape
+    assert (kh, kw) == (3, 3)
+    nout = nout or (32 if o <= 32 else 64)
+    cin = _rup(i, 32)
+    out = torch.empty((nout, 9, cin), dtype=torch.float16, device=w.device)
+    check(lib.sdmi_pack_conv_weight(ptr(w), _lib.dtype_code(w), ptr(out), o, i, 3, 3, nout, cin, 0, stream_ptr()), "pack_rrdb_weight")
+    return out
+
+
+def rrdb_conv(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor] = None, *, cin: Optional[int] = None,
+              out: Optional[torch.Tensor] = None, out_offset: int = 0, n_real: Optional[int] = None, ep: str = "lrelu",
+              alpha: float = 1.0, r1: Optional[torch.Tensor] = None, beta: float = 1.0, r2: Optional[torch.Tensor] = None,
+              up: bool = False, store: str = "f16") -> torch.Tensor:
+    """One RRDBNet 3x3 conv launch (csrc/rrdb.hip; a line of ResidualDenseBlock.forward, basicsr/archs/rrdbnet_arch.py).
+    x [B,H,W,lda] fp16 NHWC: its first `cin` channels are the input (a dense block's concat is a channel prefix of one buffer); with `up`
+    the conv runs on the nearest-x2 enlargement of x without building it.  The nout = w_packed.shape[0] output channels go to channels
+    [out_offset, out_offset + n_real) of `out` [B,Ho,Wo,ldo] (fp16; made if None), or with store = "f32_nchw" / "u8_hwc" to a new
+    [B,n_real,Ho,Wo] fp32 / [B,Ho,Wo,n_real] uint8 (clamp, x255, round half to even) tensor.
+    ep: "none" | "lrelu" | "res1" (alpha * v + r1) | "res2" (beta * (alpha * v + r1) + r2); r1 / r2 [B,Ho,Wo,ld] fp16, first nout channels."""
+    _lib.require_device()
+    assert x.dtype == torch.float16 and x.is_contiguous() and w_packed.dtype == torch.float16 and w_packed.is_contiguous()
+    b, hi, wi, lda = x.shape
+    nout, cin_w = w_packed.shape[0], w_packed.shape[2]
+    cin = cin_w if cin is None else cin
+    assert cin == cin_w, "the packed weights fix the number of input channels"
+    ho, wo = (2 * hi, 2 * wi) if up else (hi, wi)
+    n_real = nout if n_real is None else n_real
+    d = _lib.RrdbDesc()
+    d.in_, d.w = x.data_ptr(), w_packed.data_ptr()
+    d.bias = bias.data_ptr() if bias is not None else None
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == nout
+    for name, r in (("r1", r1), ("r2", r2)):
+        if r is not None:
+            assert r.dtype == torch.float16 and r.is_contiguous() and tuple(r.shape[:3]) == (b, ho, wo)
+            setattr(d, name, r.data_ptr())
+            setattr(d, "ld" + name, r.shape[3])
+    d.B, d.H, d.W, d.cin, d.lda, d.up = b, ho, wo, cin, lda, 1 if up else 0
+    d.nout, d.n_real = nout, n_real
+    d.ep = {"none": _lib.RRDB_EP_NONE, "lrelu": _lib.RRDB_EP_LRELU, "res1": _lib.RRDB_EP_RES1, "res2": _lib.RRDB_EP_RES2}[ep]
+    d.store = {"f16": _lib.RRDB_ST_F16, "f32_nchw": _lib.RRDB_ST_F32_NCHW, "u8_hwc": _lib.RRDB_ST_U8_HWC}[store]
+    d.alpha, d.beta = alpha, beta
+    if store == "f16":
+        if out is None:
+            out = torch.empty((b, ho, wo, out_offset + n_real), dtype=torch.float16, device=x.device)
+        assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape[:3]) == (b, ho, wo)
+        assert out_offset + n_real <= out.shape[3]
+        d.out, d.ldo = out.data_ptr() + 2 * out_offset, out.shape[3]
+    elif store == "f32_nchw":
+        out = torch.empty((b, n_real, ho, wo), dtype=torch.float32, device=x.device)
+        d.out = out.data_ptr()
+    else:
+        out = torch.empty((b, ho, wo, n_real), dtype=torch.uint8, device=x.device)
+        d.out = out.data_ptr()
+    check(lib.sdmi_rrdb_conv(C.byref(d), stream_ptr()), "sdmi_rrdb_conv")
+    return out

@@ -3,11 +3,16 @@
 The engine's part is decode -> [host image resize] -> encode; the resize itself stays the reference's job.  This module is
 the seam: the registry ``shared.sd_upscalers`` of ``UpscalerData(name, path, scaler)`` entries the reference's code looks names
 up in (modules/images.py:276, modules/modelloader.py:136), the ``Upscaler.upscale`` driver loop (modules/upscaler.py:54-76) and
-the three built-in PIL scalers (None / Lanczos / Nearest, modules/upscaler.py:107-154).  Model upscalers (ESRGAN, SwinIR, ...)
-register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)`` is called as in the reference.
+the three built-in PIL scalers (None / Lanczos / Nearest, modules/upscaler.py:107-154).  The RRDBNet family (ESRGAN, Real-ESRGAN)
+runs on the engine (``UpscalerESRGAN`` / ``register_esrgan`` below, csrc/rrdb.hip); other model upscalers (SwinIR, ...) register their own
+``UpscalerData`` whose ``scaler.upscale(img, scale, path)`` is called as in the reference.
 """
 from __future__ import annotations
 
+import os
+import re
+
+import numpy as np
 from PIL import Image
 
 from . import shared
@@ -84,6 +89,220 @@ class UpscalerNearest(_PilUpscaler):
 def builtin_upscalers():
     """The order modelloader.load_upscalers leaves the built-ins in (:136-141: "None" first, then by name)."""
     return [*UpscalerNone().scalers, *UpscalerLanczos().scalers, *UpscalerNearest().scalers]
+
+
+# ---- RRDBNet upscalers on the engine ----------------------------------------------------------------------------------------------
+_NEW_CONVS = ("conv_first", "conv_body", "conv_up1", "conv_up2", "conv_hr", "conv_last")
+_OLD_TO_NEW = {"model.0": "conv_first", "model.3": "conv_up1", "model.6": "conv_up2", "model.8": "conv_hr", "model.10": "conv_last"}
+
+
+def _old_arch_to_new(sd):
+    """The original ESRGAN key layout (model.0, model.1.sub.{i}.RDB{j}.conv{k}.0, model.1.sub.{nb}, model.3 / 6 / 8 / 10) renamed to
+    BasicSR's, as the webui does on load (the x4 layout only: other scales put their up-convs elsewhere)."""
+    tops = {m.group(1) for k in sd for m in [re.match(r"model\.(\d+)\.(weight|bias)$", k)] if m}
+    if tops != {"0", "3", "6", "8", "10"}:
+        raise ValueError(f"old-arch ESRGAN checkpoint is not a x4 model (top-level convs model.{sorted(tops, key=int)})")
+    subs = [int(m.group(1)) for k in sd for m in [re.match(r"model\.1\.sub\.(\d+)\.weight$", k)] if m]
+    if len(subs) != 1:
+        raise ValueError("old-arch ESRGAN checkpoint without its trunk conv (model.1.sub.<num_block>)")
+    nb, out = subs[0], {}
+    for k, v in sd.items():
+        stem, leaf = k.rsplit(".", 1)
+        m = re.match(r"model\.1\.sub\.(\d+)\.RDB(\d)\.conv(\d)\.0$", stem)
+        if m:
+            out[f"body.{m.group(1)}.rdb{m.group(2)}.conv{m.group(3)}.{leaf}"] = v
+        elif stem == f"model.1.sub.{nb}":
+            out[f"conv_body.{leaf}"] = v
+        elif stem in _OLD_TO_NEW:
+            out[f"{_OLD_TO_NEW[stem]}.{leaf}"] = v
+        else:
+            raise ValueError(f"unexpected key in an old-arch ESRGAN checkpoint: {k}")
+    return out
+
+
+def parse_esrgan_state_dict(sd):
+    """Checkpoint state dict -> (blob, num_block, in_ch, scale): the engine's weight blob (fp32, every conv's OIHW weight then its bias,
+    in checkpoint order — sdmi_esrgan_create), the number of RRDBs read from the keys (23, or 6 for the anime model) and the scale read
+    from conv_first's input channels (3 -> x4, 12 -> x2, 48 -> x1: pixel-unshuffle in front).  Host only.  Raises ValueError on anything
+    that is not a 64-feature / 32-growth RRDBNet."""
+    for wrap in ("params_ema", "params"):
+        if wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+            break
+    sd = {k: v for k, v in sd.items() if hasattr(v, "shape")}
+    if "model.0.weight" in sd:
+        sd = _old_arch_to_new(sd)
+    if "conv_first.weight" not in sd:
+        raise ValueError("not an RRDBNet checkpoint: neither conv_first.weight nor model.0.weight")
+    blocks = sorted({int(m.group(1)) for k in sd for m in [re.match(r"body\.(\d+)\.rdb1\.conv1\.weight$", k)] if m})
+    num_block = len(blocks)
+    if num_block == 0 or blocks != list(range(num_block)):
+        raise ValueError(f"RRDBNet body blocks are not 0..n-1: {blocks}")
+    names = ["conv_first"] + [f"body.{i}.rdb{j}.conv{k}" for i in range(num_block) for j in (1, 2, 3) for k in (1, 2, 3, 4, 5)]
+    names += list(_NEW_CONVS[1:])
+    missing = [n + leaf for n in names for leaf in (".weight", ".bias") if n + leaf not in sd]
+    if missing:
+        raise ValueError(f"RRDBNet checkpoint lacks {missing[:4]}{' ...' if len(missing) > 4 else ''}")
+    num_feat, in_ch = int(sd["conv_first.weight"].shape[0]), int(sd["conv_first.weight"].shape[1])
+    growth = int(sd["body.0.rdb1.conv1.weight"].shape[0])
+    if num_feat != 64:
+        raise ValueError(f"RRDBNet num_feat = {num_feat}: the engine's kernels are built for 64")
+    if growth != 32:
+        raise ValueError(f"RRDBNet num_grow_ch = {growth}: the engine's kernels are built for 32")
+    if in_ch not in (3, 12, 48):
+        raise ValueError(f"RRDBNet conv_first takes {in_ch} channels: expected 3 (x4), 12 (x2) or 48 (x1)")
+    scale = {3: 4, 12: 2, 48: 1}[in_ch]
+    parts = []
+    for n in names:
+        k = int(n[-1]) if ".conv" in n else 0
+        want = {"conv_first": (64, in_ch), "conv_last": (3, 64)}.get(n, ((32 if k < 5 else 64, 64 + 32 * (k - 1)) if k else (64, 64)))
+        w, b = sd[n + ".weight"], sd[n + ".bias"]
+        if tuple(w.shape) != (*want, 3, 3) or tuple(b.shape) != (want[0],):
+            raise ValueError(f"RRDBNet {n}: weight {tuple(w.shape)}, expected {(*want, 3, 3)}")
+        parts += [np.asarray(w.detach().float().cpu().numpy() if hasattr(w, "detach") else w, dtype=np.float32).ravel(),
+                  np.asarray(b.detach().float().cpu().numpy() if hasattr(b, "detach") else b, dtype=np.float32).ravel()]
+    return np.ascontiguousarray(np.concatenate(parts)), num_block, in_ch, scale
+
+
+def load_esrgan_checkpoint(path):
+    """.pth (torch.load, weights_only) or .safetensors -> state dict."""
+    if str(path).lower().endswith(".safetensors"):
+        from safetensors.torch import load_file
+        return load_file(path, device="cpu")
+    import torch
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
+def model_output_to_u8(y):
+    """The reference's hand-off from the model's [0, 1] output to uint8 (modules/upscaler_utils.py): clamp, x255, np.round (half to
+    even) — NOT the truncation of ops.image_to_u8.  y: float array."""
+    return np.round(np.clip(np.asarray(y, dtype=np.float32), 0.0, 1.0) * np.float32(255.0)).astype(np.uint8)
+
+
+def arena_limit_bytes(device=0):
+    """What a run's scratch may take: the device memory that is free now."""
+    import torch
+    return int(torch.cuda.mem_get_info(device)[0])
+
+
+class EsrganInputTooLarge(ValueError):
+    """An image whose intermediates the engine's arena cannot hold (EsrganNet.check_fits)."""
+
+
+class EsrganNet:
+    """One RRDBNet resident on an engine (sdmi_esrgan_*)."""
+
+    def __init__(self, state_dict, device=0, engine=None):
+        from . import _lib
+        from .engine import Engine
+        blob, self.num_block, self.in_ch, self.scale = parse_esrgan_state_dict(state_dict)
+        self.device = int(device)
+        self.engine = engine or Engine(self.device)
+        self.handle = _lib.lib.sdmi_esrgan_create(self.engine.handle, blob.ctypes.data, blob.size, self.num_block, self.in_ch, self.scale)
+        if not self.handle:
+            raise _lib.SdmiError("sdmi_esrgan_create failed: " + _lib.last_error())
+
+    def close(self):
+        if getattr(self, "handle", None):
+            from . import _lib
+            _lib.lib.sdmi_esrgan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def scratch_bytes(self, b, h, w):
+        """Arena bytes of one run, from the engine's own layout (sdmi_esrgan_scratch_bytes)."""
+        from . import _lib
+        return int(_lib.lib.sdmi_esrgan_scratch_bytes(self.handle, b, h, w))
+
+    def check_fits(self, b, h, w):
+        """Refuse an input whose intermediates (the 192-wide dense buffers, the (H s) x (W s) x 64 up-conv tensors) the arena cannot hold."""
+        unshuffle = 4 // self.scale
+        pixels = b * (h // unshuffle) * (w // unshuffle)
+        need = self.scratch_bytes(b, h, w)
+        # the arena the engine already holds is replaced, not added to, when it has to grow: it counts as available
+        limit = arena_limit_bytes(self.device) + self.engine.arena_bytes()
+        if pixels * 16 >= (1 << 31) - 256 or need > limit:
+            raise EsrganInputTooLarge(f"image {w}x{h} (batch {b}) is too large for the x{self.scale} upscaler: its intermediates need "
+                             f"{need / 2 ** 30:.1f} GiB of engine arena, {limit / 2 ** 30:.1f} GiB are available")
+
+    def run(self, x, out_u8=False):
+        """x: uint8 [B,H,W,3] (RGB; divided by 255 on the way in) or fp32 [B,3,H,W] in [0, 1], on the engine's device ->
+        fp32 [B,3,H s,W s], or with out_u8 uint8 [B,H s,W s,3] (clamp, x255, round half to even).  H, W: multiples of 4 / scale."""
+        import torch
+        from . import _lib
+        in_u8 = x.dtype == torch.uint8
+        x = x.contiguous() if in_u8 else x.float().contiguous()
+        b, h, w = (x.shape[0], x.shape[1], x.shape[2]) if in_u8 else (x.shape[0], x.shape[2], x.shape[3])
+        assert x.shape[3 if in_u8 else 1] == 3
+        self.check_fits(b, h, w)
+        s = self.scale
+        out = (torch.empty((b, h * s, w * s, 3), dtype=torch.uint8, device=x.device) if out_u8
+               else torch.empty((b, 3, h * s, w * s), dtype=torch.float32, device=x.device))
+        _lib.check(_lib.lib.sdmi_esrgan_run(self.handle, _lib.ptr(x), 1 if in_u8 else 0, b, h, w, _lib.ptr(out), 1 if out_u8 else 0,
+                                            _lib.stream_ptr()), "sdmi_esrgan_run")
+        return out
+
+
+class UpscalerESRGAN(Upscaler):
+    """ESRGAN / Real-ESRGAN on the engine: what modules/esrgan_model.py:UpscalerESRGAN.do_upscale and
+    modules/realesrgan_model.py:UpscalerRealESRGAN.do_upscale compute with ESRGAN_tile = 0 (the image whole; tiling exists there for
+    VRAM this card does not lack), with the uint8 hand-off of modules/upscaler_utils.py."""
+    name = "ESRGAN"
+
+    def __init__(self, device=0, engine=None):
+        """engine: the engine.Engine whose arena the runs use — e.g. the one that holds the UNet and VAE (SdModel.engine); without one
+        the scaler makes a single engine of its own on first use.  Every checkpoint of this scaler shares it: one arena, however many
+        models are registered."""
+        super().__init__()
+        self.device = int(device)
+        self.engine = engine
+        self._nets = {}
+
+    def load_model(self, path):
+        net = self._nets.get(path)
+        if net is None:
+            if self.engine is None:
+                from .engine import Engine
+                self.engine = Engine(self.device)
+            net = self._nets[path] = EsrganNet(load_esrgan_checkpoint(path), device=self.device, engine=self.engine)
+        return net
+
+    def do_upscale(self, img, selected_model=None):
+        import torch
+        net = self.load_model(selected_model)
+        rgb = np.array(img.convert("RGB"))
+        h, w = rgb.shape[:2]
+        f = 4 // net.scale                                   # the x2 / x1 models pixel-unshuffle: sides padded up to a multiple, cropped after
+        ph, pw = -h % f, -w % f
+        if ph or pw:
+            rgb = np.pad(rgb, ((0, ph), (0, pw), (0, 0)), mode="reflect" if min(h, w) > max(ph, pw) else "edge")
+        x = torch.from_numpy(np.ascontiguousarray(rgb)[None]).to(f"cuda:{self.device}")
+        out = net.run(x, out_u8=True)[0].cpu().numpy()
+        return Image.fromarray(out[:h * net.scale, :w * net.scale])
+
+
+def register_esrgan(paths, device=0, engine=None):
+    """Append one ``UpscalerData(name, path, scaler, scale)`` per checkpoint to shared.sd_upscalers (after the built-ins, which are
+    installed first if the list is empty): `paths` is a {name: path} mapping or a list of paths (name = the file's stem), so
+    hr_upscaler="R-ESRGAN 4x+" and opts.upscaler_for_img2img resolve through _resize_to.  The scale is read from the checkpoint.
+    engine: see UpscalerESRGAN (all entries of one call share one scaler object and so one engine)."""
+    if not shared.sd_upscalers:
+        shared.sd_upscalers = builtin_upscalers()
+    items = paths.items() if isinstance(paths, dict) else [(os.path.splitext(os.path.basename(p))[0], p) for p in paths]
+    scaler = UpscalerESRGAN(device, engine)
+    added = []
+    for name, path in items:
+        _, _, _, scale = parse_esrgan_state_dict(load_esrgan_checkpoint(path))
+        data = UpscalerData(name, path, scaler, scale)
+        scaler.scalers.append(data)
+        shared.sd_upscalers.append(data)
+        added.append(data)
+    return added
 
 
 def _resize_to(im, w, h, upscaler_name):

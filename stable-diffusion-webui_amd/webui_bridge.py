@@ -675,3 +675,43 @@ def _unhook(emb):
 def uninstall_clip_hook(sd_model):
     for emb in _clip_embedders(sd_model):
         _unhook(emb)
+
+
+# ---- image-space upscalers ----------------------------------------------------------------------------------------------------------
+def install_esrgan_hook(webui_shared, device_index: int = 0):
+    """Point the webui's own ESRGAN / Real-ESRGAN scaler objects at the engine.  Every ``UpscalerData`` of ``webui_shared.sd_upscalers``
+    whose scaler class is UpscalerESRGAN or UpscalerRealESRGAN (modules/esrgan_model.py, modules/realesrgan_model.py) keeps its name,
+    path resolution and the ``Upscaler.upscale`` driver loop; only ``do_upscale(img, selected_info)`` changes: the checkpoint the stock
+    code would load (``load_model``'s local path for ESRGAN, ``UpscalerData.local_data_path`` / ``data_path`` for Real-ESRGAN) runs as
+    rrdb_conv launches on the image whole instead of as a torch module in tiles.  Whatever the engine cannot take stays on the stock
+    path: a checkpoint that is not a 64 / 32 RRDBNet or that fails to load or pack for any reason, and an image too large for the arena.  Returns the names of the hooked entries."""
+    from . import upscaler as amd_upscaler
+    engine_scaler = amd_upscaler.UpscalerESRGAN(device_index)
+    hooked = []
+    for data in getattr(webui_shared, "sd_upscalers", []):
+        scaler = getattr(data, "scaler", None)
+        if scaler is None or type(scaler).__name__ not in ("UpscalerESRGAN", "UpscalerRealESRGAN"):
+            continue
+        hooked.append(data.name)
+        if hasattr(scaler.do_upscale, "_mi355x_stock"):
+            continue
+        stock = scaler.do_upscale
+
+        def do_upscale(img, selected_model=None, _stock=stock, _scaler=scaler):
+            path = selected_model
+            info = next((d for d in getattr(_scaler, "scalers", []) if selected_model in (d.data_path, d.name)), None)
+            if info is not None:                                  # Real-ESRGAN's rule: the downloaded file when there is one
+                path = getattr(info, "local_data_path", None) or info.data_path
+            if isinstance(path, str) and path.startswith("http"):
+                return _stock(img, selected_model)                # not on disk yet: the stock code downloads (and runs) it
+            try:
+                engine_scaler.load_model(path)
+            except Exception:                                     # not an RRDBNet the engine is built for (ValueError), a file the
+                return _stock(img, selected_model)                # weights-only loader refuses, an engine error: what worked before still works
+            try:
+                return engine_scaler.do_upscale(img, path)
+            except amd_upscaler.EsrganInputTooLarge:
+                return _stock(img, selected_model)                # the stock path tiles (ESRGAN_tile) what the arena cannot hold whole
+        do_upscale._mi355x_stock = stock
+        scaler.do_upscale = do_upscale
+    return hooked
