@@ -489,6 +489,50 @@ int64_t sdmi_esrgan_scratch_bytes(sdmi_esrgan* h, int B, int H, int W);
  * out: fp32 NCHW [B][3][H s][W s], or (out_u8 = 1) uint8 HWC [B][H s][W s][3] with the reference's clamp / x255 / np.round. */
 int sdmi_esrgan_run(sdmi_esrgan* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
 
+/* ---- compact Real-ESRGAN upscalers (SRVGGNetCompact) --------------------------------------------------------------------------------- */
+
+/* One launch of the compact networks' 3x3 conv (csrc/compact.hip): stride 1, pad 1, fp16 NHWC, 32 or 64 input and 64 output channels,
+ * fp32 accumulation, the layer's weights and an 18 x 18 halo tile resident in LDS.  Replaces one `conv` + `PReLU` pair of the
+ * `for i in range(0, len(self.body)): out = self.body[i](out)` loop of SRVGGNetCompact.forward (realesrgan/archs/srvgg_arch.py:58-60;
+ * the webui's modules/realesrgan_model.py loads the network through spandrel), and with SDMI_COMPACT_EP_TAIL the last conv together with
+ * `out = self.upsampler(out)`, `base = F.interpolate(x, scale_factor=self.upscale, mode='nearest')`, `out += base` (:62-65). */
+enum {
+    SDMI_COMPACT_EP_NONE = 0,   /* acc + bias -> fp16 NHWC rows of stride ldo */
+    SDMI_COMPACT_EP_PRELU = 1,  /* v > 0 ? v : slope[c] * v (nn.PReLU(num_parameters=64)) -> fp16 NHWC */
+    SDMI_COMPACT_EP_TAIL = 2    /* pixel_shuffle(r) + nearest-upsampled `base` -> fp32 NCHW, or uint8 HWC (clamp, x255, np.round) */
+};
+typedef struct sdmi_compact_desc {
+    const void* in;        /* fp16 NHWC, row stride lda >= cin; must not overlap out */
+    const void* w;         /* fp16 [64][9][cin] (sdmi_pack_conv_weight with O_pad = 64, I_pad = cin) */
+    const void* bias;      /* fp32 [64] or NULL */
+    const void* slope;     /* fp32 [64] (PRELU) */
+    const void* base;      /* TAIL: the network's input, uint8 [B][H][W][3] (base_u8 = 1; / 255) or fp32 [B][3][H][W] */
+    void* out;             /* fp16 rows | TAIL: fp32 [B][3][H r][W r], or (out_u8 = 1) uint8 [B][H r][W r][3] */
+    int32_t B, H, W;
+    int32_t cin;           /* 32 or 64 */
+    int32_t lda, ldo;      /* ldo: fp16 store only (0 with TAIL) */
+    int32_t n_real;        /* channels stored, <= 64; TAIL: 3 r^2 */
+    int32_t ep;
+    int32_t r;             /* TAIL: pixel-shuffle factor 1..4 */
+    int32_t base_u8, out_u8;
+    int32_t grid_cap;      /* 0: min(tiles, CUs) persistent workgroups; n > 0: at most n */
+} sdmi_compact_desc;
+int sdmi_compact_conv(const sdmi_compact_desc* d, void* stream);
+
+/* A whole SRVGGNetCompact (num_feat 64, PReLU) held by an engine (scratch from the engine's arena).  Replaces the model call inside
+ * upscale_without_tiling / tiled_upscale (modules/upscaler_utils.py:44-60, :63-140, reached from UpscalerRealESRGAN.do_upscale,
+ * modules/realesrgan_model.py:36-69, for "R-ESRGAN General 4xV3", "R-ESRGAN General WDN 4xV3" and "R-ESRGAN AnimeVideo", :72-130), run
+ * on the image whole.  blob: host fp32, per conv in checkpoint order (body.0, body.2, ...) the OIHW weight, the bias, then (all but the
+ * last conv) the 64 PReLU slopes; sdmi_compact_blob_floats gives its length.  NULL on error. */
+typedef struct sdmi_compact sdmi_compact;
+int64_t sdmi_compact_blob_floats(int num_conv, int scale);
+sdmi_compact* sdmi_compact_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, int num_conv, int scale);
+void sdmi_compact_destroy(sdmi_compact* h);
+/* arena bytes a run on B images of H x W needs: the padded input and two 64-wide low-resolution buffers */
+int64_t sdmi_compact_scratch_bytes(sdmi_compact* h, int B, int H, int W);
+/* in / out as sdmi_esrgan_run: uint8 HWC or fp32 NCHW in, fp32 NCHW or uint8 HWC [B][H s][W s][3] out (device memory). */
+int sdmi_compact_run(sdmi_compact* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

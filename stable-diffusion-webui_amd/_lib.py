@@ -17,6 +17,7 @@ EP_TRANSPOSE = 64
 EP_WRAP = 128
 RRDB_EP_NONE, RRDB_EP_LRELU, RRDB_EP_RES1, RRDB_EP_RES2 = 0, 1, 2, 3
 RRDB_ST_F16, RRDB_ST_F32_NCHW, RRDB_ST_U8_HWC = 0, 1, 2
+COMPACT_EP_NONE, COMPACT_EP_PRELU, COMPACT_EP_TAIL = 0, 1, 2
 
 
 class SdmiError(RuntimeError):
@@ -44,6 +45,14 @@ class RrdbDesc(C.Structure):
         ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("cin", C.c_int32), ("lda", C.c_int32), ("up", C.c_int32),
         ("nout", C.c_int32), ("n_real", C.c_int32), ("ldo", C.c_int32), ("ldr1", C.c_int32), ("ldr2", C.c_int32),
         ("ep", C.c_int32), ("store", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float),
+    ]
+
+
+class CompactDesc(C.Structure):
+    _fields_ = [
+        ("in_", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("slope", C.c_void_p), ("base", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("cin", C.c_int32), ("lda", C.c_int32), ("ldo", C.c_int32),
+        ("n_real", C.c_int32), ("ep", C.c_int32), ("r", C.c_int32), ("base_u8", C.c_int32), ("out_u8", C.c_int32), ("grid_cap", C.c_int32),
     ]
 
 
@@ -165,6 +174,12 @@ _SIGS = {
     "sdmi_esrgan_destroy": (None, [_vp]),
     "sdmi_esrgan_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
     "sdmi_esrgan_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "sdmi_compact_conv": (_i, [C.POINTER(CompactDesc), _vp]),
+    "sdmi_compact_blob_floats": (_i64, [_i, _i]),
+    "sdmi_compact_create": (_vp, [_vp, _vp, _i64, _i, _i]),
+    "sdmi_compact_destroy": (None, [_vp]),
+    "sdmi_compact_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
+    "sdmi_compact_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)       # AttributeError here == the .so does not export a declared symbol

@@ -30,6 +30,10 @@ int64_t esrgan_blob_floats(int num_block, int in_ch);
 int esrgan_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_block, int in_ch, int scale, sdmi_esrgan** out);
 int64_t esrgan_scratch_bytes(const sdmi_esrgan* n, int B, int H, int W);
 int esrgan_run(sdmi_esrgan* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
+int64_t compact_blob_floats(int num_conv, int scale);
+int compact_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_conv, int scale, sdmi_compact** out);
+int64_t compact_scratch_bytes(const sdmi_compact* n, int B, int H, int W);
+int compact_run(sdmi_compact* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
 }  // namespace sdmi
 
 using namespace sdmi;
@@ -610,6 +614,41 @@ int64_t sdmi_esrgan_scratch_bytes(sdmi_esrgan* h, int B, int H, int W) { return 
 int sdmi_esrgan_run(sdmi_esrgan* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
     API_GUARD_BEGIN
     return esrgan_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_compact_conv(const sdmi_compact_desc* d, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(d, "null descriptor");
+    CompactP p{};
+    p.in = (const half_t*)d->in; p.w = (const half_t*)d->w; p.bias = (const float*)d->bias; p.slope = (const float*)d->slope;
+    p.base = d->base; p.out = d->out;
+    p.B = d->B; p.H = d->H; p.W = d->W; p.cin = d->cin; p.lda = d->lda; p.ldo = d->ldo; p.n_real = d->n_real;
+    p.ep = d->ep; p.r = d->r; p.base_u8 = d->base_u8; p.out_u8 = d->out_u8; p.grid_cap = d->grid_cap;
+    return launch_compact_conv(p, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int64_t sdmi_compact_blob_floats(int num_conv, int scale) { return compact_blob_floats(num_conv, scale); }
+
+sdmi_compact* sdmi_compact_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, int num_conv, int scale) {
+    try {
+        sdmi_compact* n = nullptr;
+        if (compact_create(e, (const float*)blob_f32, blob_floats, num_conv, scale, &n) != 0) return nullptr;
+        return n;
+    } catch (const std::exception& ex) {
+        set_error(std::string("exception: ") + ex.what());
+        return nullptr;
+    }
+}
+
+void sdmi_compact_destroy(sdmi_compact* h) { delete h; }
+
+int64_t sdmi_compact_scratch_bytes(sdmi_compact* h, int B, int H, int W) { return compact_scratch_bytes(h, B, H, W); }
+
+int sdmi_compact_run(sdmi_compact* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
+    API_GUARD_BEGIN
+    return compact_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
     API_GUARD_END
 }
 

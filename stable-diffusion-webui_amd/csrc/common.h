@@ -254,6 +254,26 @@ int launch_rrdb_conv(const RrdbP& p, int nout, hipStream_t s);
 // RGB image (uint8 HWC / 255, or fp32 NCHW) -> pixel-unshuffle by f -> NHWC fp16 rows of cpad channels (zero padded)
 int launch_rrdb_input(const void* in, int u8, half_t* out, int B, int C, int H, int W, int f, int cpad, hipStream_t s);
 
+// ---- compact Real-ESRGAN 3x3 conv (compact.hip) --------------------------------------------------------------
+enum { COMPACT_EP_NONE = 0, COMPACT_EP_PRELU = 1,   // v = acc + bias;  v > 0 ? v : slope[c] * v       -> fp16 NHWC rows of stride ldo
+       COMPACT_EP_TAIL = 2 };                      // pixel shuffle by r + nearest-upsampled network input -> fp32 NCHW | uint8 HWC
+struct CompactP {
+    const half_t* in;      // NHWC rows of stride lda; the first cin (32 | 64) channels are read
+    const half_t* w;       // [64][9][cin] fp16 (launch_pack_conv_weight layout)
+    const float* bias;     // [64] or null
+    const float* slope;    // [64] PReLU slopes (COMPACT_EP_PRELU)
+    const void* base;      // TAIL: the network's input, uint8 [B][H][W][3] (base_u8; / 255) or fp32 [B][3][H][W]
+    void* out;             // fp16 rows of stride ldo | TAIL: fp32 [B][3][H r][W r] or (out_u8) uint8 [B][H r][W r][3]
+    const half_t* zero;    // set by the launcher
+    int B, H, W;
+    int cin, lda, ldo, n_real;
+    int ep, r, base_u8, out_u8;
+    int grid_cap;          // 0: min(tiles, CUs) workgroups; n > 0: at most n
+    int tiles_x, tiles_y;  // set by the launcher: 16 x 16-pixel tiles per image
+    int tiles;             // B * tiles_y * tiles_x
+};
+int launch_compact_conv(const CompactP& p, hipStream_t s);
+
 // ---- norms ------------------------------------------------------------------------------------------------
 // pre_nchunk > 0: `ws` already holds (mean, M2) [B][pre_nchunk][groups][2] of HW / pre_nchunk rows each (written by the producing GEMM): skip the statistics pass
 // x0_lo / x1_lo (engine option "residual_fp32"): the lo parts when the inputs are (hi, lo) fp16 pairs of the carried stream

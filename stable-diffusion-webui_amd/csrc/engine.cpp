@@ -2099,7 +2099,111 @@ int esrgan_run(sdmi_esrgan* n, const void* in, int in_u8, int B, int H, int W, v
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Compact Real-ESRGAN upscalers: SRVGGNetCompact.forward (realesrgan/archs/srvgg_arch.py) as compact_conv launches
+// ------------------------------------------------------------------------------------------------------------
+// blob: fp32, for every conv in checkpoint order (body.0, body.2, ..., body.{2 (num_conv + 1)}) the OIHW weight, the bias, then (all
+// but the last conv) the 64 PReLU slopes.
+int64_t compact_blob_floats(int num_conv, int scale) {
+    return (64 * 3 * 9 + 64 + 64) + (int64_t)num_conv * (64 * 64 * 9 + 64 + 64) + (3 * scale * scale * 64 * 9 + 3 * scale * scale);
+}
+
+int compact_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_conv, int scale, sdmi_compact** out) {
+    SDMI_REQUIRE(e && blob && out, "null argument");
+    SDMI_REQUIRE(num_conv >= 1 && num_conv <= 256, "num_conv");
+    SDMI_REQUIRE(scale >= 1 && scale <= 4, "SRVGGNetCompact: scale 1..4 (3 scale^2 <= 64 channels to shuffle)");
+    SDMI_REQUIRE(blob_floats == compact_blob_floats(num_conv, scale), "weight blob size does not match num_conv / scale");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    std::unique_ptr<sdmi_compact> net(new sdmi_compact);
+    net->e = e; net->num_conv = num_conv; net->scale = scale;
+    float* dblob = nullptr;
+    SDMI_CHECK_HIP(hipMalloc((void**)&dblob, blob_floats * sizeof(float)));
+    struct Free { float* p; ~Free() { (void)hipFree(p); } } guard{dblob};
+    SDMI_CHECK_HIP(hipMemcpy(dblob, blob, blob_floats * sizeof(float), hipMemcpyHostToDevice));
+    int64_t off = 0;
+    net->convs.resize((size_t)num_conv + 2);
+    for (int i = 0; i < num_conv + 2; ++i) {
+        sdmi_compact::Conv* c = &net->convs[(size_t)i];
+        const int O = i == num_conv + 1 ? 3 * scale * scale : 64, I = i == 0 ? 3 : 64, cin = i == 0 ? 32 : 64;
+        SDMI_CHECK_HIP(hipMalloc((void**)&c->w, (size_t)64 * 9 * cin * sizeof(half_t)));
+        net->owned.push_back(c->w);
+        SDMI_CHECK_HIP(hipMalloc((void**)&c->b, 2 * 64 * sizeof(float)));
+        net->owned.push_back(c->b);
+        c->slope = c->b + 64;
+        TRY(launch_pack_conv_weight(dblob + off, 1, c->w, O, I, 3, 3, 64, cin, 0, nullptr));
+        off += (int64_t)O * I * 9;
+        SDMI_CHECK_HIP(hipMemset(c->b, 0, 2 * 64 * sizeof(float)));
+        SDMI_CHECK_HIP(hipMemcpy(c->b, dblob + off, (size_t)O * sizeof(float), hipMemcpyDeviceToDevice));
+        off += O;
+        if (i <= num_conv) {
+            SDMI_CHECK_HIP(hipMemcpy(c->slope, dblob + off, 64 * sizeof(float), hipMemcpyDeviceToDevice));
+            off += 64;
+        }
+    }
+    SDMI_CHECK_HIP(hipDeviceSynchronize());
+    *out = net.release();
+    return 0;
+}
+
+namespace {
+struct CompactBufs { half_t *in, *x[2]; };
+CompactBufs compact_take(Arena& ar, size_t M) {
+    CompactBufs b;
+    ar.reset();
+    b.in = (half_t*)ar.take(M * 32 * sizeof(half_t));
+    for (int i = 0; i < 2; ++i) b.x[i] = (half_t*)ar.take(M * 64 * sizeof(half_t));
+    return b;
+}
+}  // namespace
+
+int64_t compact_scratch_bytes(const sdmi_compact* n, int B, int H, int W) {
+    if (!n || B <= 0 || H <= 0 || W <= 0) return 0;
+    Arena ar;
+    ar.dry = true;
+    compact_take(ar, (size_t)B * H * W);
+    return (int64_t)ar.high;
+}
+
+// in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
+// out: [B][3][H s][W s] fp32 NCHW, or (out_u8) uint8 HWC [B][H s][W s][3] = round_half_even(clamp(y, 0, 1) * 255).
+int compact_run(sdmi_compact* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s) {
+    SDMI_REQUIRE(n && in && out, "null argument");
+    sdmi_engine* e = n->e;
+    SDMI_REQUIRE(B > 0 && H > 0 && W > 0, "empty image");
+    SDMI_REQUIRE((long long)B * H * W * n->scale * n->scale < (1ll << 31) - 256, "image too large: the output must stay below 2^31 pixels");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    const size_t M = (size_t)B * H * W;
+    e->arena.dry = true; e->arena.high = 0;
+    compact_take(e->arena, M);
+    e->arena.dry = false;
+    TRY(ensure_arena(e, e->arena.high, s));
+    const CompactBufs b = compact_take(e->arena, M);
+
+    TRY(launch_rrdb_input(in, in_u8, b.in, B, 3, H, W, 1, 32, s));
+    const half_t* src = b.in;
+    for (int i = 0; i < n->num_conv + 2; ++i) {
+        const sdmi_compact::Conv& c = n->convs[(size_t)i];
+        const bool last = i == n->num_conv + 1;
+        CompactP p{};
+        p.in = src; p.w = c.w; p.bias = c.b; p.slope = c.slope;
+        p.B = B; p.H = H; p.W = W; p.cin = i == 0 ? 32 : 64; p.lda = p.cin;
+        if (last) {                                   // the activations never see a high-resolution tensor
+            p.ep = COMPACT_EP_TAIL; p.r = n->scale; p.n_real = 3 * n->scale * n->scale;
+            p.base = in; p.base_u8 = in_u8; p.out = out; p.out_u8 = out_u8;
+        } else {
+            p.ep = COMPACT_EP_PRELU; p.n_real = 64; p.out = b.x[i & 1]; p.ldo = 64;
+            src = b.x[i & 1];
+        }
+        TRY(launch_compact_conv(p, s));
+    }
+    return 0;
+}
+
 }  // namespace sdmi
+
+sdmi_compact::~sdmi_compact() {
+    for (void* p : owned) (void)hipFree(p);
+}
 
 sdmi_esrgan::~sdmi_esrgan() {
     for (void* p : owned) (void)hipFree(p);
@@ -2124,8 +2228,9 @@ sdmi_engine::~sdmi_engine() {
     if (ev_fork) (void)hipEventDestroy(ev_fork);
 }
 
-// The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units; there the RRDBNet
-// kernel file travels inside this one.  The GPU build compiles rrdb.hip on its own (build.sh).
+// The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units; there the upscalers'
+// kernel files travel inside this one.  The GPU build compiles rrdb.hip and compact.hip on their own (build.sh).
 #ifndef __HIP__
 #include "rrdb.hip"
+#include "compact.hip"
 #endif

@@ -256,3 +256,14 @@ struct sdmi_esrgan {
     std::vector<void*> owned;
     ~sdmi_esrgan();
 };
+
+// Compact Real-ESRGAN upscaler (SRVGGNetCompact, 64 features, PReLU): packed weights of the compact_conv launches (compact.hip).
+// Activations come from the owning engine's arena; the net is immutable after sdmi_compact_create.
+struct sdmi_compact {
+    struct Conv { half_t* w = nullptr; float* b = nullptr; float* slope = nullptr; };
+    sdmi_engine* e = nullptr;
+    int num_conv = 0, scale = 0;
+    std::vector<Conv> convs;                  // num_conv + 2: first (3 -> 64), body, last (64 -> 3 scale^2; no PReLU after it)
+    std::vector<void*> owned;
+    ~sdmi_compact();
+};

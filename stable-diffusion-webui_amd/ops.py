@@ -317,3 +317,59 @@ def rrdb_conv(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tens
         d.out = out.data_ptr()
     check(lib.sdmi_rrdb_conv(C.byref(d), stream_ptr()), "sdmi_rrdb_conv")
     return out
+
+
+def pack_compact_weight(w: torch.Tensor) -> torch.Tensor:
+    """OIHW 3x3 weight -> fp16 [64][9][cin] for compact_conv: output channels zero-padded to 64 (the last conv: 3 r^2 -> 64), input
+    channels to 32 (the first conv: 3 -> 32) or 64."""
+    _lib.require_device()
+    w = w.contiguous()
+    o, i, kh, kw = w.shape
+    assert (kh, kw) == (3, 3) and o <= 64 and i <= 64
+    cin = _rup(i, 32)
+    out = torch.empty((64, 9, cin), dtype=torch.float16, device=w.device)
+    check(lib.sdmi_pack_conv_weight(ptr(w), _lib.dtype_code(w), ptr(out), o, i, 3, 3, 64, cin, 0, stream_ptr()), "pack_compact_weight")
+    return out
+
+
+def compact_conv(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor] = None, *, slope: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, n_real: Optional[int] = None, ep: str = "prelu", r: int = 0,
+                 base: Optional[torch.Tensor] = None, store: str = "f32_nchw", grid_cap: int = 0) -> torch.Tensor:
+    """One launch of the compact Real-ESRGAN 3x3 conv (csrc/compact.hip; a conv + PReLU pair of SRVGGNetCompact.forward,
+    realesrgan/archs/srvgg_arch.py).  x [B,H,W,lda] fp16 NHWC: its first cin = w_packed.shape[2] (32 | 64) channels are the input.
+    ep "none" | "prelu" (slope: fp32 [64]): n_real (default 64) channels go to the first channels of `out` [B,H,W,ldo] (fp16; made if
+    None; never x itself).  ep "tail": the last conv, n_real = 3 r^2 — pixel shuffle by r plus the nearest-upsampled `base` (the network's
+    input: uint8 [B,H,W,3], divided by 255, or fp32 [B,3,H,W]) -> store "f32_nchw" [B,3,H r,W r] fp32 or "u8_hwc" [B,H r,W r,3] uint8
+    (clamp, x255, round half to even).  grid_cap: 0 = one persistent workgroup per tile up to the CU count; n > 0: at most n workgroups."""
+    _lib.require_device()
+    assert x.dtype == torch.float16 and x.is_contiguous() and w_packed.dtype == torch.float16 and w_packed.is_contiguous()
+    b, h, w, lda = x.shape
+    d = _lib.CompactDesc()
+    d.in_, d.w = x.data_ptr(), w_packed.data_ptr()
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == 64
+        d.bias = bias.data_ptr()
+    if slope is not None:
+        assert slope.dtype == torch.float32 and slope.numel() == 64
+        d.slope = slope.data_ptr()
+    d.B, d.H, d.W, d.cin, d.lda = b, h, w, w_packed.shape[2], lda
+    d.ep = {"none": _lib.COMPACT_EP_NONE, "prelu": _lib.COMPACT_EP_PRELU, "tail": _lib.COMPACT_EP_TAIL}[ep]
+    d.grid_cap = grid_cap
+    if ep == "tail":
+        d.r, d.n_real = r, (3 * r * r if n_real is None else n_real)
+        if base is not None:
+            assert base.is_contiguous() and base.dtype in (torch.uint8, torch.float32)
+            assert tuple(base.shape) == ((b, h, w, 3) if base.dtype == torch.uint8 else (b, 3, h, w))
+            d.base, d.base_u8 = base.data_ptr(), 1 if base.dtype == torch.uint8 else 0
+        rs = max(r, 0)
+        out = (torch.empty((b, h * rs, w * rs, 3), dtype=torch.uint8, device=x.device) if store == "u8_hwc"
+               else torch.empty((b, 3, h * rs, w * rs), dtype=torch.float32, device=x.device))
+        d.out, d.out_u8 = out.data_ptr(), 1 if store == "u8_hwc" else 0
+    else:
+        d.n_real = 64 if n_real is None else n_real
+        if out is None:
+            out = torch.empty((b, h, w, d.n_real), dtype=torch.float16, device=x.device)
+        assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape[:3]) == (b, h, w)
+        d.out, d.ldo = out.data_ptr(), out.shape[3]
+    check(lib.sdmi_compact_conv(C.byref(d), stream_ptr()), "sdmi_compact_conv")
+    return out

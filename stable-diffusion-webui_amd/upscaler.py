@@ -3,8 +3,9 @@
 The engine's part is decode -> [host image resize] -> encode; the resize itself stays the reference's job.  This module is
 the seam: the registry ``shared.sd_upscalers`` of ``UpscalerData(name, path, scaler)`` entries the reference's code looks names
 up in (modules/images.py:276, modules/modelloader.py:136), the ``Upscaler.upscale`` driver loop (modules/upscaler.py:54-76) and
-the three built-in PIL scalers (None / Lanczos / Nearest, modules/upscaler.py:107-154).  The RRDBNet family (ESRGAN, Real-ESRGAN)
-runs on the engine (``UpscalerESRGAN`` / ``register_esrgan`` below, csrc/rrdb.hip); other model upscalers (SwinIR, ...) register their own
+the three built-in PIL scalers (None / Lanczos / Nearest, modules/upscaler.py:107-154).  The RRDBNet family (ESRGAN, Real-ESRGAN) and the
+compact Real-ESRGAN models (SRVGGNetCompact: General 4xV3, General WDN 4xV3, AnimeVideo) run on the engine (``UpscalerESRGAN`` /
+``register_esrgan`` below, csrc/rrdb.hip and csrc/compact.hip); other model upscalers (SwinIR, ...) register their own
 ``UpscalerData`` whose ``scaler.upscale(img, scale, path)`` is called as in the reference.
 """
 from __future__ import annotations
@@ -164,6 +165,74 @@ def parse_esrgan_state_dict(sd):
     return np.ascontiguousarray(np.concatenate(parts)), num_block, in_ch, scale
 
 
+def _as_f32(t):
+    return np.asarray(t.detach().float().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32).ravel()
+
+
+def _unwrap_state_dict(sd):
+    for wrap in ("params_ema", "params"):
+        if wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+            break
+    return {k: v for k, v in sd.items() if hasattr(v, "shape")}
+
+
+def parse_compact_state_dict(sd):
+    """Checkpoint state dict of a compact Real-ESRGAN model (SRVGGNetCompact, realesrgan/archs/srvgg_arch.py: body.{2i} = conv i,
+    body.{2i+1} = the PReLU after it, none after the last conv) -> (blob, num_conv, scale): the engine's weight blob (fp32, per conv
+    the OIHW weight, the bias, then — all but the last conv — the 64 PReLU slopes: sdmi_compact_create), the number of body convs read
+    from the key indices (32 for General 4xV3, 16 for AnimeVideo) and the scale r = sqrt(out_ch / 3) of the last conv.  Host only.
+    Raises ValueError on anything that is not a 64-feature, 3-channel, PReLU network of scale 1..4."""
+    sd = _unwrap_state_dict(sd)
+    convs = sorted(int(m.group(1)) for k in sd for m in [re.match(r"body\.(\d+)\.weight$", k)] if m and len(sd[k].shape) == 4)
+    if "body.0.weight" not in sd or len(sd["body.0.weight"].shape) != 4:
+        raise ValueError("not a compact (SRVGGNetCompact) checkpoint: no 4-d body.0.weight")
+    if len(convs) < 3 or convs != list(range(0, 2 * len(convs), 2)):
+        raise ValueError(f"compact network: conv indices are not body.0, body.2, ... without gaps: {convs[:6]}{' ...' if len(convs) > 6 else ''}")
+    num_conv = len(convs) - 2
+    feat, in_ch = int(sd["body.0.weight"].shape[0]), int(sd["body.0.weight"].shape[1])
+    if feat != 64:
+        raise ValueError(f"compact network num_feat = {feat}: the engine's kernel is built for 64")
+    if in_ch != 3:
+        raise ValueError(f"compact network takes {in_ch} input channels: expected 3")
+    out_ch = int(sd[f"body.{convs[-1]}.weight"].shape[0])
+    scale = int(round((out_ch / 3.0) ** 0.5))
+    if out_ch != 3 * scale * scale or scale not in (1, 2, 3, 4):
+        raise ValueError(f"compact network: the last conv has {out_ch} channels, expected 3 r^2 with scale r in 1..4")
+    parts = []
+    for n, i in enumerate(convs):
+        want = (64 if n <= num_conv else out_ch, 3 if n == 0 else 64, 3, 3)
+        w, b = sd[f"body.{i}.weight"], sd.get(f"body.{i}.bias")
+        if tuple(w.shape) != want:
+            raise ValueError(f"compact network body.{i}: weight {tuple(w.shape)}, expected {want} (3x3 convs of 64 features)")
+        if b is None or tuple(b.shape) != (want[0],):
+            raise ValueError(f"compact network body.{i}: bias missing or not of shape {(want[0],)}")
+        parts += [_as_f32(w), _as_f32(b)]
+        if n <= num_conv:
+            a = sd.get(f"body.{i + 1}.weight")
+            if a is None or tuple(a.shape) != (64,):
+                raise ValueError(f"compact network body.{i + 1}: no PReLU weight of shape (64,) (a relu / leakyrelu build has none; "
+                                 f"only act_type = 'prelu' runs on the engine)")
+            parts.append(_as_f32(a))
+    return np.ascontiguousarray(np.concatenate(parts)), num_conv, scale
+
+
+def upscaler_family(sd):
+    """"rrdb" | "compact" by the key layout: conv_first.weight / model.0.weight mark an RRDBNet, a 4-d body.0.weight without them a
+    compact network.  Anything else counts as "rrdb" and gets that loader's refusal."""
+    keys = _unwrap_state_dict(sd)
+    if "conv_first.weight" not in keys and "model.0.weight" not in keys and len(getattr(keys.get("body.0.weight"), "shape", ())) == 4:
+        return "compact"
+    return "rrdb"
+
+
+def parse_upscaler_state_dict(sd):
+    """The dispatcher over the checkpoints the engine runs -> ("rrdb", parse_esrgan_state_dict(sd)) or
+    ("compact", parse_compact_state_dict(sd)); the scale is the last member of either tuple."""
+    family = upscaler_family(sd)
+    return family, (parse_compact_state_dict if family == "compact" else parse_esrgan_state_dict)(sd)
+
+
 def load_esrgan_checkpoint(path):
     """.pth (torch.load, weights_only) or .safetensors -> state dict."""
     if str(path).lower().endswith(".safetensors"):
@@ -248,10 +317,73 @@ class EsrganNet:
         return out
 
 
+class CompactNet:
+    """One compact Real-ESRGAN network (SRVGGNetCompact) resident on an engine (sdmi_compact_*): the twin of EsrganNet."""
+
+    def __init__(self, state_dict, device=0, engine=None):
+        from . import _lib
+        from .engine import Engine
+        blob, self.num_conv, self.scale = parse_compact_state_dict(state_dict)
+        self.device = int(device)
+        self.engine = engine or Engine(self.device)
+        self.handle = _lib.lib.sdmi_compact_create(self.engine.handle, blob.ctypes.data, blob.size, self.num_conv, self.scale)
+        if not self.handle:
+            raise _lib.SdmiError("sdmi_compact_create failed: " + _lib.last_error())
+
+    def close(self):
+        if getattr(self, "handle", None):
+            from . import _lib
+            _lib.lib.sdmi_compact_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def scratch_bytes(self, b, h, w):
+        """Arena bytes of one run, from the engine's own layout (sdmi_compact_scratch_bytes)."""
+        from . import _lib
+        return int(_lib.lib.sdmi_compact_scratch_bytes(self.handle, b, h, w))
+
+    def check_fits(self, b, h, w):
+        """Refuse an input whose intermediates (the padded input and two 64-wide buffers, all at the INPUT resolution) the arena cannot
+        hold, or whose output passes 2^31 pixels."""
+        need = self.scratch_bytes(b, h, w)
+        limit = arena_limit_bytes(self.device) + self.engine.arena_bytes()
+        if b * h * w * self.scale * self.scale >= (1 << 31) - 256 or need > limit:
+            raise EsrganInputTooLarge(f"image {w}x{h} (batch {b}) is too large for the x{self.scale} upscaler: its intermediates need "
+                                      f"{need / 2 ** 30:.1f} GiB of engine arena, {limit / 2 ** 30:.1f} GiB are available")
+
+    def run(self, x, out_u8=False):
+        """x: uint8 [B,H,W,3] (RGB; divided by 255 on the way in) or fp32 [B,3,H,W] in [0, 1], on the engine's device ->
+        fp32 [B,3,H s,W s], or with out_u8 uint8 [B,H s,W s,3] (clamp, x255, round half to even).  Any H, W."""
+        import torch
+        from . import _lib
+        in_u8 = x.dtype == torch.uint8
+        x = x.contiguous() if in_u8 else x.float().contiguous()
+        b, h, w = (x.shape[0], x.shape[1], x.shape[2]) if in_u8 else (x.shape[0], x.shape[2], x.shape[3])
+        assert x.shape[3 if in_u8 else 1] == 3
+        self.check_fits(b, h, w)
+        s = self.scale
+        out = (torch.empty((b, h * s, w * s, 3), dtype=torch.uint8, device=x.device) if out_u8
+               else torch.empty((b, 3, h * s, w * s), dtype=torch.float32, device=x.device))
+        _lib.check(_lib.lib.sdmi_compact_run(self.handle, _lib.ptr(x), 1 if in_u8 else 0, b, h, w, _lib.ptr(out), 1 if out_u8 else 0,
+                                             _lib.stream_ptr()), "sdmi_compact_run")
+        return out
+
+
+def make_upscaler_net(state_dict, device=0, engine=None):
+    """EsrganNet or CompactNet, by the checkpoint's key layout (upscaler_family)."""
+    return (CompactNet if upscaler_family(state_dict) == "compact" else EsrganNet)(state_dict, device=device, engine=engine)
+
+
 class UpscalerESRGAN(Upscaler):
     """ESRGAN / Real-ESRGAN on the engine: what modules/esrgan_model.py:UpscalerESRGAN.do_upscale and
     modules/realesrgan_model.py:UpscalerRealESRGAN.do_upscale compute with ESRGAN_tile = 0 (the image whole; tiling exists there for
-    VRAM this card does not lack), with the uint8 hand-off of modules/upscaler_utils.py."""
+    VRAM this card does not lack), with the uint8 hand-off of modules/upscaler_utils.py.  RRDBNet checkpoints run as EsrganNet, the
+    compact Real-ESRGAN models (General 4xV3, General WDN 4xV3, AnimeVideo) as CompactNet."""
     name = "ESRGAN"
 
     def __init__(self, device=0, engine=None):
@@ -269,7 +401,7 @@ class UpscalerESRGAN(Upscaler):
             if self.engine is None:
                 from .engine import Engine
                 self.engine = Engine(self.device)
-            net = self._nets[path] = EsrganNet(load_esrgan_checkpoint(path), device=self.device, engine=self.engine)
+            net = self._nets[path] = make_upscaler_net(load_esrgan_checkpoint(path), device=self.device, engine=self.engine)
         return net
 
     def do_upscale(self, img, selected_model=None):
@@ -277,7 +409,7 @@ class UpscalerESRGAN(Upscaler):
         net = self.load_model(selected_model)
         rgb = np.array(img.convert("RGB"))
         h, w = rgb.shape[:2]
-        f = 4 // net.scale                                   # the x2 / x1 models pixel-unshuffle: sides padded up to a multiple, cropped after
+        f = 4 // net.scale if isinstance(net, EsrganNet) else 1   # the x2 / x1 RRDBNets pixel-unshuffle: sides padded up to a multiple, cropped after
         ph, pw = -h % f, -w % f
         if ph or pw:
             rgb = np.pad(rgb, ((0, ph), (0, pw), (0, 0)), mode="reflect" if min(h, w) > max(ph, pw) else "edge")
@@ -289,7 +421,8 @@ class UpscalerESRGAN(Upscaler):
 def register_esrgan(paths, device=0, engine=None):
     """Append one ``UpscalerData(name, path, scaler, scale)`` per checkpoint to shared.sd_upscalers (after the built-ins, which are
     installed first if the list is empty): `paths` is a {name: path} mapping or a list of paths (name = the file's stem), so
-    hr_upscaler="R-ESRGAN 4x+" and opts.upscaler_for_img2img resolve through _resize_to.  The scale is read from the checkpoint.
+    hr_upscaler="R-ESRGAN 4x+" and opts.upscaler_for_img2img resolve through _resize_to.  RRDBNet and compact (SRVGGNetCompact)
+    checkpoints may be mixed; the scale is read from the checkpoint.
     engine: see UpscalerESRGAN (all entries of one call share one scaler object and so one engine)."""
     if not shared.sd_upscalers:
         shared.sd_upscalers = builtin_upscalers()
@@ -297,7 +430,7 @@ def register_esrgan(paths, device=0, engine=None):
     scaler = UpscalerESRGAN(device, engine)
     added = []
     for name, path in items:
-        _, _, _, scale = parse_esrgan_state_dict(load_esrgan_checkpoint(path))
+        scale = parse_upscaler_state_dict(load_esrgan_checkpoint(path))[1][-1]
         data = UpscalerData(name, path, scaler, scale)
         scaler.scalers.append(data)
         shared.sd_upscalers.append(data)

@@ -683,8 +683,10 @@ def install_esrgan_hook(webui_shared, device_index: int = 0):
     whose scaler class is UpscalerESRGAN or UpscalerRealESRGAN (modules/esrgan_model.py, modules/realesrgan_model.py) keeps its name,
     path resolution and the ``Upscaler.upscale`` driver loop; only ``do_upscale(img, selected_info)`` changes: the checkpoint the stock
     code would load (``load_model``'s local path for ESRGAN, ``UpscalerData.local_data_path`` / ``data_path`` for Real-ESRGAN) runs as
-    rrdb_conv launches on the image whole instead of as a torch module in tiles.  Whatever the engine cannot take stays on the stock
-    path: a checkpoint that is not a 64 / 32 RRDBNet or that fails to load or pack for any reason, and an image too large for the arena.  Returns the names of the hooked entries."""
+    rrdb_conv launches (RRDBNets) or compact_conv launches (the SRVGGNetCompact models "R-ESRGAN General 4xV3", "General WDN 4xV3" and
+    "AnimeVideo") on the image whole instead of as a torch module in tiles.  Whatever the engine cannot take stays on the stock
+    path: a checkpoint that is neither a 64 / 32 RRDBNet nor a 64-feature PReLU compact network, or that fails to load or pack for any
+    reason, and an image too large for the arena.  Returns the names of the hooked entries."""
     from . import upscaler as amd_upscaler
     engine_scaler = amd_upscaler.UpscalerESRGAN(device_index)
     hooked = []
