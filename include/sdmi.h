@@ -195,7 +195,8 @@ int sdmi_cfg_combine_affine(const void* x_f32, const void* out_f32, const void* 
 int sdmi_euler_step(void* x_f32, const void* denoised_f32, const void* noise_f32_or_null,
                     float sigma, float sigma_down, float sigma_up, float s_noise, int64_t n, void* stream);
 
-/* k-diffusion sample_dpmpp_2m update: x = ratio*x - em1*(c1*den - c2*old_den)  (c2 = 0 on first/last step). */
+/* k-diffusion sample_dpmpp_2m update: x = ratio*x - em1*(c1*den - c2*old_den)  (c2 = 0 on first/last step).
+   With old_den null the c2 term is absent and c1 still scales den: x = ratio*x - em1*c1*den (the host passes c1 = 1 there). */
 int sdmi_dpmpp2m_step(void* x_f32, const void* denoised_f32, const void* old_denoised_f32_or_null,
                       float ratio, float em1, float c1, float c2, int64_t n, void* stream);
 

@@ -284,6 +284,7 @@ int sdmi_cfg_combine(const void* x, const void* eps, const void* c_out, float co
 int sdmi_euler_step(void* x, const void* den, const void* noise, float sigma, float sigma_down, float sigma_up, float s_noise,
                     int64_t n, void* stream) {
     API_GUARD_BEGIN
+    SDMI_REQUIRE(x && den && n >= 0, "sdmi_euler_step: null x / denoised or negative n");
     return launch_euler_step((float*)x, (const float*)den, (const float*)noise, sigma, sigma_down, sigma_up, s_noise, n,
                              (hipStream_t)stream);
     API_GUARD_END
@@ -292,6 +293,7 @@ int sdmi_euler_step(void* x, const void* den, const void* noise, float sigma, fl
 int sdmi_dpmpp2m_step(void* x, const void* den, const void* old, float ratio, float em1, float c1, float c2, int64_t n,
                       void* stream) {
     API_GUARD_BEGIN
+    SDMI_REQUIRE(x && den && n >= 0, "sdmi_dpmpp2m_step: null x / denoised or negative n");
     return launch_dpmpp2m_step((float*)x, (const float*)den, (const float*)old, ratio, em1, c1, c2, n, (hipStream_t)stream);
     API_GUARD_END
 }
@@ -299,6 +301,7 @@ int sdmi_dpmpp2m_step(void* x, const void* den, const void* old, float ratio, fl
 int sdmi_ddim_step(void* x, const void* e_t, const void* noise, void* pred_x0, float a_t, float a_prev, float sigma_t,
                    float sqrt_one_minus_at, int64_t n, void* stream) {
     API_GUARD_BEGIN
+    SDMI_REQUIRE(x && e_t && n >= 0, "sdmi_ddim_step: null x / e_t or negative n");
     return launch_ddim_step((float*)x, (const float*)e_t, (const float*)noise, (float*)pred_x0, a_t, a_prev, sigma_t,
                             sqrt_one_minus_at, n, (hipStream_t)stream);
     API_GUARD_END
@@ -345,6 +348,7 @@ int sdmi_mask_blend(void* x, const void* init, const void* mask, const void* nma
 
 int sdmi_axpby(void* y, const void* x, float a, const void* z, float b, int64_t n, void* stream) {
     API_GUARD_BEGIN
+    SDMI_REQUIRE(y && x && n >= 0, "sdmi_axpby: null y / x or negative n");
     return launch_axpby((float*)y, (const float*)x, a, (const float*)z, b, n, (hipStream_t)stream);
     API_GUARD_END
 }
@@ -409,6 +413,9 @@ int sdmi_lora_merge(void* out, const void* w, int w_dtype, const void* up, int u
                     int rows, int cols, int rank, float scale, void* stream) {
     API_GUARD_BEGIN
     SDMI_REQUIRE(out && w && up && down && rows > 0 && cols > 0 && rank > 0, "bad lora_merge arguments");
+    SDMI_REQUIRE((w_dtype == SDMI_F16 || w_dtype == SDMI_F32) && (up_dtype == SDMI_F16 || up_dtype == SDMI_F32) &&
+                     (down_dtype == SDMI_F16 || down_dtype == SDMI_F32),
+                 "sdmi_lora_merge: dtypes must be SDMI_F16 or SDMI_F32");
     return launch_lora_merge((float*)out, w, w_dtype, up, up_dtype, down, down_dtype, rows, cols, rank, scale, (hipStream_t)stream);
     API_GUARD_END
 }

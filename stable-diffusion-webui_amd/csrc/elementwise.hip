@@ -67,7 +67,12 @@ __global__ __launch_bounds__(256) void cfg_prepare_kernel(const float* x, const 
     const long n = (long)B * chw;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const int b = (int)(i / chw);
-        const float v = x[i] * (c_in ? c_in[b] : 1.0f);
+        float v = x[i] * (c_in ? c_in[b] : 1.0f);
+        // the fp32 product is a value of its own (torch: `input * c_in`, then `.to(dtype_unet)`): left to the compiler, the multiply and the
+        // cast become ONE v_fma_mixlo_f16 — the exact product rounded once to fp16, which differs from the twice-rounded value in
+        // about one element in 2^14 (the fp32 value sits on an fp16 tie that the exact product misses).  In the <float> instantiation
+        // there is no cast to keep apart and the pin emits nothing.
+        asm volatile("" : "+v"(v));
         const TO hv = (TO)v;
         for (int r = 0; r < reps; ++r) xin[(long)r * n + i] = hv;
     }
@@ -93,7 +98,8 @@ __global__ __launch_bounds__(256) void cfg_prepare_concat_kernel(const float* x,
         const int ch = (int)(rem / hw);
         const long px = rem - (long)ch * hw;
         const bool is_x = ch < C;
-        const float v = is_x ? x[((long)b * C + ch) * hw + px] * (c_in ? c_in[b] : 1.0f) : cond[((long)b * Cc + (ch - C)) * hw + px];
+        float v = is_x ? x[((long)b * C + ch) * hw + px] * (c_in ? c_in[b] : 1.0f) : cond[((long)b * Cc + (ch - C)) * hw + px];
+        asm volatile("" : "+v"(v));                  // (as in cfg_prepare_kernel: round the product to fp32 before the cast)
         for (int r = 0; r < reps; ++r) xin[(long)r * n + i] = (TO)((!is_x && ((zero_reps >> r) & 1u)) ? 0.0f : v);
     }
 }
@@ -188,8 +194,8 @@ int launch_euler_step(float* x, const float* den, const float* noise, float sigm
 __global__ __launch_bounds__(256) void dpmpp2m_step_kernel(float* x, const float* den, const float* old, float ratio, float em1,
                                                           float c1, float c2, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        float dd = den[i];
-        if (old) dd = c1 * dd - c2 * old[i];       // denoised_d = (1 + 1/(2r)) * denoised - (1/(2r)) * old_denoised
+        float dd = c1 * den[i];                    // (c1 counts without `old` too, as sdmi.h writes it; the host passes 1 there: exact)
+        if (old) dd = dd - c2 * old[i];            // denoised_d = (1 + 1/(2r)) * denoised - (1/(2r)) * old_denoised
         x[i] = ratio * x[i] - em1 * dd;            // x = (sigma_next/sigma) * x - expm1(-h) * denoised_d
     }
 }

@@ -4,8 +4,10 @@ The samplers keep every tensor on the device and launch fused HIP kernels for th
 checks without a GPU — is everything else: the step plans, the ancestral / SDE step sizes, the DPM-Solver and multistep coefficients that
 are folded into one `sdmi_lincomb` per update, the order in which noise is drawn, the callbacks.  For these tests only, the device launches
 are replaced by the same elementwise arithmetic in torch, taken from the C ABI's own contract (include/sdmi.h: sdmi_euler_step,
-sdmi_dpmpp2m_step, sdmi_ddim_step, sdmi_axpby, sdmi_lincomb, sdmi_dpm_error_partials); the kernels themselves are compared with the oracle
-on the GPU (tests/test_gpu_ops.py, tests/test_gpu_models.py).  Nothing here touches libsdmi.so's compute entry points.
+sdmi_dpmpp2m_step, sdmi_ddim_step, sdmi_axpby, sdmi_lincomb, sdmi_dpm_error_partials).  tests/test_gpu_abi.py closes the triangle on the
+GPU: each kernel, and `_TorchStepKernels` below on the same inputs, against a float64 evaluation of that contract under one elementwise
+bound (sdmi_lincomb: tests/test_gpu_ops.py; whole sampler runs: tests/test_gpu_models.py).  Nothing here touches libsdmi.so's compute
+entry points.
 """
 import importlib
 import math

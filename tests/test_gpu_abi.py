@@ -1,0 +1,731 @@
+"""GPU parity tests of the op-level C ABI (include/sdmi.h), one entry at a time, against float64 restatements of the formulas written there.
+
+1. The fp32 elementwise entries (sampler updates, CFG build / combine, LoRA / LyCORIS weight deltas).  Rule (`assert_ew`): `ref` is the float64
+   evaluation of the header's formula from the fp32 inputs and the fp32-rounded scalar arguments, `mag` the same formula with every term
+   replaced by its absolute value, and |got - ref| <= 16 * 2^-24 * mag elementwise — each kernel has fewer than ten roundings (a division or
+   a square root counted as three), a wrong term is an error of order mag.  Reductions get their own constant (lora_merge: rank + 3; DoRA:
+   32).  A copy, or one multiply followed by a cast, is asserted bit-equal.  Sizes 1 / 255 / 257 / 2^20 + 257: `ew_blocks` caps the grid at
+   4096 x 256 threads, so only the last size runs a kernel's stride loop a second time.  The torch stand-ins the CPU sampler / CFG tests
+   put in the kernels' place (test_cpu_host_samplers._TorchStepKernels, test_cpu_host_cfg.TorchCfgKernels) get the same inputs and must
+   meet the same bound against the same `ref`: kernel <-> contract <-> stand-in.
+2. sdmi_attention / _vt / _wide in the layouts the header documents: row strides wider than H*D, V^T handed in with non-zero padding columns,
+   the generic kernel (forced, and as the fallback for unaligned strides), the wide form across its 4096-row block boundary.
+3. sdmi_rowchain_ff at one, three and five 32-unit chunks of hidden width against float64, measured with the fp16-storage twin
+   (the rule of tests/test_gpu_esrgan.py).
+4. What the entries refuse on the host, before any launch.
+
+Every case also runs on the host-emulated library (tests/test_cpu_abi.py); the measured figures are in profiles/abi_ops_parity.md."""
+import importlib
+import math
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from helpers import rel_l2, seeded, worst_slice_rel_l2
+from test_cpu_host_cfg import TorchCfgKernels
+from test_cpu_host_samplers import _TorchStepKernels
+from test_gpu_ops import ATTN_FOLD_MIN_M_DEFAULT, ATTN_TAU_DEFAULT, _attn_ref, assert_attn_slices, h
+
+pytestmark = pytest.mark.gpu
+
+U = 2.0 ** -24
+BIG = (1 << 20) + 257                     # past ew_blocks' cap of 4096 blocks x 256 threads
+SIZES = [1, 255, 257, BIG]
+B_IMG, IMG = 3, (4, 9, 7)                 # chw = 252: image boundaries are not block boundaries
+IMG_BIG = (4, 297, 295)                   # 3 x 350460 = 2^20 + 2804 elements, 350460 % 256 = 252
+
+
+def sub(name):
+    return importlib.import_module("stable-diffusion-webui_amd." + name)
+
+
+@pytest.fixture(scope="module")
+def dev():
+    sub("_lib").require_device()
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture(scope="module")
+def abi(dev):
+    lib = sub("_lib")
+    return lib.lib, lib.check, lib.ptr, lib.stream_ptr
+
+
+def f32(v):
+    return float(np.float32(v))
+
+
+_ALIVE = []
+
+
+def up(t, dev):
+    """A device copy the kernel may write to (under the host emulation `.to` alone would hand back the reference's own storage), kept
+    alive until the test ends: `ptr(up(...))` hands the library a bare address."""
+    if t is None:
+        return None
+    _ALIVE.append(t.clone().to(dev))
+    return _ALIVE[-1]
+
+
+@pytest.fixture(autouse=True)
+def release_device_copies():
+    yield
+    torch.cuda.synchronize()
+    _ALIVE.clear()
+
+
+def assert_ew(got, ref, mag, what, const=16):
+    got = got.detach().cpu().double().reshape(ref.shape)
+    assert bool(torch.isfinite(got).all()), what
+    err = (got - ref).abs()
+    unit = U * mag
+    worst = float((err[unit > 0] / unit[unit > 0]).max()) if bool((unit > 0).any()) else 0.0
+    print(f"[abi elementwise] {what}: worst |got - ref| = {worst:.2f} x 2^-24 mag (cap {const})")
+    bad = err > const * unit
+    assert not bool(bad.any()), (what, "elements over the bound", int(bad.sum()), "first at", int(bad.flatten().nonzero()[0]), "worst multiple", worst)
+
+
+class Guarded:
+    """An output buffer between two runs of sentinel elements that the kernel must not touch."""
+
+    def __init__(self, shape, dtype, dev, pad=64, fill=-777.0):
+        n = math.prod(shape)
+        self.full = torch.full((n + 2 * pad,), fill, dtype=dtype, device=dev)
+        self.t = self.full[pad:pad + n].view(shape)
+        self.pad, self.fill = pad, fill
+
+    def intact(self):
+        f = self.full.cpu()
+        return bool((f[:self.pad] == self.fill).all()) and bool((f[-self.pad:] == self.fill).all())
+
+
+# ---- 1. sampler updates -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_noise", [False, True], ids=["plain", "noise"])
+@pytest.mark.parametrize("n", SIZES)
+def test_euler_step_vs_float64(dev, abi, n, with_noise):
+    L, check, ptr, sp = abi
+    x, den, noise = seeded((n,), 1, 5.0), seeded((n,), 2, 4.0), seeded((n,), 3)
+    sigma, sd, su, sn = f32(3.3), f32(1.7), f32(1.2), f32(1.003)
+    X, Dn, Nz = x.double(), den.double(), noise.double()
+    ref = X + (X - Dn) / sigma * (sd - sigma)
+    mag = X.abs() + (X.abs() + Dn.abs()) / abs(sigma) * (abs(sd) + abs(sigma))
+    if with_noise:
+        ref, mag = ref + Nz * sn * su, mag + (Nz * sn * su).abs()
+    g = Guarded((n,), torch.float32, dev)
+    g.t.copy_(x)
+    check(L.sdmi_euler_step(ptr(g.t), ptr(up(den, dev)), ptr(up(noise, dev)) if with_noise else None, sigma, sd, su, sn, n, sp()))
+    assert_ew(g.t, ref, mag, f"euler_step n {n} noise {with_noise}")
+    assert g.intact()
+    xs = x.clone()
+    _TorchStepKernels.sdmi_euler_step(xs, den, noise if with_noise else None, sigma, sd, su, sn, n, None)
+    assert_ew(xs, ref, mag, f"euler_step stand-in n {n} noise {with_noise}")
+
+
+@pytest.mark.parametrize("with_old", [False, True], ids=["first", "old"])
+@pytest.mark.parametrize("n", SIZES)
+def test_dpmpp2m_step_vs_float64(dev, abi, n, with_old):
+    L, check, ptr, sp = abi
+    x, den, old = seeded((n,), 4, 5.0), seeded((n,), 5, 4.0), seeded((n,), 6, 4.0)
+    ratio, em1, c1, c2 = f32(0.62), f32(-0.41), f32(1.83), f32(0.83)              # c1 != c2: swapping them is an error of order mag
+    X, Dn, Od = x.double(), den.double(), old.double()
+    ref, mag = c1 * Dn, abs(c1) * Dn.abs()                                      # sdmi.h: c1 scales den with or without `old`
+    if with_old:
+        ref, mag = ref - c2 * Od, mag + abs(c2) * Od.abs()
+    ref, mag = ratio * X - em1 * ref, abs(ratio) * X.abs() + abs(em1) * mag
+    g = Guarded((n,), torch.float32, dev)
+    g.t.copy_(x)
+    check(L.sdmi_dpmpp2m_step(ptr(g.t), ptr(up(den, dev)), ptr(up(old, dev)) if with_old else None, ratio, em1, c1, c2, n, sp()))
+    assert_ew(g.t, ref, mag, f"dpmpp2m_step n {n} old {with_old}")
+    assert g.intact()
+    xs = x.clone()
+    _TorchStepKernels.sdmi_dpmpp2m_step(xs, den, old if with_old else None, ratio, em1, c1, c2, n, None)
+    assert_ew(xs, ref, mag, f"dpmpp2m_step stand-in n {n} old {with_old}")
+
+
+@pytest.mark.parametrize("with_pred", [False, True], ids=["nopred", "pred"])
+@pytest.mark.parametrize("with_noise", [False, True], ids=["plain", "noise"])
+@pytest.mark.parametrize("n", SIZES)
+def test_ddim_step_vs_float64(dev, abi, n, with_noise, with_pred):
+    L, check, ptr, sp = abi
+    x, e, noise = seeded((n,), 7, 2.0), seeded((n,), 8), seeded((n,), 9)
+    a_t, a_prev, sig = f32(0.45), f32(0.6), f32(0.3)                               # 1 - a_prev - sig^2 = 0.31 > 0
+    somat = f32(math.sqrt(1 - a_t))
+    X, E, Nz = x.double(), e.double(), noise.double()
+    pred = (X - somat * E) / math.sqrt(a_t)
+    pmag = (X.abs() + abs(somat) * E.abs()) / math.sqrt(a_t)
+    ref = math.sqrt(a_prev) * pred + math.sqrt(1.0 - a_prev - sig * sig) * E
+    mag = math.sqrt(a_prev) * pmag + math.sqrt(1.0 + a_prev + sig * sig) * E.abs()
+    if with_noise:
+        ref, mag = ref + sig * Nz, mag + abs(sig) * Nz.abs()
+    g = Guarded((n,), torch.float32, dev)
+    g.t.copy_(x)
+    gp = Guarded((n,), torch.float32, dev)
+    check(L.sdmi_ddim_step(ptr(g.t), ptr(up(e, dev)), ptr(up(noise, dev)) if with_noise else None, ptr(gp.t) if with_pred else None,
+                           a_t, a_prev, sig, somat, n, sp()))
+    assert_ew(g.t, ref, mag, f"ddim_step x n {n} noise {with_noise} pred {with_pred}")
+    assert g.intact() and gp.intact()
+    if with_pred:
+        assert_ew(gp.t, pred, pmag, f"ddim_step pred_x0 n {n} noise {with_noise}")
+    else:
+        assert bool((gp.t.cpu() == gp.fill).all())
+    xs, ps = x.clone(), torch.zeros(n)
+    _TorchStepKernels.sdmi_ddim_step(xs, e, noise if with_noise else None, ps if with_pred else None, a_t, a_prev, sig, somat, n, None)
+    assert_ew(xs, ref, mag, f"ddim_step stand-in x n {n} noise {with_noise} pred {with_pred}")
+    if with_pred:
+        assert_ew(ps, pred, pmag, f"ddim_step stand-in pred_x0 n {n}")
+
+
+@pytest.mark.parametrize("form", ["z_null", "z", "in_place"])
+@pytest.mark.parametrize("n", SIZES)
+def test_axpby_vs_float64(dev, abi, n, form):
+    L, check, ptr, sp = abi
+    x, z = seeded((n,), 10, 3.0), seeded((n,), 11, 2.0)
+    a, b = f32(14.6), f32(-0.37)
+    ref = a * x.double() + (b * z.double() if form != "z_null" else 0.0)
+    mag = abs(a) * x.double().abs() + (abs(b) * z.double().abs() if form != "z_null" else 0.0)
+    if form == "in_place":
+        g = Guarded((n,), torch.float32, dev)
+        g.t.copy_(x)
+        check(L.sdmi_axpby(ptr(g.t), ptr(g.t), a, ptr(up(z, dev)), b, n, sp()))
+    else:
+        g = Guarded((n,), torch.float32, dev)
+        check(L.sdmi_axpby(ptr(g.t), ptr(up(x, dev)), a, ptr(up(z, dev)) if form == "z" else None, b, n, sp()))
+    assert_ew(g.t, ref, mag, f"axpby n {n} {form}")
+    assert g.intact()
+    if form == "z_null":
+        assert torch.equal(g.t.cpu(), x * torch.tensor(a))                                     # one fp32 multiply
+    ys = x.clone() if form == "in_place" else torch.empty(n)
+    _TorchStepKernels.sdmi_axpby(ys, ys if form == "in_place" else x, a, None if form == "z_null" else z, b, n, None)
+    assert_ew(ys, ref, mag, f"axpby stand-in n {n} {form}")
+
+
+@pytest.mark.parametrize("n", [300, 5000, BIG])
+def test_dpm_error_partials_vs_float64(dev, abi, n):
+    L, check, ptr, sp = abi
+    lo, prev = seeded((n,), 12, 2.0), seeded((n,), 13, 2.0)
+    hi = lo + 0.02 * seeded((n,), 14)
+    atol, rtol = f32(0.0078), f32(0.05)
+    delta = torch.maximum(torch.full((n,), atol, dtype=torch.float64), rtol * torch.maximum(lo.double().abs(), prev.double().abs()))
+    ref = float((((lo.double() - hi.double()) / delta) ** 2).sum())
+    lod, hid, pvd = up(lo, dev), up(hi, dev), up(prev, dev)
+    parts = []
+    for _ in range(2):
+        g = Guarded((256,), torch.float32, dev)
+        g.t.fill_(float("nan"))
+        check(L.sdmi_dpm_error_partials(ptr(lod), ptr(hid), ptr(pvd), atol, rtol, ptr(g.t), n, sp()))
+        assert g.intact()
+        parts.append(g.t.cpu().clone())
+    assert bool(torch.isfinite(parts[0]).all())
+    got = float(parts[0].double().sum())
+    print(f"[abi elementwise] dpm_error_partials n {n}: sum of partials {got:.9e}, float64 {ref:.9e}, relative {abs(got - ref) / ref:.2e} (cap 1e-5)")
+    assert abs(got - ref) <= 1e-5 * ref
+    assert torch.equal(parts[0].view(torch.int32), parts[1].view(torch.int32))
+    ps = torch.full((256,), float("nan"))
+    _TorchStepKernels.sdmi_dpm_error_partials(lo, hi, prev, atol, rtol, ps, n, None)
+    assert bool(torch.isfinite(ps).all()) and abs(float(ps.double().sum()) - ref) <= 1e-5 * ref
+
+
+# ---- 1. CFG build / combine ---------------------------------------------------------------------------------------------------------------
+def cfg_inputs(img, seed):
+    x = seeded((B_IMG,) + img, seed, 5.0)
+    eps = seeded((2 * B_IMG,) + img, seed + 1)
+    mask = (seeded((B_IMG,) + img, seed + 2) > 0).float() * 0.75 + 0.125                      # not 0 / 1: both blend terms count
+    init = seeded((B_IMG,) + img, seed + 3, 3.0)
+    c_out = torch.tensor([-3.3, -1.9, -0.7])
+    c_skip = torch.tensor([0.084, 0.217, 0.671])
+    return x, eps, mask, 1.0 - mask, init, c_out, c_skip
+
+
+def per_image(c):
+    return c.double().view(B_IMG, 1, 1, 1)
+
+
+def blend64(ref, mag, use_mask, mask, nmask, init):
+    if not use_mask:
+        return ref, mag
+    return ref * nmask.double() + init.double() * mask.double(), mag * nmask.double().abs() + (init.double() * mask.double()).abs()
+
+
+COMBINE_CASES = [(IMG, 0, False), (IMG, 0, True), (IMG, 1, False), (IMG, 1, True), (IMG_BIG, 0, True), (IMG_BIG, 1, False)]
+
+
+@pytest.mark.parametrize("img,mode,use_mask", COMBINE_CASES, ids=[f"{'x'.join(map(str, c[0]))}-mode{c[1]}-{'mask' if c[2] else 'nomask'}" for c in COMBINE_CASES])
+def test_cfg_combine_vs_float64(dev, abi, img, mode, use_mask):
+    L, check, ptr, sp = abi
+    x, eps, mask, nmask, init, c_out, _ = cfg_inputs(img, 20)
+    scale = f32(7.5)
+    chw = math.prod(img)
+    X, Ec, Eu, co = x.double(), eps[:B_IMG].double(), eps[B_IMG:].double(), per_image(c_out)
+    if mode == 0:
+        dc, du = X + Ec * co, X + Eu * co
+        mdc, mdu = X.abs() + (Ec * co).abs(), X.abs() + (Eu * co).abs()
+    else:
+        dc, du, mdc, mdu = Ec, Eu, Ec.abs(), Eu.abs()
+    ref, mag = blend64(du + (dc - du) * scale, mdu + (mdc + mdu) * abs(scale), use_mask, mask, nmask, init)
+    g = Guarded((B_IMG,) + img, torch.float32, dev)
+    m = [ptr(up(t, dev)) for t in (mask, nmask, init)] if use_mask else [None, None, None]
+    xd, cod = (up(x, dev), up(c_out, dev)) if mode == 0 else (None, None)              # mode 1 reads neither
+    check(L.sdmi_cfg_combine(ptr(xd), ptr(up(eps, dev)), ptr(cod), scale, mode, m[0], m[1], m[2], ptr(g.t), B_IMG, chw, sp()))
+    assert_ew(g.t, ref, mag, f"cfg_combine {img} mode {mode} mask {use_mask}")
+    assert g.intact()
+    den = torch.empty((B_IMG,) + img)
+    TorchCfgKernels.sdmi_cfg_combine(x, eps, c_out, scale, mode, *((mask, nmask, init) if use_mask else (None, None, None)), den, B_IMG, chw, None)
+    assert_ew(den, ref, mag, f"cfg_combine stand-in {img} mode {mode} mask {use_mask}")
+
+
+@pytest.mark.parametrize("img,use_mask", [(IMG, False), (IMG, True), (IMG_BIG, True)], ids=["4x9x7-nomask", "4x9x7-mask", "4x297x295-mask"])
+def test_cfg_combine_affine_vs_float64(dev, abi, img, use_mask):
+    L, check, ptr, sp = abi
+    x, out, mask, nmask, init, c_out, c_skip = cfg_inputs(img, 30)
+    scale = f32(7.5)
+    chw = math.prod(img)
+    X, Oc, Ou, co, cs = x.double(), out[:B_IMG].double(), out[B_IMG:].double(), per_image(c_out), per_image(c_skip)
+    dc, du = Oc * co + X * cs, Ou * co + X * cs
+    mdc, mdu = (Oc * co).abs() + (X * cs).abs(), (Ou * co).abs() + (X * cs).abs()
+    ref, mag = blend64(du + (dc - du) * scale, mdu + (mdc + mdu) * abs(scale), use_mask, mask, nmask, init)
+    g = Guarded((B_IMG,) + img, torch.float32, dev)
+    m = [ptr(up(t, dev)) for t in (mask, nmask, init)] if use_mask else [None, None, None]
+    check(L.sdmi_cfg_combine_affine(ptr(up(x, dev)), ptr(up(out, dev)), ptr(up(c_out, dev)), ptr(up(c_skip, dev)), scale, m[0], m[1], m[2],
+                                    ptr(g.t), B_IMG, chw, sp()))
+    assert_ew(g.t, ref, mag, f"cfg_combine_affine {img} mask {use_mask}")
+    assert g.intact()
+    den = torch.empty((B_IMG,) + img)
+    TorchCfgKernels.sdmi_cfg_combine_affine(x, out, c_out, c_skip, scale, *((mask, nmask, init) if use_mask else (None, None, None)), den, B_IMG, chw, None)
+    assert_ew(den, ref, mag, f"cfg_combine_affine stand-in {img} mask {use_mask}")
+
+
+PREPARE_CASES = [(IMG, dt, ci, reps) for dt in (torch.float16, torch.float32) for ci in (False, True) for reps in (1, 3)] + [(IMG_BIG, torch.float16, True, 2)]
+
+
+@pytest.mark.parametrize("img,dtype,with_c_in,reps", PREPARE_CASES,
+                         ids=[f"{'x'.join(map(str, c[0]))}-{str(c[1]).split('.')[1]}-{'c_in' if c[2] else 'null'}-reps{c[3]}" for c in PREPARE_CASES])
+def test_cfg_prepare_input_is_one_multiply_and_a_cast(dev, abi, img, dtype, with_c_in, reps):
+    L, check, ptr, sp = abi
+    lib = sub("_lib")
+    x = seeded((B_IMG,) + img, 40, 5.0)
+    c_in = torch.tensor([0.29, 0.083, 0.71])
+    want = ((x * c_in.view(B_IMG, 1, 1, 1)) if with_c_in else x).to(dtype).repeat(reps, 1, 1, 1)
+    g = Guarded((reps * B_IMG,) + img, dtype, dev)
+    check(L.sdmi_cfg_prepare_input(ptr(up(x, dev)), ptr(up(c_in, dev)) if with_c_in else None, ptr(g.t), lib.dtype_code(g.t), B_IMG, reps,
+                                   math.prod(img), sp()))
+    assert torch.equal(g.t.cpu(), want) and g.intact()
+    dst = torch.empty((reps * B_IMG,) + img, dtype=dtype)
+    TorchCfgKernels.sdmi_cfg_prepare_input(x, c_in if with_c_in else None, dst, lib.dtype_code(dst), B_IMG, reps, math.prod(img), None)
+    assert torch.equal(dst, want)
+
+
+@pytest.mark.parametrize("hh,ww,dtype", [(7, 9, torch.float16), (7, 9, torch.float32), (132, 295, torch.float16)],
+                         ids=["7x9-float16", "7x9-float32", "132x295-float16"])
+def test_cfg_prepare_concat_layout(dev, abi, hh, ww, dtype):
+    """hw = 63, and 3 x 9 x 38940 = 2^20 + 2804 elements per repetition (the stride loop; enough products for the rounding of the cast to show)."""
+    L, check, ptr, sp = abi
+    lib = sub("_lib")
+    c, cc, hw, reps, zero_reps = 4, 5, hh * ww, 3, 0b010
+    x, cond = seeded((B_IMG, c, hh, ww), 41, 5.0), seeded((B_IMG, cc, hh, ww), 42, 2.0)
+    c_in = torch.tensor([0.29, 0.083, 0.71])
+    want = torch.empty((reps * B_IMG, c + cc, hh, ww), dtype=dtype)
+    for r in range(reps):
+        for b in range(B_IMG):
+            want[r * B_IMG + b, :c] = (x[b] * c_in[b]).to(dtype)
+            want[r * B_IMG + b, c:] = 0 if (zero_reps >> r) & 1 else cond[b].to(dtype)
+    assert bool((want[B_IMG:2 * B_IMG, c:] == 0).all()) and bool((want[:B_IMG, c:] != 0).any())
+    g = Guarded(tuple(want.shape), dtype, dev)
+    check(L.sdmi_cfg_prepare_concat(ptr(up(x, dev)), ptr(up(c_in, dev)), ptr(up(cond, dev)), ptr(g.t), lib.dtype_code(g.t), B_IMG, reps, c, cc, hw,
+                                    zero_reps, sp()))
+    assert torch.equal(g.t.cpu(), want) and g.intact()
+    dst = torch.full(tuple(want.shape), 9.0, dtype=dtype)
+    TorchCfgKernels.sdmi_cfg_prepare_concat(x, c_in, cond, dst, lib.dtype_code(dst), B_IMG, reps, c, cc, hw, zero_reps, None)
+    assert torch.equal(dst, want)
+
+
+# ---- 1. LoRA / LyCORIS weight deltas ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", SIZES)
+def test_weight_hadamard_vs_float64(dev, abi, n):
+    L, check, ptr, sp = abi
+    w, a, b = seeded((n,), 50), seeded((n,), 51), seeded((n,), 52)
+    scale = f32(0.37)
+    ref = w.double() + scale * (a.double() * b.double())
+    mag = w.double().abs() + abs(scale) * (a.double() * b.double()).abs()
+    g = Guarded((n,), torch.float32, dev)
+    check(L.sdmi_weight_hadamard(ptr(g.t), ptr(up(w, dev)), ptr(up(a, dev)), ptr(up(b, dev)), scale, n, sp()))
+    assert_ew(g.t, ref, mag, f"weight_hadamard n {n}")
+    assert g.intact()
+
+
+@pytest.mark.parametrize("k", [9, 1])
+def test_weight_kron_vs_numpy_kron_per_tap(dev, abi, k):
+    L, check, ptr, sp = abi
+    r1, c1, r2, c2 = 3, 5, 4, 2
+    w, w1, w2 = seeded((r1 * r2, c1 * c2, k), 53), seeded((r1, c1), 54), seeded((r2, c2, k), 55)
+    scale = f32(-0.61)
+    kron = np.stack([np.kron(w1.double().numpy(), w2[:, :, t].double().numpy()) for t in range(k)], axis=-1)
+    ref = w.double() + scale * torch.from_numpy(kron)
+    mag = w.double().abs() + abs(scale) * torch.from_numpy(np.abs(kron))
+    g = Guarded(tuple(w.shape), torch.float32, dev)
+    check(L.sdmi_weight_kron(ptr(g.t), ptr(up(w, dev)), ptr(up(w1, dev)), ptr(up(w2, dev)), r1, c1, r2, c2, k, scale, sp()))
+    assert_ew(g.t, ref, mag, f"weight_kron taps {k}")
+    assert g.intact()
+
+
+@pytest.mark.parametrize("on_input", [0, 1])
+def test_weight_ia3_vs_float64(dev, abi, on_input):
+    L, check, ptr, sp = abi
+    rows, cols = 6, 10
+    w, v = seeded((rows, cols), 56), seeded((cols if on_input else rows,), 57)
+    scale = f32(0.8)
+    vb = v.double().view(1, cols) if on_input else v.double().view(rows, 1)
+    ref = w.double() + scale * (w.double() * vb)
+    mag = w.double().abs() + abs(scale) * (w.double() * vb).abs()
+    g = Guarded((rows, cols), torch.float32, dev)
+    check(L.sdmi_weight_ia3(ptr(g.t), ptr(up(w, dev)), ptr(up(v, dev)), rows, cols, on_input, scale, sp()))
+    assert_ew(g.t, ref, mag, f"weight_ia3 on_input {on_input}")
+    assert g.intact()
+
+
+@pytest.mark.parametrize("rows,cin,k", [(70, 5, 9), (12, 5, 1)])
+def test_weight_dora_vs_float64(dev, abi, rows, cin, k):
+    """630 elements per input channel: a workgroup's 256 threads loop; 12: most threads idle.  The bound's constant is 32: the norm is a sum
+    of up to three sequential and eight tree additions of squares (non-negative: its relative error is at most the number of roundings,
+    halved by the square root), then a division, a multiply and two subtractions."""
+    L, check, ptr, sp = abi
+    w, delta, ds = seeded((rows, cin, k), 58), seeded((rows, cin, k), 59, 0.3), seeded((cin,), 60).abs() + 0.5
+    mult = f32(0.7)
+    W, Dl = w.double(), delta.double()
+    merged = W + Dl
+    norm = merged.pow(2).sum(dim=(0, 2), keepdim=True).sqrt()
+    dsb = ds.double().view(1, cin, 1)
+    ref = W + mult * (merged * dsb / norm - W)
+    mag = W.abs() + abs(mult) * ((W.abs() + Dl.abs()) * dsb.abs() / norm + W.abs())
+    g = Guarded((rows, cin, k), torch.float32, dev)
+    check(L.sdmi_weight_dora(ptr(g.t), ptr(up(w, dev)), ptr(up(delta, dev)), ptr(up(ds, dev)), rows, cin, k, mult, sp()))
+    assert_ew(g.t, ref, mag, f"weight_dora {rows}x{cin}x{k}", const=32)
+    assert g.intact()
+
+
+LORA_DTYPES = [(a, b, c) for a in (torch.float16, torch.float32) for b in (torch.float16, torch.float32) for c in (torch.float16, torch.float32)]
+LORA_CASES = [(24, 40, 6) + d for d in LORA_DTYPES] + [(1025, 1024, 4, torch.float16, torch.float32, torch.float16)]
+
+
+@pytest.mark.parametrize("rows,cols,rank,wt,ut,dt", LORA_CASES,
+                         ids=[f"{c[0]}x{c[1]}r{c[2]}-" + "".join("h" if t == torch.float16 else "f" for t in c[3:]) for c in LORA_CASES])
+def test_lora_merge_vs_float64(dev, abi, rows, cols, rank, wt, ut, dt):
+    L, check, ptr, sp = abi
+    lib = sub("_lib")
+    w, u, d = seeded((rows, cols), 61).to(wt), seeded((rows, rank), 62).to(ut), seeded((rank, cols), 63).to(dt)
+    scale = f32(0.4)
+    ref = w.double() + scale * (u.double() @ d.double())
+    mag = w.double().abs() + abs(scale) * (u.double().abs() @ d.double().abs())
+    g = Guarded((rows, cols), torch.float32, dev)
+    check(L.sdmi_lora_merge(ptr(g.t), ptr(up(w, dev)), lib.dtype_code(w), ptr(up(u, dev)), lib.dtype_code(u), ptr(up(d, dev)), lib.dtype_code(d),
+                            rows, cols, rank, scale, sp()))
+    assert_ew(g.t, ref, mag, f"lora_merge {rows}x{cols} rank {rank} {wt} {ut} {dt}", const=rank + 3)
+    assert g.intact()
+
+
+@pytest.mark.parametrize("case", ["384_columns", "lerp_branch"])
+def test_slerp_vs_oracle(dev, case):
+    from oracle import rng as orng
+    rng = sub("rng")
+    if case == "384_columns":                                   # C * W = 384 > the workgroup's 256 threads: the column loops run twice
+        low, high = seeded((4, 12, 96), 64), seeded((4, 12, 96), 65)
+    else:                                                       # mean cosine above 0.9995: the (reversed-weight) linear blend
+        low = seeded((4, 8, 8), 66)
+        high = low + 0.01 * seeded((4, 8, 8), 67)
+    want = orng.slerp(0.3, low, high)
+    if case == "lerp_branch":
+        assert torch.equal(want, low * 0.3 + high * (1 - 0.3))
+    got = rng.slerp(0.3, up(low, dev), up(high, dev)).cpu()
+    print(f"[abi elementwise] slerp {case}: largest |got - oracle| = {float((got - want).abs().max()):.2e} (atol 3e-6)")
+    np.testing.assert_allclose(got.numpy(), want.numpy(), rtol=0, atol=3e-6)
+
+
+# ---- 2. attention ------------------------------------------------------------------------------------------------------------------------
+def ref64(q, k, v, heads):
+    return _attn_ref(h(q).double(), h(k).double(), h(v).double(), heads)
+
+
+def attn_direct(abi, q, k, v, out, heads, d, ws_tail=0):
+    """sdmi_attention on (possibly strided) views [B, N|M, H*D] of wider buffers."""
+    L, check, ptr, sp = abi
+    b, n, m = q.shape[0], q.shape[1], k.shape[1]
+    for t in (q, k, v, out):
+        assert t.stride(2) == 1 and t.stride(0) == t.shape[1] * t.stride(1) and t.data_ptr() % 16 == 0
+    nbytes = int(L.sdmi_attention_workspace_bytes(b, heads, m, d))
+    ws = torch.full((nbytes + ws_tail,), 0x5A, dtype=torch.uint8, device=q.device)
+    check(L.sdmi_attention(ptr(q), ptr(k), ptr(v), ptr(out), b, heads, n, m, d, q.stride(1), k.stride(1), v.stride(1), out.stride(1),
+                           float(d ** -0.5), ptr(ws), nbytes, sp()), "sdmi_attention")
+    torch.cuda.synchronize()
+    assert bool((ws[nbytes:].cpu() == 0x5A).all()), "the workspace's tail was written"
+
+
+@pytest.mark.parametrize("d,heads", [(40, 2), (64, 3), (80, 2), (160, 1)])
+def test_attention_reads_and_writes_strided_rows(dev, abi, d, heads):
+    ops = sub("ops")
+    b, n, c = 2, 130, heads * d
+    qkv = seeded((b, n, 3 * c), 70).half()
+    buf = qkv.clone().to(dev)
+    q, k, v = buf[:, :, :c], buf[:, :, c:2 * c], buf[:, :, 2 * c:]
+    obuf = torch.full((b, n, c + 64), 123.0, dtype=torch.float16, device=dev)
+    attn_direct(abi, q, k, v, obuf[:, :, 32:32 + c], heads, d, ws_tail=4096)
+    got = obuf.cpu()
+    assert bool((got[:, :, :32] == 123.0).all()) and bool((got[:, :, 32 + c:] == 123.0).all())
+    got = got[:, :, 32:32 + c].contiguous()
+    flat = ops.attention(q.contiguous(), k.contiguous(), v.contiguous(), heads).cpu()
+    assert torch.equal(got.view(torch.int16), flat.view(torch.int16))
+    ref = ref64(qkv[:, :, :c], qkv[:, :, c:2 * c], qkv[:, :, 2 * c:], heads)
+    e = rel_l2(got, ref)
+    print(f"[abi attention] strided rows d {d} heads {heads} N = M = {n}: {e:.3e} (cap 5e-4)")
+    assert e < 5e-4
+    assert_attn_slices(got.double(), ref, heads, 5e-4, ("strided", d, heads))
+
+
+def vt_of(v, heads, m, dev, extra=64, pad_value=1000.0):
+    """[B, M, H*D] -> V^T [B, H*D, Mpad + extra] with every padding column at pad_value."""
+    b, _, c = v.shape
+    mpad = (m + 63) // 64 * 64
+    vt = torch.full((b, c, mpad + extra), pad_value, dtype=torch.float16)
+    vt[:, :, :m] = v.half().transpose(1, 2)
+    return vt.to(dev)
+
+
+@pytest.mark.parametrize("d,heads,n,m", [(40, 2, 200, 77), (64, 2, 130, 130), (160, 1, 70, 77)])
+def test_attention_vt_ignores_its_padding_columns(dev, d, heads, n, m):
+    ops = sub("ops")
+    q, k, v = seeded((2, n, heads * d), 71).half(), seeded((2, m, heads * d), 72).half(), seeded((2, m, heads * d), 73).half()
+    got = ops.attention_vt(up(q, dev), up(k, dev), vt_of(v, heads, m, dev), heads, m)
+    want = ops.attention(up(q, dev), up(k, dev), up(v, dev), heads)
+    torch.cuda.synchronize()
+    assert torch.equal(got.cpu().view(torch.int16), want.cpu().view(torch.int16))
+    e = rel_l2(got.float().cpu(), ref64(q, k, v, heads))
+    print(f"[abi attention] V^T direct d {d} heads {heads} N {n} M {m}: {e:.3e}")
+    assert e < 5e-4
+
+
+@pytest.mark.parametrize("form", [17, 20])
+def test_attention_vt_padding_in_the_d40_forms(dev, form):
+    """The folded-shift form (17) and the 8-wave role-offset form (20) at N = 384, M = 290 (five key tiles, the last ragged)."""
+    ops, lib = sub("ops"), sub("_lib")
+    d, heads, n, m = 40, 1, 384, 290
+    q, k, v = seeded((2, n, d), 74).half(), seeded((2, m, d), 75).half(), seeded((2, m, d), 76).half()
+    lib.check(lib.lib.sdmi_debug_set(b"attn_occ", form))
+    lib.check(lib.lib.sdmi_debug_set(b"attn_tau", 0))
+    lib.check(lib.lib.sdmi_debug_set(b"attn_fold_min_m", 0))
+    try:
+        got = ops.attention_vt(up(q, dev), up(k, dev), vt_of(v, heads, m, dev), heads, m)
+        want = ops.attention(up(q, dev), up(k, dev), up(v, dev), heads)
+        torch.cuda.synchronize()
+    finally:
+        lib.check(lib.lib.sdmi_debug_set(b"attn_occ", 15))
+        lib.check(lib.lib.sdmi_debug_set(b"attn_tau", ATTN_TAU_DEFAULT))
+        lib.check(lib.lib.sdmi_debug_set(b"attn_fold_min_m", ATTN_FOLD_MIN_M_DEFAULT))
+    assert torch.equal(got.cpu().view(torch.int16), want.cpu().view(torch.int16))
+    e = rel_l2(got.float().cpu(), ref64(q, k, v, heads))
+    print(f"[abi attention] V^T direct form {form} N {n} M {m}: {e:.3e}")
+    assert e < 5e-4
+
+
+GENERIC_CAP = 1.5e-3                      # the generic case of test_gpu_ops.test_attention_vs_oracle
+
+
+@pytest.mark.parametrize("d,heads,n,m", [(40, 2, 70, 77), (64, 1, 33, 200)])
+def test_attention_generic_kernel_forced(dev, d, heads, n, m):
+    ops = sub("ops")
+    q, k, v = seeded((2, n, heads * d), 77).half(), seeded((2, m, heads * d), 78).half(), seeded((2, m, heads * d), 79).half()
+    got = ops.attention_vt(up(q, dev), up(k, dev), vt_of(v, heads, m, dev), heads, m, force_generic=True).float().cpu()
+    mfma = ops.attention(up(q, dev), up(k, dev), up(v, dev), heads).float().cpu()
+    ref = ref64(q, k, v, heads)
+    e, e2 = rel_l2(got, ref), rel_l2(got, mfma)
+    print(f"[abi attention] generic forced d {d} heads {heads} N {n} M {m}: {e:.3e} from float64 (cap {GENERIC_CAP}), {e2:.3e} from the MFMA kernel")
+    assert e < GENERIC_CAP and e2 < 2 * GENERIC_CAP
+    assert_attn_slices(got.double(), ref, heads, GENERIC_CAP, ("generic", d, heads))
+
+
+def test_attention_falls_back_to_the_generic_kernel_on_unaligned_strides(dev, abi):
+    """ldq = ldk = ldo = H*D + 4 (not a multiple of 8 elements): the launcher takes the generic kernel, whose bits a forced run gives."""
+    ops = sub("ops")
+    d, heads, n, m = 40, 2, 70, 77
+    c = heads * d
+    q, k, v = seeded((2, n, c), 80).half(), seeded((2, m, c), 81).half(), seeded((2, m, c), 82).half()
+    qb, kb = torch.full((2, n, c + 4), 50.0, dtype=torch.float16), torch.full((2, m, c + 4), 50.0, dtype=torch.float16)
+    qb[:, :, :c], kb[:, :, :c] = q, k
+    qb, kb = qb.to(dev), kb.to(dev)
+    obuf = torch.full((2, n, c + 4), 123.0, dtype=torch.float16, device=dev)
+    attn_direct(abi, qb[:, :, :c], kb[:, :, :c], up(v, dev), obuf[:, :, :c], heads, d)
+    got = obuf.cpu()
+    assert bool((got[:, :, c:] == 123.0).all())
+    got = got[:, :, :c].contiguous()
+    forced = ops.attention_vt(up(q, dev), up(k, dev), vt_of(v, heads, m, dev, extra=0, pad_value=0.0), heads, m, force_generic=True).cpu()
+    mfma = ops.attention(up(q, dev), up(k, dev), up(v, dev), heads).float().cpu()
+    assert torch.equal(got.view(torch.int16), forced.view(torch.int16))
+    ref = ref64(q, k, v, heads)
+    e, e2 = rel_l2(got, ref), rel_l2(got.float(), mfma)
+    print(f"[abi attention] generic fallback, strides H*D + 4: {e:.3e} from float64 (cap {GENERIC_CAP}), {e2:.3e} from the MFMA kernel")
+    assert e < GENERIC_CAP and e2 < 2 * GENERIC_CAP
+    assert_attn_slices(got.double(), ref, heads, GENERIC_CAP, "generic fallback")
+
+
+def wide_case(dev, n=4096 + 72, m=72, d=64, ld=None):
+    ld = ld or d + 8
+    q, k, v = seeded((2, n, d), 83).half(), seeded((2, m, d), 84).half(), seeded((2, m, d), 85).half()
+    bufs = []
+    for t in (q, k, v):
+        w = torch.full((2, t.shape[1], ld), 50.0, dtype=torch.float16)
+        w[:, :, :d] = t
+        bufs.append(w.to(dev))
+    out = torch.full((2, n, ld), 123.0, dtype=torch.float16, device=dev)
+    return q, k, v, bufs, out
+
+
+def test_attention_wide_across_its_row_block_boundary(dev, abi):
+    """N = 4096 + 72: the second block of query rows is 72 rows long and starts at row 4096 of each image; every row stride is D + 8."""
+    L, check, ptr, sp = abi
+    n, m, d, ld = 4096 + 72, 72, 64, 72
+    q, k, v, (qb, kb, vb), out = wide_case(dev)
+    nbytes = int(L.sdmi_attention_wide_workspace_bytes(2, n, m, d))
+    ws = torch.full((nbytes + 4096,), 0x5A, dtype=torch.uint8, device=dev)
+    check(L.sdmi_attention_wide(ptr(qb), ptr(kb), ptr(vb), ptr(out), 2, n, m, d, ld, ld, ld, ld, float(d ** -0.5), ptr(ws), nbytes, sp()))
+    torch.cuda.synchronize()
+    assert bool((ws[nbytes:].cpu() == 0x5A).all())
+    got = out.cpu()
+    assert bool((got[:, :, d:] == 123.0).all())
+    got = got[:, :, :d].contiguous()
+    ref = ref64(q, k, v, 1)
+    e = rel_l2(got, ref)
+    worst, idx = worst_slice_rel_l2(got, ref, (0, 1))
+    print(f"[abi attention] wide N {n} M {m} D {d}, strides {ld}: {e:.3e} (cap 1e-3), worst query row {worst:.3e} at {idx} (cap 2e-3)")
+    assert e < 1e-3
+    assert_attn_slices(got.double(), ref, 1, 1e-3, "wide")
+
+
+def test_attention_wide_refusals(dev, abi):
+    L, check, ptr, sp = abi
+    lib = sub("_lib")
+    n, m, d, ld = 128, 72, 64, 72
+    q, k, v, (qb, kb, vb), out = wide_case(dev, n=n)
+    nbytes = int(L.sdmi_attention_wide_workspace_bytes(2, n, m, 96))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    def call(d_, ldq, bytes_):
+        return L.sdmi_attention_wide(ptr(qb), ptr(kb), ptr(vb), ptr(out), 2, n, m, d_, ldq, ld, ld, ld, 0.125, ptr(ws), bytes_, sp())
+    assert call(96, 104, nbytes) != 0 and "multiple of 64" in lib.last_error()
+    assert call(d, d + 4, nbytes) != 0 and "multiples of 8" in lib.last_error()
+    assert call(d, ld, int(L.sdmi_attention_wide_workspace_bytes(2, n, m, d)) - 1) != 0 and "workspace too small" in lib.last_error()
+    torch.cuda.synchronize()
+    assert bool((out.cpu() == 123.0).all())                      # nothing ran
+
+
+# ---- 3. the fused feed-forward chain -----------------------------------------------------------------------------------------------------
+def r16d(t):
+    return t.half().double()
+
+
+@pytest.mark.parametrize("biases", [True, False], ids=["b1b2", "nobias"])
+@pytest.mark.parametrize("rows", [128, 384])
+@pytest.mark.parametrize("hidden", [32, 96, 160])
+def test_rowchain_ff_at_every_chunk_parity_vs_float64(dev, hidden, rows, biases):
+    """1, 3 and 5 chunks of 32 hidden units (the chunk loop alternates two score sets and peels its ends), one and three 128-row
+    workgroups.  Reference: the float64 graph on the fp16 operands; yardstick: the same graph with the LayerNorm output, the hidden tensor
+    and the output rounded to binary16 (what a kernel storing fp16 must do).  Measured figures: profiles/abi_ops_parity.md.
+
+    x is drawn at 1/8 of unit scale (LayerNorm takes the scale out of the branch).  The stored sum x + branch is rounded to fp16, an
+    absolute error set by |out|; on `out - x` it is divided by the row's branch norm, and with 32 hidden units the GEGLU product leaves
+    some rows at a quarter of the mean norm.  At unit scale |out| ~ |x| in every row and the fp16-storage TWIN itself has rows of
+    `out - x` at 2.7 x its own global distance (hidden 32, no biases: 1.41e-3 against 5.26e-4; the engine 1.40e-3 on the same row), over the
+    per-row cap of 2.5 x that this test applies: no kernel that stores fp16 can meet a per-row cap stated against the global yardstick on
+    such inputs.  With the branch dominating the sum the rounding follows the row's own size.  That the inputs are fit for the rule is
+    asserted on the twin, which knows nothing of the kernel.  The thinnest margin (hidden 32, no biases, 128 rows: the twin's worst row at
+    2.35 x of the 2.5 x cap) belongs to this seed's draw: if a reseed or another shape trips "inputs unfit", that is a property of the
+    inputs and not of any kernel — draw other inputs, and leave the caps where they are."""
+    ops = sub("ops")
+    cw = 320
+    s = 1000 * hidden + rows
+    x = seeded((rows, cw), s, 0.125).half()
+    gam, bet = 1 + 0.1 * seeded((cw,), s + 1), 0.1 * seeded((cw,), s + 2)
+    w1, w2 = seeded((2 * hidden, cw), s + 3, cw ** -0.5).half(), seeded((cw, hidden), s + 4, hidden ** -0.5).half()
+    b1, b2 = (0.1 * seeded((2 * hidden,), s + 5), 0.1 * seeded((cw,), s + 6)) if biases else (None, None)
+    packs = ops.rowchain_ff_pack(up(w1, dev), up(b1, dev), up(w2, dev))
+    got = ops.rowchain_ff(up(x, dev), up(gam, dev), up(bet, dev), packs, up(b2, dev), hidden).cpu().double()
+    X = x.double()
+    B1, B2 = (b1.double(), b2.double()) if biases else (0.0, 0.0)
+
+    def graph(rnd):
+        nrm = rnd(F.layer_norm(X, (cw,), gam.double(), bet.double(), 1e-5))
+        hc = nrm @ w1.double().t() + B1
+        return rnd(X + rnd(hc[:, :hidden] * F.gelu(hc[:, hidden:])) @ w2.double().t() + B2)
+    ref, twin = graph(lambda t: t), graph(r16d)
+    assert bool(torch.isfinite(got).all())
+    for name, g_, r_, t_ in (("out", got, ref, twin), ("out - x", got - X, ref - X, twin - X)):
+        yard, err = rel_l2(t_, r_), rel_l2(g_, r_)
+        worst, idx = worst_slice_rel_l2(g_, r_, (0,))
+        twin_worst = worst_slice_rel_l2(t_, r_, (0,))[0]
+        print(f"[abi rowchain] hidden {hidden} rows {rows} biases {biases} {name}: engine {err:.3e}  fp16-storage twin {yard:.3e}  "
+              f"worst row: engine {worst:.3e} at {idx}, twin {twin_worst:.3e}  (caps {1.25 * yard:.3e} / {2.5 * yard:.3e})")
+        assert yard > 1e-4, (name, yard)
+        assert twin_worst <= 2 * 1.25 * yard, (name, "inputs unfit: the twin's own worst row", twin_worst, yard)
+        assert err <= 1.25 * yard, (name, err, yard)
+        assert worst <= 2 * 1.25 * yard, (name, "row", idx, worst, yard)
+
+
+def test_rowchain_ff_refusals(dev, abi):
+    L, check, ptr, sp = abi
+    lib = sub("_lib")
+    ops = sub("ops")
+    cw, hidden = 320, 32
+    x = torch.zeros((128, 640), dtype=torch.float16, device=dev)
+    out = torch.full((128, 640), 123.0, dtype=torch.float16, device=dev)
+    gam = torch.ones(640, device=dev)
+    packs = ops.rowchain_ff_pack(torch.zeros((2 * hidden, cw), dtype=torch.float16, device=dev), None, torch.zeros((cw, hidden), dtype=torch.float16, device=dev))
+    assert L.sdmi_rowchain_ff(ptr(x), ptr(out), ptr(gam), ptr(gam), ptr(packs), None, 100, cw, hidden, 1e-5, sp()) != 0
+    assert "rows % 128" in lib.last_error()
+    assert L.sdmi_rowchain_ff(ptr(x), ptr(out), ptr(gam), ptr(gam), ptr(packs), None, 128, 640, hidden, 1e-5, sp()) != 0
+    assert "C = 320" in lib.last_error()
+    assert L.sdmi_rowchain_ff(None, ptr(out), ptr(gam), ptr(gam), ptr(packs), None, 128, cw, hidden, 1e-5, sp()) != 0
+    torch.cuda.synchronize()
+    assert bool((out.cpu() == 123.0).all())
+
+
+# ---- 4. host-side argument checks ----------------------------------------------------------------------------------------------------------
+def test_sampler_entries_refuse_null_pointers_and_negative_sizes(dev, abi):
+    """Every call below is rejected by an SDMI_REQUIRE before anything is launched: the buffers keep their bits."""
+    L, check, ptr, sp = abi
+    lib = sub("_lib")
+    n = 64
+    x, y, z = (torch.full((n,), v, device=dev) for v in (1.0, 2.0, 3.0))
+    p = ptr
+    refused = [
+        ("sdmi_euler_step", lambda: L.sdmi_euler_step(None, p(y), None, 1.0, 0.5, 0.0, 1.0, n, sp())),
+        ("sdmi_euler_step", lambda: L.sdmi_euler_step(p(x), None, None, 1.0, 0.5, 0.0, 1.0, n, sp())),
+        ("sdmi_euler_step", lambda: L.sdmi_euler_step(p(x), p(y), None, 1.0, 0.5, 0.0, 1.0, -1, sp())),
+        ("sdmi_dpmpp2m_step", lambda: L.sdmi_dpmpp2m_step(None, p(y), p(z), 0.5, -0.5, 1.5, 0.5, n, sp())),
+        ("sdmi_dpmpp2m_step", lambda: L.sdmi_dpmpp2m_step(p(x), None, p(z), 0.5, -0.5, 1.5, 0.5, n, sp())),
+        ("sdmi_dpmpp2m_step", lambda: L.sdmi_dpmpp2m_step(p(x), p(y), p(z), 0.5, -0.5, 1.5, 0.5, -n, sp())),
+        ("sdmi_ddim_step", lambda: L.sdmi_ddim_step(None, p(y), None, None, 0.5, 0.6, 0.0, 0.7, n, sp())),
+        ("sdmi_ddim_step", lambda: L.sdmi_ddim_step(p(x), None, None, p(z), 0.5, 0.6, 0.0, 0.7, n, sp())),
+        ("sdmi_ddim_step", lambda: L.sdmi_ddim_step(p(x), p(y), None, p(z), 0.5, 0.6, 0.0, 0.7, -1, sp())),
+        ("sdmi_axpby", lambda: L.sdmi_axpby(None, p(x), 2.0, None, 0.0, n, sp())),
+        ("sdmi_axpby", lambda: L.sdmi_axpby(p(y), None, 2.0, p(z), 1.0, n, sp())),
+        ("sdmi_axpby", lambda: L.sdmi_axpby(p(y), p(x), 2.0, p(z), 1.0, -1, sp())),
+    ]
+    for name, call in refused:
+        assert call() != 0, name
+        assert name in lib.last_error(), (name, lib.last_error())
+    torch.cuda.synchronize()
+    assert bool((x.cpu() == 1.0).all()) and bool((y.cpu() == 2.0).all()) and bool((z.cpu() == 3.0).all())
+    check(L.sdmi_axpby(p(y), p(x), 2.0, None, 0.0, 0, sp()))                         # n = 0 is an empty, valid call
+    torch.cuda.synchronize()
+    assert bool((y.cpu() == 2.0).all())
+
+
+def test_lora_merge_refuses_unknown_dtype_codes(dev, abi):
+    L, check, ptr, sp = abi
+    lib = sub("_lib")
+    rows, cols, rank = 8, 16, 2
+    out = torch.full((rows, cols), 123.0, device=dev)
+    w, u, d = torch.zeros((rows, cols), device=dev), torch.zeros((rows, rank), device=dev), torch.zeros((rank, cols), device=dev)
+    for codes in ((2, 1, 1), (1, -1, 1), (1, 1, 7), (0, 0, 2)):
+        assert L.sdmi_lora_merge(ptr(out), ptr(w), codes[0], ptr(u), codes[1], ptr(d), codes[2], rows, cols, rank, 1.0, sp()) != 0, codes
+        assert "SDMI_F16 or SDMI_F32" in lib.last_error()
+    torch.cuda.synchronize()
+    assert bool((out.cpu() == 123.0).all())
