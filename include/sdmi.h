@@ -379,7 +379,9 @@ int sdmi_engine_set_option(sdmi_engine* e, const char* name, int value);   /* "f
 
 /* Activation taps for the parity error budget (tests/test_gpu_c1_parity.py): with option "trace" = 1 the engine records, by
  * the reference's module name ("input_blocks.4.1", "middle_block.1.transformer_blocks.0", "decoder.up.2.block.1", ...), the
- * NHWC fp16 output of every block of the LAST UNet forward / VAE decode; the tensors stay valid until the next forward
+ * NHWC fp16 output of every block of the LAST UNet forward / VAE decode / VAE encode ("encoder.down.0.block.0", ...) / CLIP
+ * forward ("embeddings", "encoder.layers.3.self_attn+x", "encoder.layers.3", "final_layer_norm", "pooled.final_layer_norm":
+ * [B][H = L][W = 1][C = hidden]); the tensors stay valid until the next forward
  * (the activation arena never reuses memory within one).  tap_read copies tap `index` ([B][H][W][C] fp16) to a device buffer. */
 int sdmi_engine_tap_count(sdmi_engine* e);
 int sdmi_engine_tap_info(sdmi_engine* e, int index, char* name_out, int capacity, int64_t* dims_bhwc);

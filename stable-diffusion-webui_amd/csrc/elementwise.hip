@@ -858,7 +858,8 @@ __global__ __launch_bounds__(256) void small_linear_kernel(const float* a, const
 // output columns per wave and pass, so an activation value read from LDS feeds four fmas.  The wave-per-column kernel above re-reads
 // the B x K activation block from L1 / L2 for every column — 80 KB per 2.5 KB weight row on the fused ResBlock embedding projection
 // (16 x 1280 -> 17920: 1.4 GB of cache reads per launch, ~150 us for 46 MB of weights).  Per output the lane -> k assignment, the fma
-// order and the shuffle tree are the kernel above's: identical bits (tests/test_gpu_ops.py).
+// order and the shuffle tree are the kernel above's: identical bits (tests/test_gpu_models.py:
+// test_small_linear_lds_forms_give_the_bits_of_the_wave_per_column_form_320_wide, at 2, 5 and 16 rows).
 template <int BMAX, int CW>
 __global__ __launch_bounds__(256) void small_linear_lds_kernel(const float* a, const half_t* w, const float* bias, const float* add,
                                                               float* out, int B, int N, int K, int lda, int ldo, int silu_in,

@@ -1575,11 +1575,17 @@ static int vae_encode_run(Run& r, const void* x, int io_dtype, float* out, int B
         a.out = cur; a.ldo = C;
         TRY(run_conv(r, v.e_conv_in, a));
     }
+    // taps under the oracle's module names (option "trace": Run::reuse() is then off, so no tapped buffer is written over before
+    // tap_read; the fp32 moments are the call's result and need no tap)
+    if (!r.dry) e->taps.clear();
+    r.tap("encoder.conv_in", cur, B, H, W, C);
     half_t* o = nullptr;
     for (int i = 0; i < c.num_levels; ++i) {
+        int bj = 0;
         for (const ResW& rb : v.e_down[i].blocks) {
             TRY(run_res(r, rb, cur, nullptr, C, 0, B, H, W, 1e-6f, nullptr, 0, &o));
             cur = o; C = rb.cout;
+            r.tap("encoder.down." + std::to_string(i) + ".block." + std::to_string(bj++), cur, B, H, W, C);
         }
         if (v.e_down[i].has_resample) {
             // pad (0,1,0,1) then 3x3 stride 2 pad 0  (sd3_impls.py:227-236): out = floor((H + 1 - 3)/2) + 1
@@ -1590,11 +1596,15 @@ static int vae_encode_run(Run& r, const void* x, int io_dtype, float* out, int B
             a.out = d; a.ldo = C;
             TRY(run_conv(r, v.e_down[i].resample, a));
             cur = d; H = Ho; W = Wo;
+            r.tap("encoder.down." + std::to_string(i) + ".downsample", cur, B, H, W, C);
         }
     }
     TRY(run_res(r, v.e_mid1, cur, nullptr, C, 0, B, H, W, 1e-6f, nullptr, 0, &o)); cur = o;
+    r.tap("encoder.mid.block_1", cur, B, H, W, C);
     TRY(run_vae_attn(r, v.e_attn, cur, B, H, W, &o)); cur = o;
+    r.tap("encoder.mid.attn_1", cur, B, H, W, C);
     TRY(run_res(r, v.e_mid2, cur, nullptr, C, 0, B, H, W, 1e-6f, nullptr, 0, &o)); cur = o;
+    r.tap("encoder.mid.block_2", cur, B, H, W, C);
     half_t* tn = r.H((size_t)B * H * W * C);
     TRY(run_gn(r, v.e_norm_out, cur, nullptr, C, 0, B, H * W, 1e-6f, true, tn));
     {
@@ -1684,6 +1694,10 @@ static int clip_run(Run& r, const ClipW& c, const int* tokens, const float* inpu
     r.e->arena.reset();
     half_t* cur = r.H(M * C);
     if (!r.dry) TRY(launch_clip_embed(tokens, c.tok_emb, c.tok_dtype, c.pos_emb, inputs_embeds, cur, B, L, C, cfg.vocab_size, r.s));
+    // taps (option "trace") as [B, H = L, W = 1, C] under the oracle's module names; this pass only bump-allocates, so every tapped
+    // buffer stays whole until the next call resets the arena
+    if (!r.dry) r.e->taps.clear();
+    r.tap("embeddings", cur, B, L, 1, C);
     // `out` taps the residual stream after block layers-skip+1; the pooled row always comes from the LAST block + final norm
     // (transformers' pooler_output; open_clip's pool(ln_final(x)) @ text_projection), so run on when it is requested
     const int ntap = cfg.layers - skip + 1;
@@ -1724,6 +1738,8 @@ static int clip_run(Run& r, const ClipW& c, const int* tokens, const float* inpu
         half_t* x2 = r.H(M * C);
         TRY(run_linear(r, w.fc2, hmid, (int)M, x1, x2, C));
         cur = x2;
+        r.tap("encoder.layers." + std::to_string(i) + ".self_attn+x", x1, B, L, 1, C);
+        r.tap("encoder.layers." + std::to_string(i), x2, B, L, 1, C);
     }
     if (tap == nullptr) tap = cur;                           // ntap == nrun
     half_t* fin = tap;
@@ -1738,9 +1754,13 @@ static int clip_run(Run& r, const ClipW& c, const int* tokens, const float* inpu
         if (c.text_proj) pool_raw = r.F((size_t)B * C);
     }
     if (r.dry) return 0;
+    if (apply_final_ln) r.tap("final_layer_norm", fin, B, L, 1, C);
     TRY(launch_convert_to_f32(fin, SDMI_F16, out, (int64_t)M * C, r.s));
     if (pooled) {
-        if (last_ln != fin) TRY(launch_layernorm(cur, c.final_ln.g, c.final_ln.b, last_ln, (int64_t)M, C, cfg.eps, r.s));
+        if (last_ln != fin) {
+            TRY(launch_layernorm(cur, c.final_ln.g, c.final_ln.b, last_ln, (int64_t)M, C, cfg.eps, r.s));
+            r.tap("pooled.final_layer_norm", last_ln, B, L, 1, C);
+        }
         if (c.text_proj) {
             TRY(launch_clip_pool(tokens, last_ln, pool_raw, B, L, C, r.s));
             TRY(launch_small_linear(pool_raw, c.text_proj, nullptr, nullptr, pooled, B, c.proj_dim, C, C, c.proj_dim, false, false, r.s));

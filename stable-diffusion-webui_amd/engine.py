@@ -236,8 +236,9 @@ class Engine:
         return out
 
     def taps(self) -> dict:
-        """Block outputs of the last UNet forward / VAE decode recorded under option "trace": {reference module name: fp16 NCHW
-        tensor} (parity error budget; see sdmi_engine_tap_*)."""
+        """Block outputs of the last UNet forward / VAE decode / VAE encode / CLIP forward recorded under option "trace": {reference
+        module name: fp16 NCHW tensor} (parity error budget; see sdmi_engine_tap_*).  A CLIP tap [B, L, hidden] comes as
+        [B, hidden, L, 1]."""
         out = {}
         dev = torch.device("cuda", self.device)
         for i in range(int(lib.sdmi_engine_tap_count(self.handle))):

@@ -10,6 +10,16 @@ fp32 (= fp32 accumulation), every tensor a GPU kernel would *write* is rounded t
 (``oracle.unet.LOADED_HYPERNETWORKS``) are modules inside the same autocast region, applied to the fp16 attention context
 (modules/hypernetworks/hypernetwork.py:358-379), and round the same way.
 
+The VAE encoder (``oracle.vae.Encoder``) rounds as the decoder does: the GroupNorm output, the SiLU in front of ``conv_out`` and every
+convolution's result are stored tensors.
+
+The CLIP text towers (``oracle.clip``) follow the same rule — every tensor a kernel of the half-precision path writes is rounded, the
+arithmetic stays fp32 — read off transformers' CLIPTextModel (modeling_clip.py, CLIPAttention / CLIPMLP / CLIPEncoderLayer /
+CLIPTextEmbeddings; the reference runs it as ``model.half()``, modules/sd_hijack_clip.py:351-360): ``q_proj(x) * scale`` is a tensor
+of its own, the scores come out of one ``bmm`` and get the causal mask added, ``softmax`` and the product with V each write their
+result, the activation writes its result behind ``fc1``, both residual sums and the sum of token and position embeddings are tensor
+additions.  Linear and LayerNorm outputs are rounded by the leaf hooks.
+
 Used by the C1 parity tests to measure how far the reference's fp16 path itself sits from its fp32 CPU path — the yardstick the
 engine's own distance is compared with (profiles/r02_parity.json).
 """
@@ -21,6 +31,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from oracle import clip as oc
 from oracle import hypernetwork as ohn
 from oracle import unet as ou
 from oracle import vae as ov
@@ -120,15 +131,53 @@ def _vae_decoder_forward(self, z):
     return self.conv_out(r16(F.silu(self.norm_out(h))))
 
 
+def _vae_encoder_forward(self, x):
+    h = self.conv_in(x)
+    for i in range(self.nres):
+        for j in range(self.nrb):
+            h = self.down[i].block[j](h)
+        if i != self.nres - 1:
+            h = self.down[i].downsample(h)
+    h = self.mid.block_2(self.mid.attn_1(self.mid.block_1(h)))
+    return self.conv_out(r16(F.silu(self.norm_out(h))))
+
+
+def _clip_attn_forward(self, x, mask):
+    b, l, c = x.shape
+    d = c // self.heads
+    q = r16(self.q_proj(x) * d ** -0.5)
+    k, v = self.k_proj(x), self.v_proj(x)
+    sp = lambda t: t.view(b, l, self.heads, d).transpose(1, 2)
+    w = r16(sp(q) @ sp(k).transpose(-1, -2) + mask)
+    o = r16(r16(w.softmax(dim=-1)) @ sp(v))
+    return self.out_proj(o.transpose(1, 2).reshape(b, l, c))
+
+
+def _clip_mlp_forward(self, x):
+    return self.fc2(r16(self.act(self.fc1(x))))
+
+
+def _clip_layer_forward(self, x, mask):
+    x = r16(x + self.self_attn(self.layer_norm1(x), mask))
+    return r16(x + self.mlp(self.layer_norm2(x)))
+
+
+def _clip_emb_forward(self, tokens, inputs_embeds=None):
+    e = self.token_embedding(tokens) if inputs_embeds is None else inputs_embeds
+    return r16(e + self.position_embedding.weight[: e.shape[1]])
+
+
 _PATCHES = [(ou.ResBlock, _res_forward), (ou.CrossAttention, _attn_forward), (ou.GEGLU, _geglu_forward),
             (ou.BasicTransformerBlock, _tblock_forward), (ou.SpatialTransformer, _st_forward),
-            (ohn.HypernetworkModule, _hn_forward), (ov.ResnetBlock, _vae_res_forward), (ov.AttnBlock, _vae_attn_forward), (ov.Decoder, _vae_decoder_forward)]
+            (ohn.HypernetworkModule, _hn_forward), (ov.ResnetBlock, _vae_res_forward), (ov.AttnBlock, _vae_attn_forward), (ov.Decoder, _vae_decoder_forward),
+            (ov.Encoder, _vae_encoder_forward), (oc.ClipAttention, _clip_attn_forward), (oc.ClipMLP, _clip_mlp_forward),
+            (oc.ClipLayer, _clip_layer_forward), (oc.ClipEmbeddings, _clip_emb_forward)]
 _LEAVES = (nn.Conv2d, nn.Linear, nn.GroupNorm, nn.LayerNorm, nn.SiLU)
 
 
 @contextlib.contextmanager
 def fp16_storage(net: nn.Module):
-    """Inside the block ``net`` (an oracle UNetModel / AutoencoderKL / Decoder) computes with fp32 arithmetic and fp16-rounded
+    """Inside the block ``net`` (an oracle UNetModel / AutoencoderKL / Decoder / Encoder / ClipTextModel) computes with fp32 arithmetic and fp16-rounded
     stores at every point where the reference's half-precision autocast path materialises a tensor."""
     saved = [(cls, cls.forward) for cls, _ in _PATCHES]
     handles = []

@@ -21,6 +21,20 @@ def seeded_module_weights(module, seed):
                 p.copy_(0.02 * torch.randn(p.shape, generator=g))
 
 
+def clip_tokens(batch, vocab, seed, length=77):
+    """Token ids as the CLIP tokenizer lays them out, for a vocabulary whose two largest ids are BOS and EOS: BOS in column 0, random
+    ids below them, then EOS to the end of the row from a column that differs per row (equal maximal ids in a row: the pooled row is
+    taken at the FIRST of them) — except the last of several rows, whose only EOS is the last column."""
+    bos, eos = vocab - 2, vocab - 1
+    tok = torch.randint(0, bos, (batch, length), generator=torch.Generator(device="cpu").manual_seed(seed))
+    tok[:, 0] = bos
+    starts = (12, 60, 33, 45, 7, 70, 21, 52)
+    assert batch <= len(starts) and length > max(starts)
+    for b in range(batch):
+        tok[b, (length - 1 if batch > 1 and b == batch - 1 else starts[b]):] = eos
+    return tok
+
+
 def rel_l2(a, b):
     a = torch.as_tensor(a).double().flatten()
     b = torch.as_tensor(b).double().flatten()

@@ -17,6 +17,13 @@ A tap is matched either by the oracle module of the same `named_modules()` name 
 the engine's tap in its place, so the next module — and every skip connection that keeps the tensor — goes on with the engine's
 activation), or, for `<block>.attn1+x`, `<block>.attn2+x` and `<block>` of a BasicTransformerBlock, by the three `+ x` points of a
 forcing-aware block forward.  A tap that nothing matches, or that the pass never reaches, is an error: no tap is left out.
+
+The CLIP text towers (oracle.clip) go the same way: `embeddings` and `final_layer_norm` by module hook, `encoder.layers.<i>.self_attn+x`
+and `encoder.layers.<i>` by the two `+ x` points of a forcing-aware ClipLayer forward.  A token tensor [B, L, C] is an NCHW tensor of
+height L and width 1, so the two slicings mean per token (b, l, 0) and per channel.  The forced call must not ask for the pooled row:
+that path runs `final_layer_norm` a second time, on another tensor.  The VAE encoder's result — the fp32 moments, `quant_conv` folded
+into `conv_out` by the engine's host code — is filed as the tap of the AutoencoderKL module `quant_conv` with the call
+`n.encode_moments(x)`: its segment is norm_out -> SiLU -> conv_out -> quant_conv from the `encoder.mid.block_2` tap.
 """
 from __future__ import annotations
 
@@ -27,6 +34,7 @@ import torch
 import fp16_emu
 from fp16_emu import fp16_storage, r16
 from helpers import rel_l2, worst_slice_rel_l2
+from oracle import clip as oc
 from oracle import unet as ou
 
 MARGIN = 1.25            # the project's standing margin over a measured floor
@@ -34,6 +42,7 @@ SLICE_FACTOR = 2.0       # worst slice within 2 x the cap of the whole tensor (t
 YARD_FLOOR = 1e-4        # the fp16 rounding of one stored output alone is 2.06e-4: a smaller yardstick means the segment compares nothing
 SLICINGS = (("pixel (b, y, x)", (0, 2, 3)), ("channel", (1,)))      # of an NCHW tensor
 SUB_TAPS = (".attn1+x", ".attn2+x", "")                              # the three `+ x` points of a BasicTransformerBlock, in order
+CLIP_SUB_TAPS = (".self_attn+x", "")                                 # the two `+ x` points of a ClipLayer, in order
 
 
 class UnmatchedTap(AssertionError):
@@ -67,7 +76,9 @@ class _Forcing:
         mods = dict(net.named_modules())
         self.transformers = [m for m in mods.values() if isinstance(m, ou.SpatialTransformer)]
         self.block_names = {id(m): n for n, m in mods.items() if isinstance(m, ou.BasicTransformerBlock)}
-        points = {n + s for n in self.block_names.values() for s in SUB_TAPS}
+        self.block_names.update({id(m): n for n, m in mods.items() if isinstance(m, oc.ClipLayer)})
+        points = {n + s for n, m in mods.items() for s in (SUB_TAPS if isinstance(m, ou.BasicTransformerBlock) else CLIP_SUB_TAPS)
+                  if id(m) in self.block_names}
         self.hooked = {n: mods[n] for n in self.names if n in mods and n not in points}
         unmatched = sorted(n for n in self.names if n not in self.hooked and n not in points)
         if unmatched:
@@ -79,7 +90,8 @@ class _Forcing:
         if name not in self.recorded:
             return out
         tap = self.taps.get(name)
-        got = as_nchw(out, self.h if tap is None else tap.shape[2])
+        # (height of a token tensor: the tap's; on a free-running pass the feature map's — or, outside a SpatialTransformer, all L tokens)
+        got = as_nchw(out, tap.shape[2] if tap is not None else (self.h or out.shape[1]))
         self.seen[name] = got.detach().clone()
         if tap is None:
             return out
@@ -109,10 +121,28 @@ def forced_transformer_blocks(state):
         cls.forward = prev
 
 
+@contextlib.contextmanager
+def forced_clip_layers(state):
+    """The same for ClipLayer.forward and its two `+ x` points (fp16_emu._clip_layer_forward tells that the fp16 pattern is active)."""
+    cls = oc.ClipLayer
+    prev = cls.forward
+    rnd = r16 if prev is fp16_emu._clip_layer_forward else (lambda t: t)
+
+    def forward(self, x, mask):
+        name = state.block_names[id(self)]
+        x = state.visit(name + CLIP_SUB_TAPS[0], rnd(x + self.self_attn(self.layer_norm1(x), mask)))
+        return state.visit(name + CLIP_SUB_TAPS[1], rnd(x + self.mlp(self.layer_norm2(x))))
+    cls.forward = forward
+    try:
+        yield
+    finally:
+        cls.forward = prev
+
+
 def _run(net, call, names, taps, fp16):
     state = _Forcing(net, names, taps)
     handles = []
-    with torch.no_grad(), (fp16_storage(net) if fp16 else contextlib.nullcontext()), forced_transformer_blocks(state):
+    with torch.no_grad(), (fp16_storage(net) if fp16 else contextlib.nullcontext()), forced_transformer_blocks(state), forced_clip_layers(state):
         try:
             for m in state.transformers:
                 handles.append(m.register_forward_pre_hook(lambda mod, inp: setattr(state, "h", inp[0].shape[2])))
@@ -161,6 +191,24 @@ def vae_tap_names(vae):
             if re.fullmatch(r"conv_in|conv_out|mid\.(block_1|attn_1|block_2)|up\.\d+\.(block\.\d+|upsample)", n)]
 
 
+def clip_tap_names(model, layers_run, final_ln):
+    """What a traced CLIP forward without the pooled row must hand back (`model`: the ClipTextModel): the embeddings, the two `+ x`
+    points of each of the first `layers_run` layers, and `final_layer_norm` when it is applied to the returned state."""
+    assert 1 <= layers_run <= len(model.encoder.layers)
+    names = ["embeddings"]
+    for i in range(layers_run):
+        names += [f"encoder.layers.{i}{s}" for s in CLIP_SUB_TAPS]
+    return names + (["final_layer_norm"] if final_ln else [])
+
+
+def vae_encoder_tap_names(vae):
+    """The same for a traced VAE encode (`vae`: the AutoencoderKL): conv_in, every down block and downsample, the mid blocks — and
+    `quant_conv` for the moments."""
+    import re
+    return ["encoder." + n for n, _ in vae.encoder.named_modules()
+            if re.fullmatch(r"conv_in|down\.\d+\.(block\.\d+|downsample)|mid\.(block_1|attn_1|block_2)", n)] + ["quant_conv"]
+
+
 def segment_errors(net, call, taps):
     """-> [row per tap, in tap order]: engine = rel_l2(tap, o32), yard = rel_l2(o16, o32), and the worst slice of the engine's error
     per slicing, (value, index).  o32 / o16: the forced pass in fp32 / under the fp16 pattern, on identical forced inputs."""
@@ -181,6 +229,8 @@ def segment_kind(net, name):
     for s in SUB_TAPS[:2]:
         if name.endswith(s):
             return "block" + s
+    if name.endswith(CLIP_SUB_TAPS[0]):
+        return "layer" + CLIP_SUB_TAPS[0]
     return type(dict(net.named_modules())[name]).__name__
 
 

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import rel_l2, seeded
+from helpers import clip_tokens, rel_l2, seeded
 
 pytestmark = pytest.mark.gpu
 
@@ -1751,7 +1751,7 @@ def _traced(eng, fn):
         taps = {k: v.float().cpu() for k, v in eng.taps().items()}
     finally:
         eng.set_option("trace", 0)
-    return out.float().cpu(), taps
+    return (tuple(o.float().cpu() for o in out) if isinstance(out, tuple) else out.float().cpu()), taps
 
 
 def _tf_summary(net, rows, label):
@@ -1912,3 +1912,162 @@ def test_teacher_forced_tiny_vae_decode(dev, tiny, hw):
     rows = tf.segment_errors(vae, lambda n: n.decode_first_stage(z), taps)
     _tf_summary(vae, rows, label)
     tf.assert_segments(rows, label)
+
+
+@pytest.mark.parametrize("shape", [(2, 3, 32, 32), (2, 3, 24, 40), (1, 3, 26, 34)], ids=["32x32", "24x40", "26x34"])
+def test_teacher_forced_tiny_vae_encode(dev, tiny, shape):
+    """The `encoder.*` taps of one encode (and the fp32 moments, `quant_conv` folded into `conv_out` by the engine, as the tap of the
+    AutoencoderKL's `quant_conv`) against the oracle VAE's modules of the same names.  24x40: HW = 960 at level 0 and 12 x 20 = 240 tokens
+    in the mid attention; 26x34: the zero column and row that `Downsample` pads on the right and at the bottom only are read by the last
+    output column and row of an odd half-size, 13 x 17.  (The image is rounded to fp16 first: that is what the engine's first launch
+    reads.)"""
+    import teacher_forcing as tf
+    model, vae = tiny["model"], tiny["oracle"].vae
+    x = torch.tanh(seeded(shape, 313)).half().float()
+    got, taps = _traced(model.engine, lambda: model.encode_first_stage(x.to(dev)))
+    assert torch.isfinite(got).all() and got.shape == (shape[0], 8, shape[2] // 2, shape[3] // 2)
+    assert torch.equal(model.encode_first_stage(x.to(dev)).cpu(), got) and model.engine.taps() == {}     # without "trace": same bits, no taps left
+    taps["quant_conv"] = got
+    expected = tf.vae_encoder_tap_names(vae)
+    assert set(taps) == set(expected) and len(expected) == 8, sorted(set(taps) ^ set(expected))
+    label = "vae_enc/%dx%d" % shape[2:]
+    rows = tf.segment_errors(vae, lambda n: n.encode_moments(x), taps)
+    _tf_summary(vae, rows, label)
+    tf.assert_segments(rows, label)
+
+
+def _clip_engine_and_oracle(cfg):
+    """-> (Engine with the tower loaded, the oracle ClipTextModel, the state dict): seeded synthetic fp16 weights."""
+    import dataclasses
+    from oracle import clip as oclip
+    schema = sub("schema")
+    sd = schema.synthetic_state_dict(clip_cfg=cfg, dtype=torch.float16)
+    om = oclip.build_clip(oclip.ClipConfig(**dataclasses.asdict(cfg)), sd)
+    eng = sub("engine").Engine(0)
+    eng.load_clip(cfg, sd)
+    return eng, om, sd
+
+
+def _teacher_forced_clip(dev, eng, om, tok, skip, final_ln, label):
+    """One traced engine forward without the pooled row, then every tap against the oracle's module or `+ x` point that produces it, run
+    on the engine's previous tap; the returned fp32 state must be the last tap, converted, bit for bit."""
+    import teacher_forcing as tf
+    got, taps = _traced(eng, lambda: eng.clip_forward(tok.to(dev), skip=skip, apply_final_ln=final_ln))
+    assert torch.isfinite(got).all()
+    layers_run = len(om.encoder.layers) - skip + 1
+    expected = tf.clip_tap_names(om, layers_run, final_ln)
+    assert set(taps) == set(expected) and len(taps) == 1 + 2 * layers_run + int(final_ln), sorted(set(taps) ^ set(expected))
+    last = taps["final_layer_norm" if final_ln else f"encoder.layers.{layers_run - 1}"]
+    assert last.shape == (tok.shape[0], om.cfg.hidden, tok.shape[1], 1)
+    assert torch.equal(got, last[:, :, :, 0].transpose(1, 2))
+    # without "trace": the same bits, and the taps of the traced run are gone
+    assert torch.equal(eng.clip_forward(tok.to(dev), skip=skip, apply_final_ln=final_ln).cpu(), got) and eng.taps() == {}
+    rows = tf.segment_errors(om, lambda n: n(tok, skip=skip, apply_final_ln=final_ln), taps)
+    _tf_summary(om, rows, label)
+    tf.assert_segments(rows, label)
+    return rows
+
+
+TF_CLIP_TINY = [(b, act, skip, 0) for b in (1, 3) for act in ("quick_gelu", "gelu") for skip in (1, 2)] + [(3, "quick_gelu", 1, 1)]
+
+
+@pytest.mark.parametrize("batch,act,skip,generic", TF_CLIP_TINY, ids=["B%d-%s-skip%d%s" % (c[0], c[1], c[2], "-generic" * c[3]) for c in TF_CLIP_TINY])
+def test_teacher_forced_tiny_clip(dev, batch, act, skip, generic):
+    """The tiny tower (3 layers, hidden 128, 2 heads of 64), L = 77: 77 and 231 rows are ragged against the 64- and 128-row GEMM tiles
+    and the 128-query attention block, and the second 64-key tile holds 13 keys.  `skip` = 1 returns the final norm of the last layer,
+    `skip` = 2 the penultimate layer without it (the SDXL CLIP-L form).  One case under `force_generic`: the generic attention kernel's
+    causal path and the generic GEMM."""
+    cfg = sub("schema").tiny_clip(act=act)
+    eng, om, _ = _clip_engine_and_oracle(cfg)
+    try:
+        eng.set_option("force_generic", generic)
+        _teacher_forced_clip(dev, eng, om, clip_tokens(batch, cfg.vocab_size, 320 + batch), skip, skip == 1,
+                             "clip/tiny B%d %s skip%d%s" % (batch, act, skip, " generic" * generic))
+    finally:
+        eng.close()
+
+
+def _pooled_row_checks(dev, eng, om, sd, tok, label):
+    """`return_pooled` with `skip` = 2: the pooled row comes from a LayerNorm of the LAST layer that the returned state does not use
+    (tap `pooled.final_layer_norm`).  That norm against the oracle's on the engine's last-layer tap; without a projection the pooled row
+    is the norm's row at the first arg-max token, bit for bit; with `text_projection` every element is within the rounding of the
+    kernel's own summation of the float64 product of that same row: 8 * ceil(K / 512) sequential FMAs per lane and a 6-level butterfly
+    (the products of two fp16 values are exact in fp32), one unit of slack: (8 * ceil(K / 512) + 7) * 2^-24 * sum_k |w_k x_k|."""
+    import math
+    import teacher_forcing as tf
+    from helpers import worst_slice_rel_l2
+    from fp16_emu import r16
+    layers, K = len(om.encoder.layers), om.cfg.hidden
+    (out, pooled), taps = _traced(eng, lambda: eng.clip_forward(tok.to(dev), skip=2, apply_final_ln=False, return_pooled=True))
+    expected = tf.clip_tap_names(om, layers, False) + ["pooled.final_layer_norm"]
+    assert set(taps) == set(expected) and len(taps) == len(expected), sorted(set(taps) ^ set(expected))
+    assert torch.equal(out, taps[f"encoder.layers.{layers - 2}"][:, :, :, 0].transpose(1, 2))
+    norm = taps["pooled.final_layer_norm"]
+    n32 = tf.as_nchw(om.final_layer_norm(taps[f"encoder.layers.{layers - 1}"][:, :, :, 0].transpose(1, 2)).detach(), tok.shape[1])
+    row = {"block": "pooled.final_layer_norm", "shape": tuple(norm.shape), "engine": rel_l2(norm, n32), "yard": rel_l2(r16(n32), n32)}
+    for name, keep in tf.SLICINGS:
+        row[name] = worst_slice_rel_l2(norm, n32, keep)
+    tf.assert_segments([row], label)
+    pos = tok.to(torch.int).argmax(dim=-1)                        # the first of equal maxima
+    rows = norm[torch.arange(tok.shape[0]), :, pos, 0]
+    if om.text_projection is None:
+        assert pooled.shape == rows.shape and torch.equal(pooled, rows)
+        return
+    w = sd[sub("schema").CLIP_PREFIX + "text_projection.weight"].double()
+    ref = rows.double() @ w.T
+    bound = (8 * math.ceil(K / 512) + 7) * 2.0 ** -24 * (rows.double().abs() @ w.abs().T)
+    err = (pooled.double() - ref).abs()
+    print(f"[pooled projection] {label}: K {K} N {w.shape[0]} worst |err| / bound {float((err / bound).max()):.3f}")
+    assert pooled.shape == ref.shape and bool((err <= bound).all()), float((err / bound).max())
+
+
+@pytest.mark.parametrize("batch", [3, 5])
+@pytest.mark.parametrize("proj_dim", [None, 192, 320])
+def test_clip_pooled_row_and_projection_against_the_engines_own_norm_tap(dev, proj_dim, batch):
+    """The tiny tower's pooled row (clip_pool_kernel, small_linear).  `proj_dim` 192 (< 256 columns) runs small_linear's wave-per-column
+    form, 320 the form that stages the rows in LDS: 4 rows at B = 3, 16 rows at B = 5."""
+    cfg = sub("schema").tiny_clip(proj_dim=proj_dim)
+    eng, om, sd = _clip_engine_and_oracle(cfg)
+    try:
+        _pooled_row_checks(dev, eng, om, sd, clip_tokens(batch, cfg.vocab_size, 330 + batch), "clip/tiny pooled B%d proj %s" % (batch, proj_dim))
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("hidden,heads,act,proj_dim,batch", [(768, 12, "quick_gelu", None, 2), (1280, 20, "gelu", 1280, 3)], ids=["768", "1280"])
+def test_teacher_forced_clip_at_real_widths(dev, hidden, heads, act, proj_dim, batch):
+    """Two layers at CLIP-L's and OpenCLIP-bigG's widths (12 / 20 heads of 64, MLP 4 x hidden, vocabulary 1000): every segment is forced,
+    so depth adds nothing.  `skip` = 1 with the final norm, then `skip` = 2 without; at 1280 also the pooled row through the 1280-column
+    projection (K = 1280: three passes of 512 per lane)."""
+    cfg = sub("schema").ClipConfig(vocab_size=1000, hidden=hidden, layers=2, heads=heads, intermediate=4 * hidden, act=act, proj_dim=proj_dim)
+    eng, om, sd = _clip_engine_and_oracle(cfg)
+    tok = clip_tokens(batch, cfg.vocab_size, 340 + batch)
+    try:
+        _teacher_forced_clip(dev, eng, om, tok, 1, True, "clip/%d B%d skip1" % (hidden, batch))
+        _teacher_forced_clip(dev, eng, om, tok, 2, False, "clip/%d B%d skip2" % (hidden, batch))
+        if proj_dim:
+            _pooled_row_checks(dev, eng, om, sd, tok, "clip/%d pooled B%d" % (hidden, batch))
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("batch", [2, 5, 16])
+def test_small_linear_lds_forms_give_the_bits_of_the_wave_per_column_form_320_wide(dev, batch):
+    """small_linear_lds_kernel (csrc/elementwise.hip) claims the bits of small_linear_kernel: same lane -> k assignment, FMA order and
+    shuffle tree.  On the 320-wide UNet (time-embedding MLP: K = 320 and 1280; the fused ResBlock embedding projection: K = 1280, all
+    blocks' columns at once) one forward with the knob off and one with it on — B = 2: the 4-row LDS form, 5 and 16: the 16-row form."""
+    schema, lib = sub("schema"), sub("_lib")
+    cfg = schema.tiny_unet(model_channels=320, num_heads=8, num_head_channels=-1, context_dim=768)
+    sd = schema.synthetic_state_dict(cfg, None, dtype=torch.float16)
+    eng = sub("engine").Engine(0)
+    eng.load_unet(cfg, sd)
+    x, t, ctx = seeded((batch, 4, 16, 16), 350), torch.linspace(999.0, 1.0, batch), seeded((batch, 77, 768), 351)
+    outs = {}
+    try:
+        for mode in (0, 1):
+            lib.check(lib.lib.sdmi_debug_set(b"small_linear_lds", mode))
+            outs[mode] = eng.unet_forward(x.to(dev), t.to(dev), ctx.to(dev)).cpu()
+    finally:
+        lib.check(lib.lib.sdmi_debug_set(b"small_linear_lds", 1))
+        eng.close()
+    assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1])
