@@ -73,7 +73,32 @@ int sdmi_attention_vt(const void* q, const void* k, const void* vt, void* out,
  *   out[m, n] = epilogue( alpha * sum_{tap,c} A(m, tap, c) * W[n, tap*Cin + c] )
  * Replaces the torch ops issued by ldm's ResBlock / Downsample / Upsample / SpatialTransformer / FeedForward modules
  * (third-party; layer names pinned at extensions-builtin/Lora/networks.py:43-98; op inventory SURVEY.md 2.3 K1,K4,K7,K8).
- * All fields are plain values / device pointers. */
+ * All fields are plain values / device pointers.
+ *
+ * Per batch element z (grid.z, 0 <= z < batch), output row m = (b, yo, xo) and output column n:
+ *   out_z[m][n] = alpha * sum_{tap,c} A_z(m, tap, c) * W_z[n][tap*Cin + c] + bias[n or m] + rowbias[b][n] + resid_z[m][n]
+ * with A_z read at a0 / a1 + z*a_bs + pixel*lda0 / lda1 + c (both sources move by the same a_bs), W_z at w + z*w_bs, resid_z at
+ * resid + z*r_bs + m*ldr + n and out_z stored at out + z*o_bs + m*ldo + n — SDMI_EP_GEGLU: N/2 columns; SDMI_EP_TRANSPOSE:
+ * out + z*o_bs + (b*N + n)*ldo + (m - b*Ho*Wo); SDMI_EP_NCHW: out + z*o_bs + ((b*n_real + n)*Ho + yo)*Wo + xo, ldo unused.  All strides
+ * count elements.  bias and rowbias are shared by all batch elements.  Only the stored columns of the stored rows are written: the
+ * elements between them (ldo wider than the columns, o_bs larger than one element's rows) keep their contents.
+ *
+ * Zero means: lda0 / lda1 = 0 -> c0 / c1 (dense pixels); ldo = 0 -> the stored columns (N; N/2 with GEGLU; Ho*Wo transposed); ldr = 0
+ * -> N; stride = 0 -> 1; alpha = 0 -> 1 (a product scaled by zero cannot be asked for); n_real = 0 -> N; batch <= 0 -> 1.
+ * a_bs = 0, w_bs = 0 or r_bs = 0 with batch > 1 is a broadcast: every batch element reads the same A, W or residual.
+ *
+ * Refused before anything is launched (non-zero return, sdmi_last_error): a null a0 / w / out; B, Hi, Wi, Ho, Wo, N or c0 (c1 with a1)
+ * not positive; taps other than 1 / 9; a stride other than 1 / 2; c0 or c1 not a multiple of 8; lda0 < c0 or lda1 < c1; ldo smaller
+ * than the stored columns; ldr < N with a residual; n_real outside 1 .. N with SDMI_EP_NCHW; SDMI_EP_GEGLU with N % 64 != 0; a
+ * negative batch stride; batch > 1 with o_bs smaller than the elements one batch element stores (o_bs = 0: every element would write
+ * the same memory).
+ *
+ * Alignment.  The MFMA kernels load 16 bytes at a time: they run when N, c0 + c1 (and c0, with a second source) are multiples of 64,
+ * lda0 / lda1 multiples of 8, a0 / a1 / w, a column bias and rowbias 16-byte aligned and, with batch > 1, a_bs and w_bs multiples
+ * of 8.  Anything else runs the generic kernel, which takes any stride and base (force_generic = 1 asks for it).  On the MFMA
+ * kernels the stores are 4 elements wide at least: ldo, ldr and (batch > 1) o_bs, r_bs must be multiples of 4, out 8-byte aligned
+ * (16 with SDMI_EP_OUT_F32; 4 with SDMI_EP_NCHW) and resid 8-byte aligned, or the call is refused; multiples of 8 and 16-byte
+ * aligned bases get the 16-byte epilogue, with the same bits. */
 typedef struct sdmi_conv_desc {
     const void* a0;        /* source 0, NHWC fp16 [B,Hi,Wi,c0] (pixel stride lda0 elements) */
     const void* a1;        /* optional source 1 (channel-concatenated after source 0), or NULL */
@@ -85,14 +110,14 @@ typedef struct sdmi_conv_desc {
     int32_t c0, c1, lda0, lda1;
     int32_t B, Hi, Wi, Ho, Wo;
     int32_t taps;          /* 1 or 9 */
-    int32_t stride;        /* 1 or 2 */
+    int32_t stride;        /* 1 or 2 (0 = 1) */
     int32_t pad;           /* 1: symmetric "padding=1"; 0: none (VAE-encoder downsample pads right/bottom only) */
     int32_t up;            /* 1: nearest x2 upsample of the source fused into the gather */
     int32_t N;             /* output channels as packed (multiple of 64 for the MFMA kernel) */
     int32_t n_real;        /* output channels actually stored (NCHW mode), else = N */
-    int32_t ldo, ldr;
+    int32_t ldo, ldr;      /* row strides of out / resid in elements (0 = dense) */
     int32_t flags;         /* SDMI_EP_* */
-    float alpha;
+    float alpha;           /* 0 = 1 */
     int32_t batch;         /* grid.z batched GEMM count (>=1) with the strides below (elements) */
     int64_t a_bs, w_bs, o_bs, r_bs;
     int32_t force_generic; /* 1: run the simple non-MFMA HIP kernel (debug / unsupported shapes) */

@@ -142,8 +142,14 @@ int sdmi_attention_wide(const void* q, const void* k, const void* v, void* out, 
     API_GUARD_END
 }
 
+// The layout rules stated in sdmi_conv_desc's comment (include/sdmi.h), checked here before anything is launched; what depends on the
+// kernel family — the 16-byte operand loads, the 8-byte stores — is checked by launch_gemm.
 static int desc_to_p(const sdmi_conv_desc* d, GemmP* p) {
     SDMI_REQUIRE(d != nullptr, "null descriptor");
+    SDMI_REQUIRE(d->a0 && d->w && d->out, "sdmi_conv_gemm: null a0 / w / out");
+    SDMI_REQUIRE(d->B > 0 && d->Hi > 0 && d->Wi > 0 && d->Ho > 0 && d->Wo > 0 && d->N > 0 && d->c0 > 0 && (!d->a1 || d->c1 > 0),
+                 "sdmi_conv_gemm: B, Hi, Wi, Ho, Wo, N, c0 (and c1 with a second source) must be positive");
+    SDMI_REQUIRE(d->stride >= 0 && d->stride <= 2, "sdmi_conv_gemm: stride must be 1 or 2 (0 = 1)");
     *p = GemmP{};
     p->a0 = (const half_t*)d->a0; p->a1 = (const half_t*)d->a1; p->w = (const half_t*)d->w;
     p->bias = (const float*)d->bias; p->rowbias = (const float*)d->rowbias; p->resid = (const half_t*)d->resid;
@@ -153,14 +159,30 @@ static int desc_to_p(const sdmi_conv_desc* d, GemmP* p) {
     p->Hi = d->Hi; p->Wi = d->Wi; p->Ho = d->Ho; p->Wo = d->Wo;
     p->taps = d->taps; p->stride = d->stride ? d->stride : 1; p->pad = d->pad; p->up = d->up;
     SDMI_REQUIRE(p->taps == 1 || p->taps == 9, "taps must be 1 or 9");
+    SDMI_REQUIRE(p->c0 % 8 == 0 && p->c1 % 8 == 0, "sdmi_conv_gemm: c0 and c1 must each be a multiple of 8 (pad channels)");
+    SDMI_REQUIRE(p->lda0 >= p->c0 && (!p->a1 || p->lda1 >= p->c1), "sdmi_conv_gemm: lda smaller than the channel count");
     p->M = d->B * d->Ho * d->Wo; p->N = d->N; p->K = p->taps * p->cin;
-    p->ldo = d->ldo; p->ldr = d->ldr; p->ldw = p->K; p->ldrb = d->N;
+    p->ldw = p->K; p->ldrb = d->N;
     p->rows_per_batch = d->Ho * d->Wo;
     p->n_real = d->n_real ? d->n_real : d->N;
     p->flags = d->flags;
+    SDMI_REQUIRE(!(p->flags & EP_NCHW) || (p->n_real > 0 && p->n_real <= p->N), "sdmi_conv_gemm: n_real must lie in 1 .. N");
+    SDMI_REQUIRE(!(p->flags & EP_GEGLU) || p->N % 64 == 0, "sdmi_conv_gemm: SDMI_EP_GEGLU needs N % 64 == 0 (32 values | 32 gates)");
+    // stored rows x columns of one batch element, and the strides with 0 = dense
+    const int batch = d->batch > 0 ? d->batch : 1;
+    const bool tr = (p->flags & EP_TRANSPOSE) != 0, nchw = (p->flags & EP_NCHW) != 0;
+    const long cols = tr ? p->rows_per_batch : (p->flags & EP_GEGLU) ? p->N / 2 : p->N;
+    const long rows = tr ? (long)d->B * p->N : p->M;
+    p->ldo = d->ldo ? d->ldo : (int)cols; p->ldr = d->ldr ? d->ldr : d->N;
+    SDMI_REQUIRE(nchw || p->ldo >= cols, "sdmi_conv_gemm: ldo smaller than the stored columns");
+    SDMI_REQUIRE(!p->resid || p->ldr >= p->N, "sdmi_conv_gemm: ldr smaller than N");
     p->alpha = d->alpha == 0.f ? 1.f : d->alpha;
     p->a_bs = d->a_bs; p->w_bs = d->w_bs; p->o_bs = d->o_bs; p->r_bs = d->r_bs;
-    const size_t need = gemm_splitk_ws_bytes(p->M, p->N, p->K, d->batch > 0 ? d->batch : 1);
+    // every batch element stores its own output (a_bs / w_bs / r_bs = 0 only repeat what is read: a broadcast)
+    const long foot = nchw ? (long)d->B * p->n_real * p->rows_per_batch : (rows - 1) * p->ldo + cols;
+    SDMI_REQUIRE(batch == 1 || p->o_bs >= foot, "sdmi_conv_gemm: batch > 1 needs o_bs >= the elements one batch element stores");
+    SDMI_REQUIRE(batch == 1 || (p->a_bs >= 0 && p->w_bs >= 0 && p->r_bs >= 0), "sdmi_conv_gemm: negative batch stride");
+    const size_t need = gemm_splitk_ws_bytes(p->M, p->N, p->K, batch);
     if (d->splitk_workspace && need && (size_t)d->splitk_workspace_bytes >= need) p->splitk_ws = (float*)d->splitk_workspace;
     return 0;
 }

@@ -1986,6 +1986,7 @@ __global__ __launch_bounds__(512) void gemm_mfma_pingpong_dx_kernel(GemmP p) {
 // Generic kernel: one thread per output element, same addressing rules, no shape restrictions beyond Cin % 8 == 0.
 // Used for shapes the MFMA kernel does not cover and as the independent HIP cross-check in the parity tests.
 // ---------------------------------------------------------------------------------------------------------------
+typedef half_t h8u __attribute__((ext_vector_type(8), aligned(2)));
 __device__ __forceinline__ float dot_row(const GemmP& p, const half_t* a0, const half_t* a1, const half_t* wrow,
                                          const RowInfo& ri) {
     float acc = 0.f;
@@ -2013,8 +2014,9 @@ __device__ __forceinline__ float dot_row(const GemmP& p, const half_t* a0, const
             }
             if (!ok) continue;
             const long pix = ((long)ri.b * p.Hi + yi) * p.Wi + xi;
-            const h8 av = *reinterpret_cast<const h8*>(src + pix * lda + cch);
-            const h8 wv = *reinterpret_cast<const h8*>(wrow + (long)tap * p.cin + cb);
+            // (h8u: 2-byte aligned — this kernel is where launch_gemm sends row / batch strides and bases off the 16-byte grid)
+            const h8 av = *reinterpret_cast<const h8u*>(src + pix * lda + cch);
+            const h8 wv = *reinterpret_cast<const h8u*>(wrow + (long)tap * p.cin + cb);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc = fmaf((float)av[e], (float)wv[e], acc);
         }
@@ -2312,6 +2314,18 @@ bool gemm_mfma_supported(const GemmP& p) {
     return true;
 }
 
+// The MFMA kernels stage their operand tiles with 16-byte loads (LDS-direct or through registers) at a0 / a1 / w + z * batch stride +
+// row * ld + 8 * chunk, and read the column bias and the [B][N] row bias as float4: all of these on the 16-byte grid, or the launch
+// goes to the generic kernel (scalar / alignment-agnostic accesses), the way a row stride with lda % 8 != 0 does.
+static bool gemm_loads_aligned(const GemmP& p, int batch) {
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    if (!al16(p.a0) || !al16(p.a1) || !al16(p.w)) return false;
+    if (batch > 1 && (p.a_bs % 8 || p.w_bs % 8)) return false;
+    if (p.bias && !(p.flags & EP_BIAS_ROW) && !al16(p.bias)) return false;
+    if (p.rowbias && !al16(p.rowbias)) return false;
+    return true;
+}
+
 // Tile configurations.  flop per byte staged into LDS = BM*BN/(BM+BN): the big 8-wave tiles exist because the
 // 128x128 tile (64 flop/B) saturates the L2 -> LDS path long before the MFMA pipe.
 enum GemmCfg {
@@ -2516,8 +2530,9 @@ int launch_gemm(const GemmP& p_in, int batch, bool force_generic, bool use_glds,
                      "EP_LNFOLD: 1x1 / linear layers with fp16 row-major (or transposed) output only");
         SDMI_REQUIRE(!force_generic && use_glds && gemm_mfma_supported(p), "EP_LNFOLD runs on the LDS-direct MFMA kernels only");
     }
-    if (force_generic || !gemm_mfma_supported(p)) {
+    if (force_generic || !gemm_mfma_supported(p) || !gemm_loads_aligned(p, batch)) {
         SDMI_REQUIRE(!(p.flags & EP_HILO), "(hi, lo) stream tensors need the MFMA kernels (shape not supported / force_generic)");
+        SDMI_REQUIRE(!(p.flags & EP_LNFOLD), "EP_LNFOLD runs on the MFMA kernels only (operand not 16-byte aligned)");
         const bool geglu = p.flags & EP_GEGLU;
         const long total = (long)p.M * (geglu ? p.N / 2 : p.N);
         int blocks = (int)std::min<long>((total + 255) / 256, 65535L * 8);
@@ -2527,12 +2542,24 @@ int launch_gemm(const GemmP& p_in, int batch, bool force_generic, bool use_glds,
         return 0;
     }
     {
+        // The narrowest stores of the MFMA epilogues and of the split-K reduce pass are 4 consecutive elements at out + z * o_bs +
+        // row * ldo + 4 * q (8 bytes of fp16, 16 of fp32; EP_NCHW: single floats), the residual is read the same way: refused here, before
+        // any launch, if a stride or a base is off that grid (force_generic takes any).
+        const bool nchw = (p.flags & EP_NCHW) != 0;
+        const uintptr_t omask = nchw ? 3 : (p.flags & EP_OUT_F32) ? 15 : 7;
+        SDMI_REQUIRE((nchw || (p.ldo % 4 == 0 && (batch == 1 || p.o_bs % 4 == 0))) &&
+                         (!p.resid || (p.ldr % 4 == 0 && (batch == 1 || p.r_bs % 4 == 0))),
+                     "ldo / ldr / o_bs / r_bs must be multiples of 4 elements on the MFMA kernels (force_generic takes any)");
+        SDMI_REQUIRE(((uintptr_t)p.out & omask) == 0 && ((uintptr_t)p.resid & 7) == 0,
+                     "out / resid not aligned for the MFMA kernels' stores: 8 bytes (16 for an fp32 store; force_generic takes any)");
+    }
+    {
         // 16-byte epilogue accesses need 16-byte aligned rows and bases (EP_TRANSPOSE: 8 consecutive tokens inside one image)
         auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
         bool wide = g_ep_wide != 0 && al16(p.out) && p.ldo % 8 == 0 && p.o_bs % 8 == 0 && p.N % 8 == 0;
         if (p.resid) wide = wide && al16(p.resid) && p.ldr % 8 == 0 && p.r_bs % 8 == 0;
         if (p.flags & EP_TRANSPOSE) wide = wide && p.rows_per_batch % 8 == 0 && p.M % 8 == 0;
-        if (!wide) p.flags |= EP_NARROW;
+        if (!wide) p.flags |= EP_NARROW;                     // (the profiler's launch name says so: "_ep8")
     }
     // (hi, lo) stream tensors (EP_HILO, engine option "residual_fp32"): plain fp16 row-major launches.  Round 6: they take split-K (the
     // reduce pass carries the pair), the GroupNorm-statistics epilogue (sums of hi + lo: what the norm reads) and 16-byte accesses —
@@ -2617,7 +2644,7 @@ int launch_gemm(const GemmP& p_in, int batch, bool force_generic, bool use_glds,
     std::string pname;
     if (prof_enabled()) {
         pname = std::string(kCfgName[cfg]) + (phase ? "pp" : "") + (split > 1 ? "_splitk" + std::to_string(p.splitk) : "") + (p.taps == 9 ? "_conv3x3" : "_1x1") +
-                ((p.flags & EP_GEGLU) ? "_geglu" : "") + ((p.flags & EP_TRANSPOSE) ? "_tr" : "") + ((p.flags & EP_HILO) ? "_hl" : "") + (p.tile_order ? "_mf" : "") + (p.stats_nchunk ? "_gn" : "") + (p.korder == 2 ? "_dx" : "") + " M" + std::to_string(p.M) + " N" + std::to_string(p.N) + " K" + std::to_string(p.K) +
+                ((p.flags & EP_GEGLU) ? "_geglu" : "") + ((p.flags & EP_TRANSPOSE) ? "_tr" : "") + ((p.flags & EP_HILO) ? "_hl" : "") + (p.tile_order ? "_mf" : "") + (p.stats_nchunk ? "_gn" : "") + (p.korder == 2 ? "_dx" : "") + ((p.flags & EP_NARROW) ? "_ep8" : "") + " M" + std::to_string(p.M) + " N" + std::to_string(p.N) + " K" + std::to_string(p.K) +
                 ((p.flags & EP_LNFOLD) ? " ln" : "") + (batch > 1 ? " x" + std::to_string(batch) : "");
     }
     ProfScope ps(pname.c_str(), pf_flops, pf_bytes, s);

@@ -9,7 +9,10 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the cases of tests/test_gpu_abi.py: sampler updates, CFG, weight deltas and slerp | attention | rowchain | refusals
-GPU_FILE_CASES = (8 + 8 + 16 + 12 + 3) + (6 + 3 + 9 + 3) + (4 + 2 + 2 + 2 + 9 + 2) + (4 + 3 + 2 + 2 + 1 + 1 + 1) + (12 + 1) + 2
+# | sdmi_conv_gemm from raw descriptors: batched scores, shared A, split-K (+ the broadcast residual), 3x3 with strided sources, GEGLU /
+#   transposed / NCHW stores, wide against narrow epilogue, alpha, the misaligned batch stride, refusals; sdmi_pack_conv_weight
+GPU_FILE_CASES = ((8 + 8 + 16 + 12 + 3) + (6 + 3 + 9 + 3) + (4 + 2 + 2 + 2 + 9 + 2) + (4 + 3 + 2 + 2 + 1 + 1 + 1) + (12 + 1) + 2 +
+                  (18 + 4 + 12 + 1 + 22 + 3 + 3 + 2 + 4 + 2 + 1 + 1) + 8)
 
 
 def sub(name):

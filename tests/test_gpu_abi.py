@@ -13,9 +13,21 @@
 3. sdmi_rowchain_ff at one, three and five 32-unit chunks of hidden width against float64, measured with the fp16-storage twin
    (the rule of tests/test_gpu_esrgan.py).
 4. What the entries refuse on the host, before any launch.
+5. sdmi_conv_gemm on descriptors filled here, in the layouts sdmi_conv_desc documents and the engine's batched launches use: batch > 1 with
+   the four batch strides, pixel rows wider than the channel count, output and residual rows inside wider buffers, alpha, the row bias, a
+   caller's split-K workspace with a batch, over every kernel family (forced with the tuning knobs and confirmed from the launch name).
+   Rule (`assert_gemm`): the reference is the header's formula in float64 from the fp16-rounded operands, `mag` the same with every term
+   replaced by its absolute value, and |got - ref| <= r |ref| + c 2^-24 mag elementwise, r = 2^-11 (fp16 store) or 2^-24 (fp32 store),
+   c = 2 (K + 8): K additions in any order at up to two units each (the matrix core's accumulate need not round to nearest) plus the
+   epilogue's terms — a wrong row, batch element or stride is an error of order mag / sqrt(K).  Next to it the relative-L2 caps of
+   tests/test_gpu_ops.py (6e-4 fp16 store, 2e-5 fp32 store, 8e-4 GEGLU — the only rule for GEGLU, which is not linear), globally and
+   per output row / column.  The gaps of the input buffers hold 3000, the output sits in a sentinel-filled buffer (`GuardedRows`).
+   sdmi_pack_conv_weight bit-equal against numpy.
 
 Every case also runs on the host-emulated library (tests/test_cpu_abi.py); the measured figures are in profiles/abi_ops_parity.md."""
+import ctypes
 import importlib
+import json
 import math
 
 import numpy as np
@@ -729,3 +741,483 @@ def test_lora_merge_refuses_unknown_dtype_codes(dev, abi):
         assert "SDMI_F16 or SDMI_F32" in lib.last_error()
     torch.cuda.synchronize()
     assert bool((out.cpu() == 123.0).all())
+
+
+# ---- 5. sdmi_conv_gemm in the layouts the header documents ---------------------------------------------------------------------------------
+EP_OUT_F32, EP_GEGLU, EP_NCHW, EP_BIAS_ROW, EP_TRANSPOSE = 1, 2, 4, 8, 64
+GAP = 3000.0                               # what the unused parts of the input buffers hold: finite, and an error of order 1e3 x mag if read
+OUT_FILL = -777.0                          # what the output buffer holds wherever the entry must not write
+LEAD = 64                                  # elements in front of every operand: 128 / 256 bytes, so the bases keep the allocation's alignment
+KNOB_RESET = {"gemm_cfg": -1, "gemm_split": 0, "gemm_pipe": -1, "tile_order": -1, "ep_wide": 1, "conv_korder": -1}
+
+
+def lay(dense, ld, bs, dtype, dev, lead=LEAD, fill=GAP):
+    """dense [batch, rows, cols] -> (flat device buffer, address of element (0, 0, 0)); element (z, r, c) sits at z * bs + r * ld + c,
+    everything else — the columns from cols to ld, the tail of each batch element, both ends — holds `fill`."""
+    batch, rows, cols = dense.shape
+    assert ld >= cols and (batch == 1 or bs >= rows * ld)
+    flat = torch.full((lead + (batch - 1) * bs + rows * ld + LEAD,), fill, dtype=dtype)
+    for z in range(batch):
+        flat[lead + z * bs:lead + z * bs + rows * ld].view(rows, ld)[:, :cols] = dense[z].to(dtype)
+    flat = up(flat, dev)
+    return flat, flat.data_ptr() + lead * flat.element_size()
+
+
+class GuardedRows:
+    """Guarded for a strided, batched output: [batch] x [rows][ld] with `cols` stored columns inside one allocation filled with OUT_FILL.
+    `read` returns the stored elements and requires every other one — the columns from cols to ld of every row, the rows between
+    rows * ld and bs of every batch element, both ends of the buffer — to be bit-equal to the sentinel."""
+
+    def __init__(self, batch, rows, cols, ld, bs, dtype, dev, lead=LEAD):
+        assert ld >= cols and (batch == 1 or bs >= rows * ld)
+        self.geom = (batch, rows, cols, ld, bs, lead)
+        self.full = torch.full((lead + (batch - 1) * bs + rows * ld + LEAD,), OUT_FILL, dtype=dtype, device=dev)
+        self.addr = self.full.data_ptr() + lead * self.full.element_size()
+
+    def read(self, what):
+        batch, rows, cols, ld, bs, lead = self.geom
+        f = self.full.cpu()
+        free = torch.ones(f.shape, dtype=torch.bool)
+        got = []
+        for z in range(batch):
+            lo = lead + z * bs
+            free[lo:lo + rows * ld].view(rows, ld)[:, :cols] = False
+            got.append(f[lo:lo + rows * ld].view(rows, ld)[:, :cols].clone())
+        ints = torch.int16 if f.dtype == torch.float16 else torch.int32
+        sentinel = torch.full((1,), OUT_FILL, dtype=f.dtype).view(ints)
+        touched = (f.view(ints)[free] != sentinel).nonzero()
+        assert touched.numel() == 0, (what, "elements outside the stored layout were written", int(touched.numel()), "first free-slot index", int(touched[0]))
+        return torch.stack(got)
+
+
+_PROBLEMS = {}
+
+
+def gemm_problem(**kw):
+    """The operands of one launch (CPU tensors, fp16-rounded) and the header's formula in float64: ref and mag [batch, rows, cols] in the
+    store layout.  Cached: every kernel family of a case group gets the same operands and the same reference."""
+    key = tuple(sorted(kw.items()))
+    if key in _PROBLEMS:
+        return _PROBLEMS[key]
+    g = dict(taps=1, batch=1, B=1, Hi=1, Wi=1, c0=64, c1=0, N=64, stride=1, up=0, flags=0, alpha=1.0, bias=None, rowbias=False, resid=False,
+             shared_a=False, shared_r=False, n_real=0, seed=0)
+    g.update(kw)
+    taps, batch, B, Hi, Wi, c0, c1, N, seed = (g[k] for k in ("taps", "batch", "B", "Hi", "Wi", "c0", "c1", "N", "seed"))
+    k3 = 3 if taps == 9 else 1
+    cin = c0 + c1
+    za = 1 if g["shared_a"] else batch
+    a0 = seeded((za, B, Hi, Wi, c0), seed + 1).half()
+    a1 = seeded((za, B, Hi, Wi, c1), seed + 2).half() if c1 else None
+    w = seeded((batch, N, cin, k3, k3), seed + 3, (taps * cin) ** -0.5).half()
+    if g["up"]:
+        Ho, Wo = 2 * Hi, 2 * Wi
+    elif taps == 9:
+        Ho, Wo = (Hi - 1) // g["stride"] + 1, (Wi - 1) // g["stride"] + 1
+    else:
+        Ho, Wo = Hi, Wi
+    M, hw = B * Ho * Wo, Ho * Wo
+    acc, amag = [], []
+    for z in range(batch):
+        x = a0[min(z, za - 1)] if a1 is None else torch.cat([a0[min(z, za - 1)], a1[min(z, za - 1)]], dim=3)
+        x = x.double().permute(0, 3, 1, 2)
+        if g["up"]:
+            x = x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+        for lst, xx, ww in ((acc, x, w[z].double()), (amag, x.abs(), w[z].double().abs())):
+            lst.append(F.conv2d(xx, ww, stride=g["stride"], padding=1 if taps == 9 else 0).permute(0, 2, 3, 1).reshape(M, N))
+    acc, amag = torch.stack(acc), torch.stack(amag)
+    alpha = f32(g["alpha"])
+    ref, mag = alpha * acc, abs(alpha) * amag
+    bias = rowbias = resid = None
+    if g["bias"] == "col":
+        bias = seeded((N,), seed + 4, 0.5)
+        ref, mag = ref + bias.double(), mag + bias.double().abs()
+    elif g["bias"] == "row":
+        bias = seeded((M,), seed + 4, 0.5)
+        ref, mag = ref + bias.double()[:, None], mag + bias.double().abs()[:, None]
+    if g["rowbias"]:
+        rowbias = seeded((B, N), seed + 5, 0.5)
+        rb = rowbias.double().repeat_interleave(hw, dim=0)
+        ref, mag = ref + rb, mag + rb.abs()
+    if g["resid"]:
+        resid = seeded((1 if g["shared_r"] else batch, M, N), seed + 6).half()
+        ref, mag = ref + resid.double(), mag + resid.double().abs()
+    if g["flags"] & EP_GEGLU:                               # W rows in (32 value | 32 gate) groups -> N / 2 columns a * gelu(g); no mag: nonlinear
+        v = ref.view(batch, M, N // 64, 2, 32)
+        ref = (v[:, :, :, 0] * F.gelu(v[:, :, :, 1])).reshape(batch, M, N // 2)
+        mag = None
+    elif g["flags"] & EP_TRANSPOSE:                         # out[b][n][m - b * Ho * Wo]
+        ref, mag = (t.view(batch, B, hw, N).transpose(2, 3).reshape(batch, B * N, hw) for t in (ref, mag))
+    elif g["flags"] & EP_NCHW:                              # fp32 [B][n_real][Ho][Wo], dense
+        ref, mag = (t.view(batch, B, hw, N)[..., :g["n_real"]].transpose(2, 3).reshape(batch, 1, B * g["n_real"] * hw) for t in (ref, mag))
+    out = dict(g, a0=a0, a1=a1, w=w.permute(0, 1, 3, 4, 2).reshape(batch, N, taps * cin), bias_t=bias, rowbias_t=rowbias, resid_t=resid,
+               Ho=Ho, Wo=Wo, M=M, K=taps * cin, ref=ref, mag=mag)
+    _PROBLEMS[key] = out
+    return out
+
+
+def launch_gemm(abi, dev, pr, *, lda0=0, lda1=0, ldo=0, ldr=0, a_gap=0, w_gap=0, o_gap=0, r_gap=0, impl=0, workspace=False, out_lead=LEAD,
+                resid_lead=LEAD, alpha=None, edit=None):
+    """One sdmi_conv_gemm call on a descriptor filled here (not through ops.conv_gemm): every operand strided inside a larger buffer whose
+    gaps hold GAP, the output inside a GuardedRows.  ld* = 0: dense.  *_gap: elements added to the dense batch stride.
+    -> (stored elements [batch, rows, cols] on the CPU, launch names); with `edit` (a function that changes the descriptor just before the
+    call, for the refusal test): (return code, the GuardedRows)."""
+    L, check, ptr, sp = abi
+    lib = sub("_lib")
+    batch, B, Hi, Wi, c0, c1, N, M, flags = (pr[k] for k in ("batch", "B", "Hi", "Wi", "c0", "c1", "N", "M", "flags"))
+    pix = B * Hi * Wi
+    lda0, lda1 = lda0 or c0, lda1 or c1
+    a_bs = 0 if pr["shared_a"] else pix * max(lda0, lda1) + a_gap
+    d = lib.ConvDesc()
+    _, d.a0 = lay(pr["a0"].reshape(-1, pix, c0), lda0, a_bs, torch.float16, dev)
+    if c1:
+        _, d.a1 = lay(pr["a1"].reshape(-1, pix, c1), lda1, a_bs, torch.float16, dev)
+    w_bs = N * pr["K"] + w_gap
+    _, d.w = lay(pr["w"], pr["K"], w_bs, torch.float16, dev)
+    if pr["bias_t"] is not None:
+        d.bias = up(pr["bias_t"], dev).data_ptr()
+    if pr["rowbias_t"] is not None:
+        d.rowbias = up(pr["rowbias_t"], dev).data_ptr()
+    _, rows, cols = pr["ref"].shape
+    nchw = bool(flags & EP_NCHW)
+    ldo_eff = cols if nchw else (ldo or cols)
+    o_bs = rows * ldo_eff + o_gap
+    out = GuardedRows(batch, rows, cols, ldo_eff, o_bs, torch.float32 if flags & (EP_OUT_F32 | EP_NCHW) else torch.float16, dev, lead=out_lead)
+    d.out = out.addr
+    if pr["resid_t"] is not None:
+        ldr = ldr or N
+        d.r_bs = 0 if pr["shared_r"] else M * ldr + r_gap
+        _, d.resid = lay(pr["resid_t"], ldr, d.r_bs, torch.float16, dev, lead=resid_lead)
+    d.c0, d.c1, d.lda0, d.lda1 = c0, c1, lda0, lda1 if c1 else 0
+    d.B, d.Hi, d.Wi, d.Ho, d.Wo = B, Hi, Wi, pr["Ho"], pr["Wo"]
+    d.taps, d.stride, d.pad, d.up = pr["taps"], pr["stride"], 1 if pr["taps"] == 9 else 0, pr["up"]
+    d.N, d.n_real, d.ldo, d.ldr, d.flags = N, pr["n_real"], 0 if nchw else ldo_eff, ldr, flags
+    d.alpha = pr["alpha"] if alpha is None else alpha
+    d.batch, d.a_bs, d.w_bs, d.o_bs = batch, a_bs, w_bs, o_bs
+    d.force_generic = impl
+    if workspace:
+        nbytes = int(L.sdmi_conv_splitk_workspace_bytes(M, N, pr["K"], batch))
+        assert nbytes > 0
+        ws = up(torch.zeros(nbytes + 4096, dtype=torch.uint8), dev)
+        ws[nbytes:] = 0x5A
+        d.splitk_workspace, d.splitk_workspace_bytes = ws.data_ptr(), nbytes
+    if edit:
+        edit(d)
+    check(L.sdmi_profile_begin(), "profile_begin")
+    try:
+        rc = L.sdmi_conv_gemm(ctypes.byref(d), sp())
+        torch.cuda.synchronize()
+    finally:
+        buf = ctypes.create_string_buffer(1 << 16)
+        check(L.sdmi_profile_end(buf, len(buf)), "profile_end")
+    if edit:
+        return rc, out
+    check(rc, "sdmi_conv_gemm")
+    if workspace:
+        assert bool((ws[nbytes:].cpu() == 0x5A).all()), "the split-K workspace's tail was written"
+    names = [k["name"] for k in json.loads(buf.value.decode())["kernels"]]
+    return out.read(names), names
+
+
+def assert_gemm(got, pr, group, what):
+    """Section 2 of the module's rule for sdmi_conv_gemm: elementwise |got - ref| <= r |ref| + c 2^-24 mag with r the store format's half
+    ulp and c = 2 (K + 8), next to the project's relative-L2 caps, globally and per output row / output column."""
+    ref, mag, K = pr["ref"], pr["mag"], pr["K"]
+    f32_store = bool(pr["flags"] & (EP_OUT_F32 | EP_NCHW))
+    cap = 8e-4 if pr["flags"] & EP_GEGLU else 2e-5 if f32_store else 6e-4
+    got = got.double()
+    assert got.shape == ref.shape and bool(torch.isfinite(got).all()), what
+    worst = 0.0
+    if mag is not None:
+        r, c = (2.0 ** -24 if f32_store else 2.0 ** -11), 2 * (K + 8)
+        err = (got - ref).abs()
+        over = (err - r * ref.abs()).clamp_min(0.0)
+        unit = U * mag
+        worst = float((over[unit > 0] / unit[unit > 0]).max())
+        bad = err > r * ref.abs() + c * unit
+    e = rel_l2(got, ref)
+    rows, cols = worst_slice_rel_l2(got, ref, (0, 1)), worst_slice_rel_l2(got, ref, (2,))
+    print(f"[abi conv_gemm] <{group}> {what}: worst (|got - ref| - r |ref|) = {worst:.2f} x 2^-24 mag (cap {2 * (K + 8)}); rel_l2 {e:.3e} (cap {cap:.0e}), "
+          f"worst row {rows[0]:.3e} at {rows[1]}, worst column {cols[0]:.3e} at {cols[1]} (cap {2 * cap:.0e})")
+    if mag is not None:
+        assert not bool(bad.any()), (what, "elements over the bound", int(bad.sum()), "first at", int(bad.flatten().nonzero()[0]), "worst multiple", worst)
+    assert e < cap, (what, e, cap)
+    assert rows[0] < 2 * cap and cols[0] < 2 * cap, (what, "row", rows, "column", cols, "cap", 2 * cap)
+
+
+class knobs:
+    """sdmi_debug_set for the duration of a block; every knob this section touches goes back to its default on the way out."""
+
+    def __init__(self, **kv):
+        self.kv = kv
+
+    def __enter__(self):
+        lib = sub("_lib")
+        for k, v in self.kv.items():
+            lib.check(lib.lib.sdmi_debug_set(k.encode(), v), k)
+
+    def __exit__(self, *exc):
+        lib = sub("_lib")
+        for k, v in KNOB_RESET.items():
+            lib.check(lib.lib.sdmi_debug_set(k.encode(), v), k)
+
+
+TILE_NAMES = {0: "128x128", 2: "64x64", 3: "128x128k32", 4: "256x256", 5: "256x320", 7: "128x64", 8: "128x320", 9: "128x160",
+              10: "128x160r4", 11: "128x128r4", 12: "128x64r3", 13: "128x160r3"}
+PINGPONG = (4, 5, 8)
+
+
+def family(fam):
+    """A kernel family by name — "default", "mfma_reg", "generic", a gemm_cfg number, or one with "ts" (its two-stage form under gemm_pipe = 0)
+    -> (knobs, force_generic code, a predicate on the launch names: did that family really run?)."""
+    if fam == "default":
+        return {}, 0, lambda names: any(n.startswith("gemm_mfma_") for n in names)
+    if fam == "mfma_reg":
+        return {}, 2, lambda names: any(n.startswith("gemm_mfma_") for n in names)
+    if fam == "generic":
+        return {}, 1, lambda names: names == ["gemm_generic"]
+    cfg, two_stage = (int(fam[:-2]), True) if fam.endswith("ts") else (int(fam), False)
+    tile = "gemm_mfma_" + TILE_NAMES[cfg]
+    pp = cfg in PINGPONG and not two_stage
+
+    def ran(names):
+        first = names[0].split(" ")[0]
+        head = first.split("_splitk")[0].split("_1x1")[0].split("_conv3x3")[0]
+        return head == tile + ("pp" if pp else "")
+    return dict(gemm_cfg=cfg, **({"gemm_pipe": 0} if two_stage else {})), 0, ran
+
+
+def n_for(fam, narrow, wide):
+    """The output width a family's tile divides: 128 / 256 / 512 for the 64-, 128- and 256-wide tiles, 320 / 640 for the x160 / x320 ones."""
+    cfg = int(fam.rstrip("ts")) if fam[0].isdigit() else -1
+    return wide if cfg in (5, 8, 9, 10, 13) else narrow
+
+
+SCORE_FAMILIES = ["default", "0", "2", "3", "7", "9", "4", "5", "8", "4ts", "5ts", "8ts", "10", "11", "12", "13", "mfma_reg", "generic"]
+
+
+@pytest.mark.parametrize("fam", SCORE_FAMILIES)
+def test_conv_gemm_batched_scores(dev, abi, fam):
+    """The Q K^T of the VAE attention: batch 3, K = 128 read out of pixel rows of 256 elements, fp32 store with alpha = 128^-0.5 into rows
+    of ldo = N + 8, the three batch strides each wider than dense by another multiple of 8.  M = 200 (a ragged second 128-row tile); the
+    256-row tiles get M = 264 and two column tiles, so that both tile orders exist for them too."""
+    kn, impl, ran = family(fam)
+    big = fam.rstrip("ts") in ("4", "5")
+    rows = 264 if big else 200
+    n = n_for(fam, 512 if big else 256, 640)
+    pr = gemm_problem(batch=3, Hi=rows, c0=128, N=n, flags=EP_OUT_F32, alpha=128 ** -0.5, seed=100)
+    for order in ((0, 1) if impl != 1 else (-1,)):
+        with knobs(tile_order=order, **kn):
+            got, names = launch_gemm(abi, dev, pr, lda0=256, ldo=n + 8, a_gap=16, w_gap=8, o_gap=24, impl=impl)
+        assert ran(names), (fam, names)
+        if fam[0].isdigit():
+            assert ("_mf" in names[0][len("gemm_mfma_"):]) == (order == 1), names
+        if impl != 1:
+            assert names[0].endswith(" x3"), names
+        assert_gemm(got, pr, "batched scores", f"scores {fam} tile_order {order} {names[0]}")
+
+
+@pytest.mark.parametrize("fam", ["default", "5", "12", "generic"])
+def test_conv_gemm_shared_a_with_a_row_bias(dev, abi, fam):
+    """The fallback form of the V^T projection: a_bs = 0 (every batch element reads the same A), a weight stride, a bias of length M
+    indexed by the output row, fp16 rows of ldo = N + 8."""
+    kn, impl, ran = family(fam)
+    n = n_for(fam, 256, 320)
+    pr = gemm_problem(batch=3, Hi=200, c0=128, N=n, flags=EP_BIAS_ROW, bias="row", shared_a=True, seed=200)
+    with knobs(**kn):
+        got, names = launch_gemm(abi, dev, pr, lda0=136, ldo=n + 8, w_gap=24, o_gap=40, impl=impl)
+    assert ran(names), (fam, names)
+    assert_gemm(got, pr, "shared A, row bias", f"shared A {fam} {names[0]}")
+
+
+SPLIT_CASES = [(cfg, split, i) for i, (cfg, split) in enumerate((c, s) for c in (-1, 0, 5, 8) for s in (0, 2, 4))]
+
+
+@pytest.mark.parametrize("cfg,split,i", SPLIT_CASES, ids=[f"cfg{c}-split{s}" for c, s, _ in SPLIT_CASES])
+def test_conv_gemm_batched_long_k_with_split_k(dev, abi, cfg, split, i):
+    """The P V^T form: batch 2, M = 72, K = 1152, alpha = 0.5, a residual in rows of ldr = N + 16 with its own batch stride, a column or a
+    row bias, fp16 and fp32 stores, a caller's split-K workspace sized for the batch.  A forced split really splits (launch name), meets
+    the same bounds and repeats its bits."""
+    n = 320 if cfg in (5, 8) else 128
+    f32_store, row_bias = bool(i & 1), bool((i >> 1) & 1)
+    pr = gemm_problem(batch=2, Hi=72, c0=1152, N=n, flags=(EP_OUT_F32 if f32_store else 0) | (EP_BIAS_ROW if row_bias else 0),
+                      bias="row" if row_bias else "col", resid=True, alpha=0.5, seed=300)
+    runs = []
+    with knobs(gemm_cfg=cfg, gemm_split=split):
+        for _ in range(2):
+            runs.append(launch_gemm(abi, dev, pr, lda0=1160, ldo=n + 8, ldr=n + 16, a_gap=8, w_gap=16, o_gap=24, r_gap=32, workspace=True))
+    (got, names), (again, _) = runs
+    if cfg >= 0:
+        assert names[0].startswith("gemm_mfma_" + TILE_NAMES[cfg]), names
+        assert (f"_splitk{split}" in names[0]) == (split > 1), names
+    assert_gemm(got, pr, "long K, split-K", f"long K cfg {cfg} split {split} f32 {f32_store} row bias {row_bias} {names[0]}")
+    assert torch.equal(got.view(torch.int32 if f32_store else torch.int16), again.view(torch.int32 if f32_store else torch.int16))
+
+
+def test_conv_gemm_residual_without_a_batch_stride_is_a_broadcast(dev, abi):
+    """r_bs = 0 with batch > 1: every batch element adds the same residual (it is only read), like a_bs = 0."""
+    pr = gemm_problem(batch=2, Hi=72, c0=128, N=128, resid=True, shared_r=True, seed=350)
+    for impl in (0, 1):
+        got, names = launch_gemm(abi, dev, pr, ldo=136, ldr=144, o_gap=8, impl=impl)
+        assert_gemm(got, pr, "broadcast residual", f"r_bs = 0 impl {impl} {names[0]}")
+
+
+CONV_GEOMS = {"12x10": dict(Hi=12, Wi=10), "8x16": dict(Hi=8, Wi=16), "11x9s2": dict(Hi=11, Wi=9, stride=2), "6x5up": dict(Hi=6, Wi=5, up=1)}
+CONV_CASES = ([(g, f, -1) for g in ("12x10", "8x16") for f in ("default", "5", "8", "0", "mfma_reg", "generic")] +
+              [("8x16", f, 0) for f in ("5", "8")] + [(g, f, -1) for g in ("11x9s2", "6x5up") for f in ("default", "5", "0", "generic")])
+
+
+@pytest.mark.parametrize("geom,fam,korder", CONV_CASES, ids=[f"{g}-{f}" + ("-tapmajor" if k == 0 else "") for g, f, k in CONV_CASES])
+def test_conv_gemm_3x3_with_strided_sources(dev, abi, geom, fam, korder):
+    """batch 2 x B = 2 images, two sources of 64 channels read out of pixel rows of 96 and 72 elements, a residual in rows of ldr = N + 16,
+    a [B][N] row bias shared by the batch elements, fp16 rows of ldo = N + 8.  8 x 16 images: a 128- or 256-row tile is whole image rows,
+    so the ping-pong tiles take the row-shared (dx) walk unless conv_korder = 0 asks for the tap-major one."""
+    kn, impl, ran = family(fam)
+    n = n_for(fam, 128, 320)
+    pr = gemm_problem(taps=9, batch=2, B=2, c0=64, c1=64, N=n, bias="col", rowbias=True, resid=True, seed=400, **CONV_GEOMS[geom])
+    with knobs(conv_korder=korder, **kn):
+        got, names = launch_gemm(abi, dev, pr, lda0=96, lda1=72, ldo=n + 8, ldr=n + 16, a_gap=8, w_gap=16, o_gap=24, r_gap=40, impl=impl)
+    assert ran(names), (fam, names)
+    if fam in ("5", "8"):
+        assert ("_dx" in names[0]) == (geom == "8x16" and korder != 0), names
+    assert_gemm(got, pr, "3x3, strided sources", f"3x3 {geom} {fam} korder {korder} {names[0]}")
+
+
+@pytest.mark.parametrize("fam", ["default", "4", "generic"])
+def test_conv_gemm_geglu_rows_inside_wider_rows(dev, abi, fam):
+    kn, impl, ran = family(fam)
+    pr = gemm_problem(batch=2, Hi=200, c0=64, N=256, flags=EP_GEGLU, bias="col", seed=500)
+    with knobs(**kn):
+        got, names = launch_gemm(abi, dev, pr, lda0=72, ldo=128 + 8, a_gap=8, w_gap=8, o_gap=16, impl=impl)
+    assert ran(names) and (impl == 1 or "_geglu" in names[0]), (fam, names)
+    assert_gemm(got, pr, "GEGLU into wider rows", f"GEGLU {fam} {names[0]}")
+
+
+@pytest.mark.parametrize("fam", ["default", "4", "generic"])
+def test_conv_gemm_transposed_store_into_padded_rows(dev, abi, fam):
+    """EP_TRANSPOSE: out[b][n][token] in rows of ldo = 128 > Ho * Wo = 72 (a multiple of 64, as the attention kernel wants its padding)."""
+    kn, impl, ran = family(fam)
+    pr = gemm_problem(batch=2, B=2, Hi=72, c0=64, N=256, flags=EP_TRANSPOSE, bias="col", seed=510)
+    with knobs(**kn):
+        got, names = launch_gemm(abi, dev, pr, lda0=72, ldo=128, a_gap=8, w_gap=8, o_gap=64, impl=impl)
+    assert ran(names) and (impl == 1 or "_tr" in names[0]), (fam, names)
+    assert_gemm(got, pr, "transposed store into wider rows", f"transposed {fam} {names[0]}")
+
+
+@pytest.mark.parametrize("fam", ["default", "generic"])
+def test_conv_gemm_nchw_store_of_four_channels_per_batch_element(dev, abi, fam):
+    kn, impl, ran = family(fam)
+    pr = gemm_problem(taps=9, batch=2, B=2, Hi=9, Wi=7, c0=64, N=64, n_real=4, flags=EP_NCHW, bias="col", seed=520)
+    got, names = launch_gemm(abi, dev, pr, lda0=72, a_gap=8, w_gap=8, o_gap=12, impl=impl)
+    assert ran(names), (fam, names)
+    assert_gemm(got, pr, "NCHW store, n_real = 4", f"NCHW {fam} {names[0]}")
+
+
+@pytest.mark.parametrize("cfg", [-1, 5])
+@pytest.mark.parametrize("taps", [1, 9])
+def test_conv_gemm_wide_and_narrow_epilogues_store_the_same_bits(dev, abi, taps, cfg):
+    """ldo / ldr / o_bs / r_bs = 0 (mod 8) with 16-byte aligned bases takes the 16-byte epilogue; the strides = 4 (mod 8), or the output
+    and residual bases moved by 8 bytes, the 8-byte one ("_ep8" in the launch name).  Same arithmetic per element: same bits."""
+    n = 320 if cfg == 5 else 128
+    geom = dict(B=2, Hi=8, Wi=16) if taps == 9 else dict(Hi=200)
+    pr = gemm_problem(taps=taps, batch=2, c0=64, N=n, bias="col", resid=True, rowbias=taps == 9, seed=600, **geom)
+    res = []
+    with knobs(gemm_cfg=cfg):
+        wide = dict(ldo=n + 8, ldr=n + 16, o_gap=8, r_gap=16)              # M = 200 / 256: M * ld = 0 (mod 8), so the gaps decide the batch strides
+        for what, kw in (("0 mod 8", wide), ("4 mod 8", dict(ldo=n + 4, ldr=n + 12, o_gap=4, r_gap=12)),
+                         ("bases + 8 bytes", dict(wide, out_lead=LEAD + 4, resid_lead=LEAD + 4)),
+                         # each of the six conditions on its own sends the launch to the 8-byte epilogue
+                         ("ldo", dict(wide, ldo=n + 4)), ("ldr", dict(wide, ldr=n + 12)), ("o_bs", dict(wide, o_gap=4)), ("r_bs", dict(wide, r_gap=12)),
+                         ("out + 8 bytes", dict(wide, out_lead=LEAD + 4)), ("resid + 8 bytes", dict(wide, resid_lead=LEAD + 4))):
+            got, names = launch_gemm(abi, dev, pr, lda0=72, a_gap=8, w_gap=8, **kw)
+            assert names[0].startswith("gemm_mfma_") and ("_ep8" in names[0]) == (what != "0 mod 8"), (what, names)
+            assert_gemm(got, pr, "wide / narrow epilogue", f"epilogue {what} taps {taps} cfg {cfg} {names[0]}")
+            res.append(got.view(torch.int16))
+    assert all(torch.equal(res[0], r) for r in res[1:])
+
+
+@pytest.mark.parametrize("impl", [0, 1], ids=["mfma", "generic"])
+def test_conv_gemm_alpha_zero_means_one_and_negative_alpha(dev, abi, impl):
+    pr = gemm_problem(batch=2, Hi=72, c0=128, N=128, bias="col", alpha=1.0, seed=700)
+    one, _ = launch_gemm(abi, dev, pr, ldo=136, o_gap=8, impl=impl)
+    zero, _ = launch_gemm(abi, dev, pr, ldo=136, o_gap=8, impl=impl, alpha=0.0)
+    assert torch.equal(one.view(torch.int16), zero.view(torch.int16))
+    assert_gemm(one, pr, "alpha", f"alpha 0 = 1 impl {impl}")
+    neg = gemm_problem(batch=2, Hi=72, c0=128, N=128, bias="col", alpha=-1.75, seed=700)
+    got, names = launch_gemm(abi, dev, neg, ldo=136, o_gap=8, impl=impl)
+    assert_gemm(got, neg, "alpha", f"alpha -1.75 impl {impl} {names[0]}")
+
+
+def test_conv_gemm_takes_the_generic_kernel_for_a_batch_stride_off_16_bytes(dev, abi):
+    """a_bs = 4 (mod 8) elements: the second batch element's rows start 8 bytes off the 16-byte grid of the MFMA kernels' loads.  The launcher
+    hands the launch to the generic kernel, as it does for lda % 8 != 0; w_bs alike."""
+    pr = gemm_problem(batch=3, Hi=72, c0=128, N=128, bias="col", seed=800)
+    for what, kw in (("a_bs", dict(a_gap=4, w_gap=8)), ("w_bs", dict(a_gap=8, w_gap=4))):
+        got, names = launch_gemm(abi, dev, pr, lda0=136, ldo=136, o_gap=8, **kw)
+        assert names == ["gemm_generic"], (what, names)
+        assert_gemm(got, pr, "misaligned batch stride", f"{what} = 4 mod 8 {names[0]}")
+
+
+def test_conv_gemm_refusals(dev, abi):
+    """What sdmi_conv_desc's comment rules out is refused on the host: a non-zero return, a message, the guarded output untouched."""
+    L, check, ptr, sp = abi
+    lib = sub("_lib")
+    pr = gemm_problem(batch=2, Hi=72, c0=128, N=128, resid=True, seed=900)
+
+    def edit(message, **fields):
+        def apply(d):
+            for k, v in fields.items():
+                setattr(d, k, v(d) if callable(v) else v)
+        rc, out = launch_gemm(abi, dev, pr, ldo=136, ldr=144, o_gap=8, r_gap=8, edit=apply)
+        assert rc != 0, ("accepted", message, fields)
+        assert message in lib.last_error(), (message, lib.last_error())
+        out.geom = out.geom[:2] + (0,) + out.geom[3:]                # nothing may be stored: the whole buffer is sentinel
+        out.read(message)
+
+    for f in ("a0", "w", "out"):
+        edit("null", **{f: None})
+    for f in ("B", "Hi", "Wi", "Ho", "Wo", "N", "c0"):
+        edit("positive", **{f: 0})
+        edit("positive", **{f: -1})
+    edit("stride", stride=3)
+    edit("stride", stride=-1)
+    edit("taps", taps=3)
+    edit("ldo", ldo=127)
+    edit("ldr", ldr=127)
+    edit("multiples of 4", ldo=130)
+    edit("multiples of 4", ldr=130)
+    edit("multiples of 4", o_bs=lambda d: d.o_bs + 2)
+    edit("multiples of 4", r_bs=lambda d: d.r_bs + 2)
+    edit("aligned", out=lambda d: d.out + 2)
+    edit("aligned", resid=lambda d: d.resid + 4)
+    edit("o_bs", o_bs=0)
+    edit("o_bs", o_bs=71 * 136)
+    edit("n_real", n_real=129, flags=EP_NCHW)
+    edit("GEGLU", N=96, flags=EP_GEGLU, resid=None)
+    edit("multiple of 8", c0=124)
+    edit("lda smaller", lda0=120)
+    edit("positive", a1=lambda d: d.a0, c1=0)
+    edit("negative batch stride", a_bs=-8)
+
+
+PACK_CASES = [(dt, i, k) for dt in (torch.float16, torch.float32) for i in (4, 100) for k in (3, 1)]
+
+
+@pytest.mark.parametrize("dtype,cin,k", PACK_CASES, ids=[f"{str(c[0]).split('.')[1]}-I{c[1]}-{c[2]}x{c[2]}" for c in PACK_CASES])
+def test_pack_conv_weight_layout_bit_equal(dev, abi, dtype, cin, k):
+    """sdmi_pack_conv_weight against the documented layout [O_pad][ky * 3 + kx][I_pad] restated in numpy: O = 70 -> 128 rows, I = 4 -> 64
+    and 100 -> 128 channels, the padding exactly zero; with the GEGLU interleave (O = 128: 32 value rows, then their 32 gate rows)."""
+    L, check, ptr, sp = abi
+    lib = sub("_lib")
+    i_pad = (cin + 63) // 64 * 64
+    for o, geglu in ((70, 0), (128, 1)):
+        w = seeded((o, cin, k, k), 1000 + cin + k).to(dtype)
+        want = np.zeros((128, k * k, i_pad), dtype=np.float16)
+        src = w.numpy().astype(np.float16).transpose(0, 2, 3, 1).reshape(o, k * k, cin)
+        for row in range(o):
+            g, r = divmod(row, 64)
+            want[row, :, :cin] = src[(g * 32 + r if r < 32 else o // 2 + g * 32 + r - 32) if geglu else row]
+        out = Guarded((128, k * k, i_pad), torch.float16, dev, fill=OUT_FILL)
+        check(L.sdmi_pack_conv_weight(ptr(up(w, dev)), lib.dtype_code(w), ptr(out.t), o, cin, k, k, 128, i_pad, geglu, sp()))
+        torch.cuda.synchronize()
+        assert np.array_equal(out.t.cpu().numpy().view(np.int16), want.view(np.int16)), (o, geglu)
+        assert out.intact()
