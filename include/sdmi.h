@@ -561,6 +561,66 @@ int64_t sdmi_compact_scratch_bytes(sdmi_compact* h, int B, int H, int W);
 /* in / out as sdmi_esrgan_run: uint8 HWC or fp32 NCHW in, fp32 NCHW or uint8 HWC [B][H s][W s][3] out (device memory). */
 int sdmi_compact_run(sdmi_compact* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
 
+/* ---- SwinIR upscalers ---------------------------------------------------------------------------------------------------------------- */
+
+/* Shifted-window attention of one SwinTransformerBlock (csrc/swinir.hip), window size 8, head dim <= 32.  Replaces, in
+ * SwinTransformerBlock.forward (the webui's extensions-builtin/SwinIR/swinir_model_arch.py), `torch.roll(x, (-shift, -shift), (1, 2))`,
+ * `window_partition`, WindowAttention.forward between its qkv and proj linears (`q * scale @ k^T + relative_position_bias + mask`,
+ * softmax, `@ v`), `window_reverse` and the roll back: the roll and the partition are index arithmetic (a token is read from and
+ * written back to its own row), the mask (-100 between tokens of different regions of the shifted grid, applied when shift > 0) is
+ * computed, never stored.  Scores, bias, mask and softmax in fp32; the probabilities are rounded to fp16 for the second product.
+ * Refused (non-zero, message in sdmi_last_error, nothing written): null pointers; H or W not a positive multiple of 8; D outside 1..32;
+ * shift not 0 or 4; ldq < 96 heads; ldo < 32 heads; qkv / out / bias not 16-byte aligned, ldq or ldo not a multiple of 8. */
+typedef struct sdmi_swin_attn_desc {
+    const void* qkv;       /* fp16 token rows [B*H*W][ldq]: head h has q, k, v in 32-wide slots at columns h*32, (heads + h)*32,
+                              (2 heads + h)*32; dims 0 .. D-1 real, the tail of every slot zero */
+    const void* bias;      /* fp32 [heads][64][64]: bias[h][a][b] = table[(ya - yb + 7) * 15 + (xa - xb + 7)][h] for window-local tokens a, b */
+    void* out;             /* fp16 token rows [B*H*W][ldo]: head h at columns h*32, dims D .. 31 stored as zero; columns >= 32 heads untouched */
+    int32_t B, H, W;       /* the token grid (row-major rows) */
+    int32_t heads, D;
+    int32_t ldq, ldo;
+    int32_t shift;         /* 0 | 4 */
+    float scale;           /* D^-1/2 */
+} sdmi_swin_attn_desc;
+int sdmi_swin_attention(const sdmi_swin_attn_desc* d, void* stream);
+
+/* nn.LayerNorm(C) over the first C columns of fp16 rows of stride ld (norm1 / norm2 of a block, patch_embed.norm, the final norm): fp32
+ * statistics, centred variance.  The engine's token rows are C rounded up to 64 wide (the MFMA GEMMs read dense multiples of 64):
+ * columns C .. roundup(C, 64) - 1 of `out` are written as zeros.  gamma / beta fp32 [C].  Refused: null pointers, ld < roundup(C, 64),
+ * odd ld.  sdmi_layernorm (dense rows of C) is unchanged. */
+int sdmi_swin_layernorm(const void* x, const void* gamma, const void* beta, void* out, int64_t rows, int C, int ld, float eps, void* stream);
+
+/* A whole SwinIR network with the `nearest+conv` upsampler (the real-world SR models: SwinIR-L x4 GAN, the M models x4 / x2) held by an
+ * engine (scratch from the engine's arena).  Replaces the model call inside UpscalerSwinIR.do_upscale / `upscale` / `inference`
+ * (extensions-builtin/SwinIR/scripts/swinir_model.py), run on the image whole instead of in SWIN_tile tiles.  Fixed: window_size 8, head
+ * dim <= 32, 3 channels in / out, num_feat 64, img_range 1, scale 4 or 2.
+ * blob: host fp32, every tensor flattened, in this order (weight then bias for convs, linears and norms):
+ *   conv_first; patch_embed.norm;
+ *   per layer i, per block j: norm1, attn.relative_position_bias_table [225][heads], attn.qkv, attn.proj, norm2, mlp.fc1, mlp.fc2;
+ *     then the layer's conv (resi_3conv: conv.0, conv.2, conv.4);
+ *   norm; conv_after_body (resi_3conv: .0, .2, .4); conv_before_upsample.0; conv_up1; conv_up2 (scale 4 only); conv_hr; conv_last.
+ * sdmi_swinir_blob_floats gives its length (0 for a config the engine refuses).  NULL on error: a blob of another length,
+ * num_heads * 32 < embed_dim, embed_dim not a multiple of num_heads, embed_dim % 4 != 0 or embed_dim / 4 > 64 with resi_3conv,
+ * scale not 2 or 4, more than 16 layers. */
+typedef struct sdmi_swinir_config {
+    int32_t embed_dim;
+    int32_t num_layers;
+    int32_t depths[16];    /* blocks per layer (RSTB) */
+    int32_t num_heads;
+    int32_t mlp_hidden;    /* mlp_ratio * embed_dim */
+    int32_t resi_3conv;    /* 0: one 3x3 conv closes a layer; 1: 3x3 (C -> C/4), 1x1, 3x3 (C/4 -> C) with LeakyReLU(0.2) between */
+    int32_t scale;         /* 4 | 2 */
+} sdmi_swinir_config;
+typedef struct sdmi_swinir sdmi_swinir;
+int64_t sdmi_swinir_blob_floats(const sdmi_swinir_config* cfg);
+sdmi_swinir* sdmi_swinir_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_swinir_config* cfg);
+void sdmi_swinir_destroy(sdmi_swinir* h);
+/* arena bytes a run on B images of H x W needs (0 for a refused size) */
+int64_t sdmi_swinir_scratch_bytes(sdmi_swinir* h, int B, int H, int W);
+/* in / out as sdmi_esrgan_run: uint8 HWC or fp32 NCHW in, fp32 NCHW or uint8 HWC [B][H s][W s][3] out (device memory).  Any H, W >= 8: the
+ * image is reflect-padded to multiples of 8 on the way in and the output cropped.  Refused: a side below 8, tensors of 2^31 elements. */
+int sdmi_swinir_run(sdmi_swinir* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

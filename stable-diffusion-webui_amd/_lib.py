@@ -56,6 +56,19 @@ class CompactDesc(C.Structure):
     ]
 
 
+class SwinAttnDesc(C.Structure):
+    _fields_ = [
+        ("qkv", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("heads", C.c_int32), ("D", C.c_int32),
+        ("ldq", C.c_int32), ("ldo", C.c_int32), ("shift", C.c_int32), ("scale", C.c_float),
+    ]
+
+
+class SwinIRConfigC(C.Structure):
+    _fields_ = [("embed_dim", C.c_int32), ("num_layers", C.c_int32), ("depths", C.c_int32 * 16), ("num_heads", C.c_int32),
+                ("mlp_hidden", C.c_int32), ("resi_3conv", C.c_int32), ("scale", C.c_int32)]
+
+
 class UNetConfigC(C.Structure):
     _fields_ = [
         ("in_channels", C.c_int32), ("out_channels", C.c_int32), ("model_channels", C.c_int32),
@@ -180,6 +193,13 @@ _SIGS = {
     "sdmi_compact_destroy": (None, [_vp]),
     "sdmi_compact_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
     "sdmi_compact_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "sdmi_swin_attention": (_i, [C.POINTER(SwinAttnDesc), _vp]),
+    "sdmi_swin_layernorm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _f, _vp]),
+    "sdmi_swinir_blob_floats": (_i64, [C.POINTER(SwinIRConfigC)]),
+    "sdmi_swinir_create": (_vp, [_vp, _vp, _i64, C.POINTER(SwinIRConfigC)]),
+    "sdmi_swinir_destroy": (None, [_vp]),
+    "sdmi_swinir_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
+    "sdmi_swinir_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)       # AttributeError here == the .so does not export a declared symbol

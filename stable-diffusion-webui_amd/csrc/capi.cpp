@@ -34,6 +34,10 @@ int64_t compact_blob_floats(int num_conv, int scale);
 int compact_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_conv, int scale, sdmi_compact** out);
 int64_t compact_scratch_bytes(const sdmi_compact* n, int B, int H, int W);
 int compact_run(sdmi_compact* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
+int64_t swinir_blob_floats(const sdmi_swinir_config* cfg);
+int swinir_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swinir_config* cfg, sdmi_swinir** out);
+int64_t swinir_scratch_bytes(const sdmi_swinir* n, int B, int H, int W);
+int swinir_run(sdmi_swinir* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
 }  // namespace sdmi
 
 using namespace sdmi;
@@ -678,6 +682,45 @@ int64_t sdmi_compact_scratch_bytes(sdmi_compact* h, int B, int H, int W) { retur
 int sdmi_compact_run(sdmi_compact* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
     API_GUARD_BEGIN
     return compact_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_swin_attention(const sdmi_swin_attn_desc* d, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(d, "null descriptor");
+    SwinAttnP p{};
+    p.qkv = (const half_t*)d->qkv; p.bias = (const float*)d->bias; p.out = (half_t*)d->out;
+    p.B = d->B; p.H = d->H; p.W = d->W; p.heads = d->heads; p.D = d->D; p.ldq = d->ldq; p.ldo = d->ldo; p.shift = d->shift; p.scale = d->scale;
+    return launch_swin_attention(p, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_swin_layernorm(const void* x, const void* gamma, const void* beta, void* out, int64_t rows, int C, int ld, float eps, void* stream) {
+    API_GUARD_BEGIN
+    return launch_swin_layernorm((const half_t*)x, (const float*)gamma, (const float*)beta, (half_t*)out, rows, C, ld, eps, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int64_t sdmi_swinir_blob_floats(const sdmi_swinir_config* cfg) { return swinir_blob_floats(cfg); }
+
+sdmi_swinir* sdmi_swinir_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_swinir_config* cfg) {
+    try {
+        sdmi_swinir* n = nullptr;
+        if (swinir_create(e, (const float*)blob_f32, blob_floats, cfg, &n) != 0) return nullptr;
+        return n;
+    } catch (const std::exception& ex) {
+        set_error(std::string("exception: ") + ex.what());
+        return nullptr;
+    }
+}
+
+void sdmi_swinir_destroy(sdmi_swinir* h) { delete h; }
+
+int64_t sdmi_swinir_scratch_bytes(sdmi_swinir* h, int B, int H, int W) { return swinir_scratch_bytes(h, B, H, W); }
+
+int sdmi_swinir_run(sdmi_swinir* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
+    API_GUARD_BEGIN
+    return swinir_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
     API_GUARD_END
 }
 

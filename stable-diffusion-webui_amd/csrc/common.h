@@ -274,6 +274,27 @@ struct CompactP {
 };
 int launch_compact_conv(const CompactP& p, hipStream_t s);
 
+// ---- SwinIR: shifted-window attention, padded-row LayerNorm, input / output / activation passes (swinir.hip) --
+struct SwinAttnP {
+    const half_t* qkv;     // token rows [B*H*W][ldq]: head h has q / k / v in 32-wide slots at columns h*32, (heads + h)*32, (2 heads + h)*32;
+                           // dims 0 .. D-1 are real, the slot's tail is zero
+    const float* bias;     // [heads][64][64]: relative-position bias of (query, key) inside a window
+    half_t* out;           // token rows [B*H*W][ldo]: head h at columns h*32, dims D .. 31 stored as zero
+    int B, H, W;           // token grid; H, W multiples of the window size 8
+    int heads, D, ldq, ldo;
+    int shift;             // 0 | 4: cyclic shift of the window grid (with 4 the region mask is applied)
+    float scale;           // D^-1/2
+};
+int launch_swin_attention(const SwinAttnP& p, hipStream_t s);
+// LayerNorm over the first C columns of ld-wide rows (ld >= C rounded up to 64); the columns up to that width are written as zeros
+int launch_swin_layernorm(const half_t* x, const float* gamma, const float* beta, half_t* out, int64_t rows, int C, int ld, float eps,
+                          hipStream_t s);
+// RGB image (uint8 HWC / 255, or fp32 NCHW) -> reflect-padded to Hp x Wp, minus the mean -> NHWC fp16 rows of cpad channels
+int launch_swin_input(const void* in, int u8, half_t* out, int B, int H, int W, int Hp, int Wp, int cpad, hipStream_t s);
+int launch_swin_lrelu(half_t* x, int64_t n, float slope, hipStream_t s);               // in place
+// fp32 [B][3][Hp][Wp] cropped to H x W -> fp32 NCHW or (out_u8) uint8 HWC
+int launch_swin_output(const float* src, void* out, int out_u8, int B, int H, int W, int Hp, int Wp, hipStream_t s);
+
 // ---- norms ------------------------------------------------------------------------------------------------
 // pre_nchunk > 0: `ws` already holds (mean, M2) [B][pre_nchunk][groups][2] of HW / pre_nchunk rows each (written by the producing GEMM): skip the statistics pass
 // x0_lo / x1_lo (engine option "residual_fp32"): the lo parts when the inputs are (hi, lo) fp16 pairs of the carried stream

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 
 namespace sdmi {
 
@@ -2219,7 +2220,270 @@ int compact_run(sdmi_compact* n, const void* in, int in_u8, int B, int H, int W,
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// SwinIR upscalers (nearest+conv upsampler): SwinIR.forward as GEMM launches (gemm.hip), swin_window_attn / swin_layernorm (swinir.hip)
+// and the 64-channel tail on rrdb_conv (rrdb.hip)
+// ------------------------------------------------------------------------------------------------------------
+// blob: fp32, in the order include/sdmi.h documents at sdmi_swinir_config.
+static bool swinir_config_ok(const sdmi_swinir_config& c, std::string* why) {
+    auto fail = [&](const char* m) { if (why) *why = m; return false; };
+    if (c.embed_dim < 1 || c.num_heads < 1 || c.embed_dim % c.num_heads) return fail("embed_dim must be a positive multiple of num_heads");
+    if (c.num_heads * 32 < c.embed_dim) return fail("head dim = embed_dim / num_heads must be <= 32 (num_heads * 32 >= embed_dim)");
+    if (c.num_layers < 1 || c.num_layers > 16) return fail("num_layers in 1..16");
+    for (int i = 0; i < c.num_layers; ++i)
+        if (c.depths[i] < 1 || c.depths[i] > 64) return fail("depths[i] in 1..64");
+    if (c.mlp_hidden < 1) return fail("mlp_hidden");
+    if (c.scale != 2 && c.scale != 4) return fail("scale 4 (conv_up1, conv_up2) or 2 (conv_up1)");
+    if (c.resi_3conv != 0 && c.resi_3conv != 1) return fail("resi_3conv 0 | 1");
+    if (c.resi_3conv && (c.embed_dim % 4 || c.embed_dim / 4 > 64)) return fail("3conv: embed_dim / 4 must be an integer <= 64");
+    return true;
+}
+
+int64_t swinir_blob_floats(const sdmi_swinir_config* c) {
+    if (!c || !swinir_config_ok(*c, nullptr)) return 0;
+    const int64_t C = c->embed_dim, Hd = c->mlp_hidden, q = C / 4;
+    auto lin = [](int64_t o, int64_t i, int64_t taps = 1) { return o * i * taps + o; };
+    const int64_t resi = c->resi_3conv ? lin(q, C, 9) + lin(q, q) + lin(C, q, 9) : lin(C, C, 9);
+    const int64_t block = 2 * C + 225 * c->num_heads + lin(3 * C, C) + lin(C, C) + 2 * C + lin(Hd, C) + lin(C, Hd);
+    int64_t n = lin(C, 3, 9) + 2 * C;
+    for (int i = 0; i < c->num_layers; ++i) n += c->depths[i] * block + resi;
+    n += 2 * C + resi + lin(64, C, 9) + (c->scale == 4 ? 3 : 2) * lin(64, 64, 9) + lin(3, 64, 9);
+    return n;
+}
+
+int swinir_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swinir_config* cfg, sdmi_swinir** out) {
+    SDMI_REQUIRE(e && blob && cfg && out, "null argument");
+    std::string why;
+    SDMI_REQUIRE(swinir_config_ok(*cfg, &why), "SwinIR config: " + why);
+    SDMI_REQUIRE(blob_floats == swinir_blob_floats(cfg), "weight blob size does not match the config");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    std::unique_ptr<sdmi_swinir> net(new sdmi_swinir);
+    net->e = e; net->cfg = *cfg;
+    const int C = cfg->embed_dim, heads = cfg->num_heads, D = C / heads, Hd = cfg->mlp_hidden, Cq = C / 4;
+    const int Cp = rup(C, 64), hid_pad = rup(Hd, 64), ldq = rup(96 * heads, 64), lda = rup(32 * heads, 64);
+    net->C = C; net->Cp = Cp; net->D = D; net->ldq = ldq; net->lda = lda; net->hid_pad = hid_pad;
+    const float* src = blob;
+    auto upload = [&](const void* host, size_t bytes, void** dev) -> int {
+        SDMI_CHECK_HIP(hipMalloc(dev, std::max<size_t>(bytes, 256)));
+        net->owned.push_back(*dev);
+        SDMI_CHECK_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+        return 0;
+    };
+    // one conv / linear: OIHW weight then bias off the blob -> [n_pad][taps][cin_pad] fp16 + [n_pad] fp32, output row o at row_of(o),
+    // input channel i at col_of(i), everything else zero; bias_add: a constant per REAL output row (the output mean on conv_last)
+    auto ident = [](int v) { return v; };
+    auto pack = [&](ConvW* c, int O, int I, int taps, int n_pad, int cin_pad, const std::function<int(int)>& row_of,
+                    const std::function<int(int)>& col_of, const float* bias_add = nullptr) -> int {
+        std::vector<half_t> w((size_t)n_pad * taps * cin_pad, (half_t)0.f);
+        std::vector<float> b((size_t)n_pad, 0.f);
+        for (int o = 0; o < O; ++o)
+            for (int i = 0; i < I; ++i)
+                for (int t = 0; t < taps; ++t)
+                    w[((size_t)row_of(o) * taps + t) * cin_pad + col_of(i)] = (half_t)src[((size_t)o * I + i) * taps + t];
+        src += (size_t)O * I * taps;
+        for (int o = 0; o < O; ++o) b[(size_t)row_of(o)] = src[o] + (bias_add ? bias_add[o] : 0.f);
+        src += O;
+        c->cin = I; c->cin_pad = cin_pad; c->cout = O; c->n_pad = n_pad; c->taps = taps;
+        TRY(upload(w.data(), w.size() * sizeof(half_t), (void**)&c->w));
+        return upload(b.data(), b.size() * sizeof(float), (void**)&c->b);
+    };
+    auto norm = [&](NormW* n) -> int {
+        n->c = C;
+        TRY(upload(src, (size_t)C * sizeof(float), (void**)&n->g));
+        TRY(upload(src + C, (size_t)C * sizeof(float), (void**)&n->b));
+        src += 2 * C;
+        return 0;
+    };
+    // the conv that closes a layer / the trunk: 1conv, or 3conv with C / 4 padded to 64
+    auto resi = [&](ConvW* c) -> int {
+        if (!cfg->resi_3conv) return pack(&c[0], C, C, 9, Cp, Cp, ident, ident);
+        TRY(pack(&c[0], Cq, C, 9, 64, Cp, ident, ident));
+        TRY(pack(&c[1], Cq, Cq, 1, 64, 64, ident, ident));
+        return pack(&c[2], C, Cq, 9, Cp, 64, ident, ident);
+    };
+    auto slot = [&](int v) { return (v / D) * 32 + v % D; };          // feature h * D + d -> column h * 32 + d
+
+    TRY(pack(&net->first, C, 3, 9, Cp, 64, ident, ident));
+    TRY(norm(&net->pe_norm));
+    net->layers.resize((size_t)cfg->num_layers);
+    std::vector<float> bias((size_t)heads * 4096);
+    for (int i = 0; i < cfg->num_layers; ++i) {
+        sdmi_swinir::Layer& L = net->layers[(size_t)i];
+        L.blocks.resize((size_t)cfg->depths[i]);
+        for (sdmi_swinir::Block& bk : L.blocks) {
+            TRY(norm(&bk.n1));
+            for (int h = 0; h < heads; ++h)                            // bias[h][a][b] = table[(ya - yb + 7) * 15 + (xa - xb + 7)][h]
+                for (int a = 0; a < 64; ++a)
+                    for (int b = 0; b < 64; ++b)
+                        bias[((size_t)h * 64 + a) * 64 + b] = src[(size_t)(((a >> 3) - (b >> 3) + 7) * 15 + ((a & 7) - (b & 7) + 7)) * heads + h];
+            src += 225 * heads;
+            TRY(upload(bias.data(), bias.size() * sizeof(float), (void**)&bk.bias));
+            TRY(pack(&bk.qkv, 3 * C, C, 1, ldq, Cp, [&](int o) { return (o / C) * heads * 32 + slot(o % C); }, ident));
+            TRY(pack(&bk.proj, C, C, 1, Cp, lda, ident, slot));
+            TRY(norm(&bk.n2));
+            TRY(pack(&bk.fc1, Hd, C, 1, hid_pad, Cp, ident, ident));
+            TRY(pack(&bk.fc2, C, Hd, 1, Cp, hid_pad, ident, ident));
+        }
+        TRY(resi(L.conv));
+    }
+    TRY(norm(&net->norm));
+    TRY(resi(net->after));
+    TRY(pack(&net->before, 64, C, 9, 64, Cp, ident, ident));
+    TRY(pack(&net->up1, 64, 64, 9, 64, 64, ident, ident));
+    if (cfg->scale == 4) TRY(pack(&net->up2, 64, 64, 9, 64, 64, ident, ident));
+    TRY(pack(&net->hr, 64, 64, 9, 64, 64, ident, ident));
+    const float mean[3] = {0.4488f, 0.4371f, 0.4040f};                 // y / img_range + mean folds into conv_last's bias
+    TRY(pack(&net->last, 3, 64, 9, 32, 64, ident, ident, mean));
+    SDMI_REQUIRE(src - blob == blob_floats, "internal: blob walk does not end at its length");
+    SDMI_CHECK_HIP(hipDeviceSynchronize());
+    *out = net.release();
+    return 0;
+}
+
+// One pass over the network (dry: the arena layout alone).  M tokens = B * Hp * Wp on the padded grid; every token tensor is Cp wide with
+// zeros in columns C .. Cp - 1 (zero weight rows / bias entries and swin_layernorm keep them so).
+static int swinir_pass(Run& r, const sdmi_swinir& n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8) {
+    const int Hp = rup(H, 8), Wp = rup(W, 8), sc = n.cfg.scale, Cp = n.Cp;
+    const size_t M = (size_t)B * Hp * Wp;
+    r.ar->reset();
+    half_t* x0 = r.H(M * 64);                                 // the padded, mean-subtracted input
+    half_t* feat = r.H(M * Cp);                               // conv_first's output: the trunk's skip tensor
+    half_t* pool[4];                                          // token tensors: a layer's input and the blocks' ping-pong
+    for (half_t*& p : pool) p = r.H(M * Cp);
+    half_t* ln = r.H(M * Cp);
+    half_t* qkv = r.H(M * n.ldq);
+    half_t* att = r.H(M * n.lda);
+    half_t* hid = r.H(M * n.hid_pad);
+    half_t* c1 = r.H(M * 64);
+    half_t* c2 = r.H(M * 64);
+    half_t* up[3] = {r.H(M * 4 * 64), sc == 4 ? r.H(M * 16 * 64) : nullptr, r.H(M * sc * sc * 64)};
+    float* full = r.F(M * sc * sc * 3);                       // conv_last on the padded grid, cropped by swin_output
+
+    auto conv = [&](const ConvW& w, const half_t* a, const half_t* resid, half_t* o, int flags = 0) -> int {      // 3x3 pad 1 / 1x1 / linear
+        ConvArgs c;
+        c.a0 = a; c.c0 = w.cin_pad; c.B = B; c.Hi = c.Ho = Hp; c.Wi = c.Wo = Wp; c.pad = w.taps == 9 ? 1 : 0;
+        c.resid = resid; c.ldr = w.n_pad; c.out = o; c.ldo = w.n_pad; c.flags = flags;
+        const size_t mark = r.ar->mark();                     // a split-K workspace lives for its launch only
+        const int rc = run_conv(r, w, c);
+        r.ar->rewind(mark);
+        return rc;
+    };
+    auto lnorm = [&](const NormW& w, const half_t* a, half_t* o) -> int {
+        return r.dry ? 0 : launch_swin_layernorm(a, w.g, w.b, o, (int64_t)M, n.C, Cp, 1e-5f, r.s);
+    };
+    auto lrelu = [&](half_t* a, size_t cnt, float slope) -> int { return r.dry ? 0 : launch_swin_lrelu(a, (int64_t)cnt, slope, r.s); };
+    // conv(x) + resid with the layer-closing conv (1conv | 3conv)
+    auto resi = [&](const ConvW* w, const half_t* a, const half_t* resid, half_t* o) -> int {
+        if (!n.cfg.resi_3conv) return conv(w[0], a, resid, o);
+        TRY(conv(w[0], a, nullptr, c1));
+        TRY(lrelu(c1, M * 64, 0.2f));
+        TRY(conv(w[1], c1, nullptr, c2));
+        TRY(lrelu(c2, M * 64, 0.2f));
+        return conv(w[2], c2, resid, o);
+    };
+
+    if (!r.dry) {
+        TRY(launch_swin_input(in, in_u8, x0, B, H, W, Hp, Wp, 64, r.s));
+        if (n.lda > 32 * n.cfg.num_heads)                     // an odd head count: proj reads 32 columns the attention never writes (zero weights, but not NaN x 0)
+            SDMI_CHECK_HIP(hipMemsetAsync(att, 0, M * n.lda * sizeof(half_t), r.s));
+    }
+    TRY(conv(n.first, x0, nullptr, feat));
+    half_t* x = pool[0];
+    std::vector<half_t*> free_ = {pool[1], pool[2], pool[3]};
+    TRY(lnorm(n.pe_norm, feat, x));
+    for (const sdmi_swinir::Layer& L : n.layers) {
+        half_t* cur = x;
+        for (size_t j = 0; j < L.blocks.size(); ++j) {
+            const sdmi_swinir::Block& bk = L.blocks[j];
+            half_t* mid = free_.back(); free_.pop_back();
+            half_t* nxt = free_.back(); free_.pop_back();
+            TRY(lnorm(bk.n1, cur, ln));
+            TRY(conv(bk.qkv, ln, nullptr, qkv));
+            if (!r.dry) {
+                SwinAttnP a{};
+                a.qkv = qkv; a.bias = bk.bias; a.out = att; a.B = B; a.H = Hp; a.W = Wp; a.heads = n.cfg.num_heads; a.D = n.D;
+                a.ldq = n.ldq; a.ldo = n.lda; a.shift = (j & 1) ? 4 : 0; a.scale = 1.0f / sqrtf((float)n.D);
+                TRY(launch_swin_attention(a, r.s));
+            }
+            TRY(conv(bk.proj, att, cur, mid));
+            TRY(lnorm(bk.n2, mid, ln));
+            TRY(conv(bk.fc1, ln, nullptr, hid, EP_GELU));
+            TRY(conv(bk.fc2, hid, mid, nxt));
+            free_.push_back(mid);
+            if (cur != x) free_.push_back(cur);
+            cur = nxt;
+        }
+        half_t* y = free_.back(); free_.pop_back();
+        TRY(resi(L.conv, cur, x, y));
+        free_.push_back(x);
+        if (cur != x) free_.push_back(cur);
+        x = y;
+    }
+    TRY(lnorm(n.norm, x, ln));
+    half_t* trunk = free_.back();
+    TRY(resi(n.after, ln, feat, trunk));
+    TRY(conv(n.before, trunk, nullptr, c1));
+    TRY(lrelu(c1, M * 64, 0.01f));
+    if (r.dry) return 0;
+
+    auto tail = [&](const ConvW& w, const half_t* src, int hh, int ww, int upf, void* dst, int store) -> int {
+        RrdbP p{};
+        p.in = src; p.w = w.w; p.bias = w.b; p.out = dst;
+        p.B = B; p.H = hh; p.W = ww; p.cin = 64; p.lda = 64; p.up = upf;
+        p.ldo = store == RRDB_ST_F16 ? 64 : 0; p.n_real = w.cout; p.ep = store == RRDB_ST_F16 ? RRDB_EP_LRELU : RRDB_EP_NONE; p.store = store;
+        p.alpha = 1.f; p.beta = 1.f;
+        return launch_rrdb_conv(p, w.n_pad, r.s);
+    };
+    TRY(tail(n.up1, c1, 2 * Hp, 2 * Wp, 1, up[0], RRDB_ST_F16));
+    const half_t* t = up[0];
+    if (sc == 4) { TRY(tail(n.up2, t, 4 * Hp, 4 * Wp, 1, up[1], RRDB_ST_F16)); t = up[1]; }
+    TRY(tail(n.hr, t, sc * Hp, sc * Wp, 0, up[2], RRDB_ST_F16));
+    TRY(tail(n.last, up[2], sc * Hp, sc * Wp, 0, full, RRDB_ST_F32_NCHW));
+    return launch_swin_output(full, out, out_u8, B, H * sc, W * sc, Hp * sc, Wp * sc, r.s);
+}
+
+static bool swinir_size_ok(const sdmi_swinir& n, int B, int H, int W) {
+    if (B <= 0 || H < 8 || W < 8) return false;
+    const long long M = (long long)B * rup(H, 8) * rup(W, 8);
+    const long long widest = std::max<long long>({(long long)n.ldq, (long long)n.hid_pad, (long long)n.Cp, 64ll * n.cfg.scale * n.cfg.scale});
+    return M * widest < (1ll << 31) - 256;
+}
+
+int64_t swinir_scratch_bytes(const sdmi_swinir* n, int B, int H, int W) {
+    if (!n || !swinir_size_ok(*n, B, H, W)) return 0;
+    Arena ar;
+    ar.dry = true;
+    Run dry(n->e, nullptr, true, &ar);
+    if (swinir_pass(dry, *n, nullptr, 0, B, H, W, nullptr, 0) != 0) return 0;
+    return (int64_t)ar.high;
+}
+
+// in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
+// out: [B][3][H s][W s] fp32 NCHW, or (out_u8) uint8 HWC [B][H s][W s][3] = round_half_even(clamp(y, 0, 1) * 255).
+int swinir_run(sdmi_swinir* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s) {
+    SDMI_REQUIRE(n && in && out, "null argument");
+    sdmi_engine* e = n->e;
+    SDMI_REQUIRE(B > 0 && H >= 8 && W >= 8, "image sides must be at least 8 (a smaller side cannot be reflect-padded to a window)");
+    SDMI_REQUIRE(swinir_size_ok(*n, B, H, W), "image too large: every intermediate tensor must stay below 2^31 elements");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    const bool tiling = e->tiling;                            // p.tiling belongs to the diffusion model's convs, not to an upscaler's
+    e->tiling = false;
+    struct Restore { sdmi_engine* e; bool v; ~Restore() { e->tiling = v; } } restore{e, tiling};
+    Run dry{e, s, true};
+    e->arena.dry = true; e->arena.high = 0;
+    const int rc = swinir_pass(dry, *n, in, in_u8, B, H, W, out, out_u8);
+    e->arena.dry = false;
+    TRY(rc);
+    TRY(ensure_arena(e, e->arena.high, s));
+    Run run{e, s, false};
+    return swinir_pass(run, *n, in, in_u8, B, H, W, out, out_u8);
+}
+
 }  // namespace sdmi
+
+sdmi_swinir::~sdmi_swinir() {
+    for (void* p : owned) (void)hipFree(p);
+}
 
 sdmi_compact::~sdmi_compact() {
     for (void* p : owned) (void)hipFree(p);
@@ -2249,8 +2513,9 @@ sdmi_engine::~sdmi_engine() {
 }
 
 // The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units; there the upscalers'
-// kernel files travel inside this one.  The GPU build compiles rrdb.hip and compact.hip on their own (build.sh).
+// kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip and swinir.hip on their own (build.sh).
 #ifndef __HIP__
 #include "rrdb.hip"
 #include "compact.hip"
+#include "swinir.hip"
 #endif

@@ -267,3 +267,26 @@ struct sdmi_compact {
     std::vector<void*> owned;
     ~sdmi_compact();
 };
+
+// SwinIR upscaler (nearest+conv upsampler): packed weights of the GEMM launches (linears and trunk convs, rows / columns padded to
+// multiples of 64, qkv / proj permuted into 32-wide head slots), the expanded relative-position bias of every block, and the 64-channel
+// tail as rrdb_conv weights.  Activations come from the owning engine's arena; the net is immutable after sdmi_swinir_create.
+struct sdmi_swinir {
+    struct Block {
+        sdmi::NormW n1, n2;
+        sdmi::ConvW qkv, proj, fc1, fc2;
+        float* bias = nullptr;                // [heads][64][64]
+    };
+    struct Layer {
+        std::vector<Block> blocks;
+        sdmi::ConvW conv[3];                  // 1conv: conv[0]; 3conv: 3x3 (C -> C/4), 1x1, 3x3 (C/4 -> C)
+    };
+    sdmi_engine* e = nullptr;
+    sdmi_swinir_config cfg{};
+    int C = 0, Cp = 0, D = 0, ldq = 0, lda = 0, hid_pad = 0;      // lda: row width of the attention output (32 heads rounded up to 64)
+    sdmi::ConvW first, after[3], before, up1, up2, hr, last;
+    sdmi::NormW pe_norm, norm;
+    std::vector<Layer> layers;
+    std::vector<void*> owned;
+    ~sdmi_swinir();
+};

@@ -373,3 +373,41 @@ def compact_conv(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.T
         d.out, d.ldo = out.data_ptr(), out.shape[3]
     check(lib.sdmi_compact_conv(C.byref(d), stream_ptr()), "sdmi_compact_conv")
     return out
+
+
+def swin_attention(qkv: torch.Tensor, bias: torch.Tensor, heads: int, d: int, shift: int = 0, scale: Optional[float] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Shifted-window attention of a SwinIR block (csrc/swinir.hip; window 8, head dim d <= 32): the roll, the window partition, the
+    relative-position bias, the shift mask, softmax and the product with v of SwinTransformerBlock.forward / WindowAttention.forward
+    between the qkv and proj linears.  qkv fp16 [B, H, W, ldq]: head h has q / k / v in 32-wide slots at columns h*32, (heads + h)*32,
+    (2 heads + h)*32, dims d..31 zero; bias fp32 [heads, 64, 64]; shift 0 | 4 -> fp16 [B, H, W, ldo] (ldo = 32 heads, or `out`'s row
+    width: columns past 32 heads keep their bits), head h at columns h*32 with dims d..31 zero."""
+    _lib.require_device()
+    assert qkv.dtype == torch.float16 and qkv.dim() == 4 and qkv.is_contiguous()
+    b, h, w, ldq = qkv.shape
+    bias = bias.float().contiguous()
+    assert tuple(bias.shape) == (heads, 64, 64)
+    if out is None:
+        out = torch.empty((b, h, w, 32 * heads), dtype=torch.float16, device=qkv.device)
+    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape[:3]) == (b, h, w)
+    desc = _lib.SwinAttnDesc()
+    desc.qkv, desc.bias, desc.out = qkv.data_ptr(), bias.data_ptr(), out.data_ptr()
+    desc.B, desc.H, desc.W, desc.heads, desc.D = b, h, w, heads, d
+    desc.ldq, desc.ldo, desc.shift, desc.scale = ldq, out.shape[3], shift, float(d ** -0.5 if scale is None else scale)
+    check(lib.sdmi_swin_attention(C.byref(desc), stream_ptr()), "sdmi_swin_attention")
+    return out
+
+
+def swin_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LayerNorm over the first C = len(gamma) columns of fp16 rows [..., ld] (ld >= C rounded up to 64): columns C .. roundup(C, 64) - 1
+    of the result are zeros (the engine's padded token rows, csrc/swinir.hip); columns past that keep `out`'s bits."""
+    _lib.require_device()
+    assert x.dtype == torch.float16 and x.is_contiguous()
+    c, ld = gamma.numel(), x.shape[-1]
+    if out is None:
+        out = torch.zeros_like(x)
+    assert out.dtype == torch.float16 and out.is_contiguous() and out.shape == x.shape
+    check(lib.sdmi_swin_layernorm(ptr(x), ptr(gamma.float().contiguous()), ptr(beta.float().contiguous()), ptr(out), x.numel() // ld, c, ld,
+                                  float(eps), stream_ptr()), "sdmi_swin_layernorm")
+    return out

@@ -5,8 +5,9 @@ the seam: the registry ``shared.sd_upscalers`` of ``UpscalerData(name, path, sca
 up in (modules/images.py:276, modules/modelloader.py:136), the ``Upscaler.upscale`` driver loop (modules/upscaler.py:54-76) and
 the three built-in PIL scalers (None / Lanczos / Nearest, modules/upscaler.py:107-154).  The RRDBNet family (ESRGAN, Real-ESRGAN) and the
 compact Real-ESRGAN models (SRVGGNetCompact: General 4xV3, General WDN 4xV3, AnimeVideo) run on the engine (``UpscalerESRGAN`` /
-``register_esrgan`` below, csrc/rrdb.hip and csrc/compact.hip); other model upscalers (SwinIR, ...) register their own
-``UpscalerData`` whose ``scaler.upscale(img, scale, path)`` is called as in the reference.
+``register_esrgan`` below, csrc/rrdb.hip and csrc/compact.hip), and so do the SwinIR models with the nearest+conv upsampler
+(``SwinIRNet``, csrc/swinir.hip); other model upscalers register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)``
+is called as in the reference.
 """
 from __future__ import annotations
 
@@ -217,19 +218,110 @@ def parse_compact_state_dict(sd):
     return np.ascontiguousarray(np.concatenate(parts)), num_conv, scale
 
 
+SWINIR_MARK = "layers.0.residual_group.blocks.0.attn.qkv.weight"
+
+
+def parse_swinir_state_dict(sd):
+    """Checkpoint state dict of a SwinIR network with the nearest+conv upsampler (the real-world SR models: SwinIR-L x4 GAN, the M
+    models x4 / x2) -> (blob, config): the engine's weight blob (fp32, every tensor flattened in the order include/sdmi.h documents at
+    sdmi_swinir_config: conv_first; patch_embed.norm; per layer its blocks' norm1, relative_position_bias_table, qkv, proj, norm2, fc1,
+    fc2, then the layer's conv(s); norm; conv_after_body; conv_before_upsample.0; conv_up1; conv_up2 (x4); conv_hr; conv_last — weight
+    then bias) and config = dict(embed_dim, depths, num_heads, mlp_hidden, resi_3conv, scale), all read from the checkpoint.  The
+    buffers relative_position_index / attn_mask are ignored.  Host only.  Raises ValueError on what the engine's kernels are not built
+    for: another upsampler, window size, head dim > 32, ape, other channel counts."""
+    sd = _unwrap_state_dict(sd)
+    if SWINIR_MARK not in sd or "conv_first.weight" not in sd:
+        raise ValueError(f"not a SwinIR checkpoint: no {SWINIR_MARK}")
+    if "absolute_pos_embed" in sd:
+        raise ValueError("SwinIR with ape (absolute_pos_embed): the engine runs the models without it")
+    if "conv_before_upsample.0.weight" not in sd or "conv_up1.weight" not in sd or "conv_hr.weight" not in sd:
+        kind = ("pixelshuffle" if "upsample.0.weight" in sd and "conv_before_upsample.0.weight" in sd
+                else "pixelshuffledirect" if "upsample.0.weight" in sd else "none")
+        raise ValueError(f"SwinIR upsampler '{kind}': the engine runs the nearest+conv upsampler only (conv_before_upsample.0, conv_up1, conv_hr)")
+    c, in_ch = int(sd["conv_first.weight"].shape[0]), int(sd["conv_first.weight"].shape[1])
+    if in_ch != 3 or tuple(sd["conv_first.weight"].shape[2:]) != (3, 3):
+        raise ValueError(f"SwinIR conv_first takes {in_ch} input channels: expected 3")
+    layers = sorted({int(m.group(1)) for k in sd for m in [re.match(r"layers\.(\d+)\.residual_group\.blocks\.0\.attn\.qkv\.weight$", k)] if m})
+    if layers != list(range(len(layers))) or len(layers) > 16:
+        raise ValueError(f"SwinIR layers are not 0..n-1 with n <= 16: {layers}")
+    depths = []
+    for i in layers:
+        blocks = sorted({int(m.group(1)) for k in sd for m in [re.match(rf"layers\.{i}\.residual_group\.blocks\.(\d+)\.attn\.qkv\.weight$", k)] if m})
+        if blocks != list(range(len(blocks))):
+            raise ValueError(f"SwinIR layers.{i}: blocks are not 0..n-1: {blocks}")
+        depths.append(len(blocks))
+    b0 = "layers.0.residual_group.blocks.0."
+    table = sd.get(b0 + "attn.relative_position_bias_table")
+    if table is None or len(table.shape) != 2:
+        raise ValueError(f"SwinIR checkpoint lacks {b0}attn.relative_position_bias_table")
+    heads = int(table.shape[1])
+    if int(table.shape[0]) != 225:
+        w = (int(round(int(table.shape[0]) ** 0.5)) + 1) // 2
+        raise ValueError(f"SwinIR window_size {w} (a {int(table.shape[0])}-row bias table): the engine's attention kernel is built for 8 (225 rows)")
+    if c % heads or c // heads > 32:
+        raise ValueError(f"SwinIR head_dim = {c}/{heads} = {c / heads:g}: the engine's attention kernel is built for head_dim <= 32")
+    if b0 + "mlp.fc1.weight" not in sd:
+        raise ValueError(f"SwinIR checkpoint lacks {b0}mlp.fc1.weight")
+    hidden = int(sd[b0 + "mlp.fc1.weight"].shape[0])
+    resi3 = "layers.0.conv.0.weight" in sd
+    if not resi3 and "layers.0.conv.weight" not in sd:
+        raise ValueError("SwinIR checkpoint lacks layers.0.conv (.weight for 1conv, .0 / .2 / .4 for 3conv)")
+    if resi3 and (c % 4 or c // 4 > 64):
+        raise ValueError(f"SwinIR 3conv with embed_dim {c}: the engine packs embed_dim / 4 <= 64 channels")
+    if int(sd["conv_before_upsample.0.weight"].shape[0]) != 64:
+        raise ValueError(f"SwinIR num_feat = {int(sd['conv_before_upsample.0.weight'].shape[0])}: the engine's tail kernel is built for 64")
+    if int(sd["conv_last.weight"].shape[0]) != 3:
+        raise ValueError(f"SwinIR conv_last writes {int(sd['conv_last.weight'].shape[0])} channels: expected 3")
+    scale = 4 if "conv_up2.weight" in sd else 2
+    q = c // 4
+    resi = (lambda stem: [(stem + ".0", (q, c, 3, 3)), (stem + ".2", (q, q, 1, 1)), (stem + ".4", (c, q, 3, 3))]) if resi3 \
+        else (lambda stem: [(stem, (c, c, 3, 3))])
+    want = [("conv_first", (c, 3, 3, 3)), ("patch_embed.norm", (c,))]
+    for i, depth in enumerate(depths):
+        for j in range(depth):
+            b = f"layers.{i}.residual_group.blocks.{j}."
+            want += [(b + "norm1", (c,)), (b + "attn.relative_position_bias_table", (225, heads)), (b + "attn.qkv", (3 * c, c)),
+                     (b + "attn.proj", (c, c)), (b + "norm2", (c,)), (b + "mlp.fc1", (hidden, c)), (b + "mlp.fc2", (c, hidden))]
+        want += resi(f"layers.{i}.conv")
+    want += [("norm", (c,))] + resi("conv_after_body") + [("conv_before_upsample.0", (64, c, 3, 3)), ("conv_up1", (64, 64, 3, 3))]
+    want += ([("conv_up2", (64, 64, 3, 3))] if scale == 4 else []) + [("conv_hr", (64, 64, 3, 3)), ("conv_last", (3, 64, 3, 3))]
+    parts = []
+    for name, shape in want:
+        if name.endswith("relative_position_bias_table"):
+            t = sd.get(name)
+            if t is None or tuple(t.shape) != shape:
+                raise ValueError(f"SwinIR {name}: {None if t is None else tuple(t.shape)}, expected {shape}")
+            parts.append(_as_f32(t))
+            continue
+        w, b = sd.get(name + ".weight"), sd.get(name + ".bias")
+        if w is None or b is None:
+            raise ValueError(f"SwinIR checkpoint lacks {name}.{'weight' if w is None else 'bias'}")
+        if tuple(w.shape) != shape or tuple(b.shape) != (shape[0],):
+            raise ValueError(f"SwinIR {name}: weight {tuple(w.shape)}, expected {shape}")
+        parts += [_as_f32(w), _as_f32(b)]
+    config = dict(embed_dim=c, depths=tuple(depths), num_heads=heads, mlp_hidden=hidden, resi_3conv=int(resi3), scale=scale)
+    return np.ascontiguousarray(np.concatenate(parts)), config
+
+
 def upscaler_family(sd):
-    """"rrdb" | "compact" by the key layout: conv_first.weight / model.0.weight mark an RRDBNet, a 4-d body.0.weight without them a
-    compact network.  Anything else counts as "rrdb" and gets that loader's refusal."""
+    """"rrdb" | "compact" | "swinir" by the key layout: the first block's attn.qkv.weight marks a SwinIR network (it has a conv_first.weight
+    too, so this test comes first); conv_first.weight / model.0.weight mark an RRDBNet, a 4-d body.0.weight without them a compact
+    network.  Anything else counts as "rrdb" and gets that loader's refusal."""
     keys = _unwrap_state_dict(sd)
+    if SWINIR_MARK in keys:
+        return "swinir"
     if "conv_first.weight" not in keys and "model.0.weight" not in keys and len(getattr(keys.get("body.0.weight"), "shape", ())) == 4:
         return "compact"
     return "rrdb"
 
 
 def parse_upscaler_state_dict(sd):
-    """The dispatcher over the checkpoints the engine runs -> ("rrdb", parse_esrgan_state_dict(sd)) or
-    ("compact", parse_compact_state_dict(sd)); the scale is the last member of either tuple."""
+    """The dispatcher over the checkpoints the engine runs -> ("rrdb", parse_esrgan_state_dict(sd)), ("compact",
+    parse_compact_state_dict(sd)) or ("swinir", (blob, config, scale)); the scale is the last member of each tuple."""
     family = upscaler_family(sd)
+    if family == "swinir":
+        blob, config = parse_swinir_state_dict(sd)
+        return family, (blob, config, config["scale"])
     return family, (parse_compact_state_dict if family == "compact" else parse_esrgan_state_dict)(sd)
 
 
@@ -374,16 +466,88 @@ class CompactNet:
         return out
 
 
+class SwinIRNet:
+    """One SwinIR network (nearest+conv upsampler) resident on an engine (sdmi_swinir_*): the twin of EsrganNet."""
+
+    def __init__(self, state_dict, device=0, engine=None):
+        from . import _lib
+        from .engine import Engine
+        blob, self.config = parse_swinir_state_dict(state_dict)
+        self.scale = self.config["scale"]
+        self.device = int(device)
+        self.engine = engine or Engine(self.device)
+        cfg = _lib.SwinIRConfigC()
+        cfg.embed_dim, cfg.num_layers, cfg.num_heads = self.config["embed_dim"], len(self.config["depths"]), self.config["num_heads"]
+        cfg.mlp_hidden, cfg.resi_3conv, cfg.scale = self.config["mlp_hidden"], self.config["resi_3conv"], self.scale
+        for i, d in enumerate(self.config["depths"]):
+            cfg.depths[i] = d
+        import ctypes
+        self.handle = _lib.lib.sdmi_swinir_create(self.engine.handle, blob.ctypes.data, blob.size, ctypes.byref(cfg))
+        if not self.handle:
+            raise _lib.SdmiError("sdmi_swinir_create failed: " + _lib.last_error())
+
+    def close(self):
+        if getattr(self, "handle", None):
+            from . import _lib
+            _lib.lib.sdmi_swinir_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def scratch_bytes(self, b, h, w):
+        """Arena bytes of one run, from the engine's own layout (sdmi_swinir_scratch_bytes; 0 for a size the engine refuses)."""
+        from . import _lib
+        return int(_lib.lib.sdmi_swinir_scratch_bytes(self.handle, b, h, w))
+
+    def check_fits(self, b, h, w):
+        """Refuse an input whose intermediates (token tensors of the padded grid, the qkv and MLP rows, the (H s) x (W s) x 64 tail) the
+        arena cannot hold, or one of whose tensors passes 2^31 elements."""
+        if min(h, w) < 8:
+            raise ValueError(f"image {w}x{h}: SwinIR needs sides of at least 8 (one window)")
+        need = self.scratch_bytes(b, h, w)
+        limit = arena_limit_bytes(self.device) + self.engine.arena_bytes()
+        if need <= 0 or need > limit:
+            raise EsrganInputTooLarge(f"image {w}x{h} (batch {b}) is too large for the x{self.scale} upscaler: its intermediates need "
+                                      f"{need / 2 ** 30:.1f} GiB of engine arena, {limit / 2 ** 30:.1f} GiB are available"
+                                      if need > 0 else
+                                      f"image {w}x{h} (batch {b}) is too large for the x{self.scale} upscaler: a tensor passes 2^31 elements")
+
+    def run(self, x, out_u8=False):
+        """x: uint8 [B,H,W,3] (RGB; divided by 255 on the way in) or fp32 [B,3,H,W] in [0, 1], on the engine's device ->
+        fp32 [B,3,H s,W s], or with out_u8 uint8 [B,H s,W s,3] (clamp, x255, round half to even).  Any H, W >= 8: the reflect padding to
+        multiples of the window and the crop happen on the device."""
+        import torch
+        from . import _lib
+        in_u8 = x.dtype == torch.uint8
+        x = x.contiguous() if in_u8 else x.float().contiguous()
+        b, h, w = (x.shape[0], x.shape[1], x.shape[2]) if in_u8 else (x.shape[0], x.shape[2], x.shape[3])
+        assert x.shape[3 if in_u8 else 1] == 3
+        self.check_fits(b, h, w)
+        s = self.scale
+        out = (torch.empty((b, h * s, w * s, 3), dtype=torch.uint8, device=x.device) if out_u8
+               else torch.empty((b, 3, h * s, w * s), dtype=torch.float32, device=x.device))
+        _lib.check(_lib.lib.sdmi_swinir_run(self.handle, _lib.ptr(x), 1 if in_u8 else 0, b, h, w, _lib.ptr(out), 1 if out_u8 else 0,
+                                            _lib.stream_ptr()), "sdmi_swinir_run")
+        return out
+
+
 def make_upscaler_net(state_dict, device=0, engine=None):
-    """EsrganNet or CompactNet, by the checkpoint's key layout (upscaler_family)."""
-    return (CompactNet if upscaler_family(state_dict) == "compact" else EsrganNet)(state_dict, device=device, engine=engine)
+    """EsrganNet, CompactNet or SwinIRNet, by the checkpoint's key layout (upscaler_family)."""
+    cls = {"compact": CompactNet, "swinir": SwinIRNet}.get(upscaler_family(state_dict), EsrganNet)
+    return cls(state_dict, device=device, engine=engine)
 
 
 class UpscalerESRGAN(Upscaler):
     """ESRGAN / Real-ESRGAN on the engine: what modules/esrgan_model.py:UpscalerESRGAN.do_upscale and
     modules/realesrgan_model.py:UpscalerRealESRGAN.do_upscale compute with ESRGAN_tile = 0 (the image whole; tiling exists there for
     VRAM this card does not lack), with the uint8 hand-off of modules/upscaler_utils.py.  RRDBNet checkpoints run as EsrganNet, the
-    compact Real-ESRGAN models (General 4xV3, General WDN 4xV3, AnimeVideo) as CompactNet."""
+    compact Real-ESRGAN models (General 4xV3, General WDN 4xV3, AnimeVideo) as CompactNet.  SwinIR checkpoints (nearest+conv upsampler)
+    run as SwinIRNet: what extensions-builtin/SwinIR's UpscalerSwinIR.do_upscale computes with the image in one tile (SWIN_tile exists
+    for the same VRAM reason as ESRGAN_tile), the padding to the window size done on the device."""
     name = "ESRGAN"
 
     def __init__(self, device=0, engine=None):
@@ -421,7 +585,7 @@ class UpscalerESRGAN(Upscaler):
 def register_esrgan(paths, device=0, engine=None):
     """Append one ``UpscalerData(name, path, scaler, scale)`` per checkpoint to shared.sd_upscalers (after the built-ins, which are
     installed first if the list is empty): `paths` is a {name: path} mapping or a list of paths (name = the file's stem), so
-    hr_upscaler="R-ESRGAN 4x+" and opts.upscaler_for_img2img resolve through _resize_to.  RRDBNet and compact (SRVGGNetCompact)
+    hr_upscaler="R-ESRGAN 4x+" and opts.upscaler_for_img2img resolve through _resize_to.  RRDBNet, compact (SRVGGNetCompact) and SwinIR
     checkpoints may be mixed; the scale is read from the checkpoint.
     engine: see UpscalerESRGAN (all entries of one call share one scaler object and so one engine)."""
     if not shared.sd_upscalers:

@@ -717,3 +717,42 @@ def install_esrgan_hook(webui_shared, device_index: int = 0):
         do_upscale._mi355x_stock = stock
         scaler.do_upscale = do_upscale
     return hooked
+
+
+def install_swinir_hook(webui_shared, device_index: int = 0):
+    """Point the webui's SwinIR scaler objects (extensions-builtin/SwinIR/scripts/swinir_model.py) at the engine: install_esrgan_hook for
+    the entries of ``webui_shared.sd_upscalers`` whose scaler class is UpscalerSwinIR.  Name, path / download resolution and the
+    ``Upscaler.upscale`` driver loop stay; ``do_upscale(img, model_file)`` runs the checkpoint as sdmi_swinir_run on the image whole
+    instead of as a torch module in SWIN_tile tiles.  The same fall-back rules: a URL that is not on disk yet, a checkpoint the loader
+    refuses (another upsampler or window size, ape, head dim > 32) or that fails to load or pack, and an image too large for the arena
+    stay on the stock path.  Returns the names of the hooked entries."""
+    from . import upscaler as amd_upscaler
+    engine_scaler = amd_upscaler.UpscalerESRGAN(device_index)
+    hooked = []
+    for data in getattr(webui_shared, "sd_upscalers", []):
+        scaler = getattr(data, "scaler", None)
+        if scaler is None or type(scaler).__name__ != "UpscalerSwinIR":
+            continue
+        hooked.append(data.name)
+        if hasattr(scaler.do_upscale, "_mi355x_stock"):
+            continue
+        stock = scaler.do_upscale
+
+        def do_upscale(img, model_file=None, _stock=stock, _scaler=scaler):
+            path = model_file
+            info = next((d for d in getattr(_scaler, "scalers", []) if model_file in (d.data_path, d.name)), None)
+            if info is not None:
+                path = getattr(info, "local_data_path", None) or info.data_path
+            if not isinstance(path, str) or path.startswith("http"):
+                return _stock(img, model_file)                    # not on disk yet: the stock code downloads (and runs) it
+            try:
+                engine_scaler.load_model(path)
+            except Exception:                                     # the loader's refusal (ValueError), an unreadable file, an engine error
+                return _stock(img, model_file)
+            try:
+                return engine_scaler.do_upscale(img, path)
+            except ValueError:                                    # EsrganInputTooLarge (the stock path tiles it), or a side below one window
+                return _stock(img, model_file)
+        do_upscale._mi355x_stock = stock
+        scaler.do_upscale = do_upscale
+    return hooked
