@@ -267,6 +267,14 @@ int sdmi_rowchain_ff(const void* x, void* out, const void* g, const void* b, con
                               hidden, eps, (hipStream_t)stream);
     API_GUARD_END
 }
+int sdmi_xattn_chain(const void* x, void* out, const void* g, const void* b, const void* wq, const void* wo, const void* bo, const void* k,
+                     const void* vt, int64_t rows, int rows_per_image, int C, int heads, int L, int Lpad, float eps, void* stream) {
+    API_GUARD_BEGIN
+    return launch_xattn_chain((const half_t*)x, (half_t*)out, (const float*)g, (const float*)b, (const half_t*)wq, (const half_t*)wo,
+                              (const float*)bo, (const half_t*)k, (const half_t*)vt, (long)rows, rows_per_image, C, heads, L, Lpad, eps,
+                              (hipStream_t)stream);
+    API_GUARD_END
+}
 
 
 int sdmi_philox_randn(void* out, int64_t n, uint64_t seed, uint32_t offset, void* stream) {

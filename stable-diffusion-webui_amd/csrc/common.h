@@ -230,6 +230,14 @@ int launch_rowchain_ff_pack(const half_t* w1, const float* b1, const half_t* w2,
 int launch_rowchain_ff(const half_t* x, half_t* out, const float* gamma, const float* beta, const void* packs, const float* bias_out,
                        long rows, int C, int hidden, float eps, hipStream_t s);
 
+// ---- the cross-attention third of the transformer block at the 320-wide level (xattn_chain.hip) -----------------
+// out = x + Wo attention(Wq LN(x), k, vt) + bo as one launch.  x / out [rows][C] fp16; gamma / beta fp32 [C]; wq / wo packed [C][C] fp16;
+// bo fp32 [C] or null; k [images][L][C] and vt [images][C][Lpad] as set_context caches them.  C = 320, heads = 8 (d = 40), rows and
+// rows_per_image multiples of 128.
+int launch_xattn_chain(const half_t* x, half_t* out, const float* gamma, const float* beta, const half_t* wq, const half_t* wo,
+                       const float* bo, const half_t* k, const half_t* vt, long rows, int rows_per_image, int C, int heads, int L, int Lpad,
+                       float eps, hipStream_t s);
+
 // ---- RRDBNet 3x3 conv (rrdb.hip) -----------------------------------------------------------------------------
 enum { RRDB_EP_NONE = 0, RRDB_EP_LRELU = 1,      // v = acc + bias;  LeakyReLU(0.2)(v)
        RRDB_EP_RES1 = 2,                         // alpha * v + r1                   (RDB exit x5 * 0.2 + x; alpha = 1: feat + conv_body)

@@ -807,8 +807,21 @@ static int run_st(Run& r, const STW& st, const half_t* x, int B, int H, int Wd, 
         // wave's one LDS staging region after the hi rows, in and out: 324 us against 269 us for LayerNorm + GEGLU GEMM + GEMM on the pair,
         // profiles/r06_fwd_ab_accuracy_with_hilo_chain.txt — and removed again)
         const bool chain_ok = !fold && !acc && !e->force_generic && e->use_glds && rowchain_supports(C) && HW % 128 == 0 && e->n_streams <= 1;
+        // option "fuse_rows" bit 0: norm2 -> attn2.to_q -> attention over the cached context -> attn2.to_out + x1 as one launch
+        // (xattn_chain.hip): the normalised tokens, q and the attention output are not allocated.  The decision uses nothing that
+        // differs between the dry and the real pass; hypernetworks of this width transform the normalised tokens, so they keep the launches.
+        const bool xchain = chain_ok && (e->fuse_rows & 1) && !hn_has_dim(e, C) && st.heads == 8 && st.dhead == 40 && !b.q2.b &&
+                            b.q2.cin_pad == C && b.q2.n_pad == C && b.o2.cin_pad == C && b.o2.n_pad == C;
         half_t* x2 = nullptr;
-        {
+        if (xchain) {
+            x2 = r.S(M * C);
+            if (!r.dry) {
+                SDMI_REQUIRE(e->ctx_valid && e->ctx_B == (r.Btot ? r.Btot : B), "context not set for this batch size");
+                TRY(launch_xattn_chain(x1, x2, b.ln2.g, b.ln2.b, b.q2.w, b.o2.w, b.o2.b, e->ctx_k[b.ctx_slot] + (size_t)r.b0 * e->ctx_L * C,
+                                       e->ctx_vt[b.ctx_slot] + (size_t)r.b0 * C * e->ctx_Lpad, (long)M, HW, C, st.heads, e->ctx_L,
+                                       e->ctx_Lpad, 1e-5f, r.s));
+            }
+        } else {
         half_t* q2 = nullptr;
         if (fold) {
             LnStats st2;
@@ -2513,9 +2526,11 @@ sdmi_engine::~sdmi_engine() {
 }
 
 // The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units; there the upscalers'
-// kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip and swinir.hip on their own (build.sh).
+// and the cross-attention chain's kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip, swinir.hip and
+// xattn_chain.hip on their own (build.sh).
 #ifndef __HIP__
 #include "rrdb.hip"
 #include "compact.hip"
 #include "swinir.hip"
+#include "xattn_chain.hip"
 #endif

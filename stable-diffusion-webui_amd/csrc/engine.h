@@ -208,8 +208,13 @@ struct sdmi_engine {
     int ln_fold = 0;                          // 1: row statistics from ln_rowstats_kernel; 2: also per-tile partial sums from the producing GEMMs' epilogues
     // The feed-forward chain of the transformer blocks at the 320-wide level as a single launch (rowchain.hip), option "fuse_rows" bit 1:
     // norm3 -> GEGLU -> ff.net.2 -> + x.  Default 2 (round 5, same-box A/Bs of the forward, profiles/r05_fwd_ab_*): 203-219 us against
-    // 263 us of LayerNorm + GEGLU GEMM + GEMM.  (Bit 0 was the cross-attention chain: measured slower, removed in round 6; the bit is ignored.)
-    int fuse_rows = [] { const char* e = getenv("SDMI_FUSE_ROWS"); return e ? atoi(e) : 2; }();
+    // 263 us of LayerNorm + GEGLU GEMM + GEMM.
+    // Bit 0: the cross-attention third, norm2 -> attn2.to_q -> attention over the cached context -> attn2.to_out + x, as one launch
+    // (xattn_chain.hip; a tiled GEMM over 128 whole token rows — round 5's lane-owns-row chain behind this bit was slower than the launches
+    // and was removed).  Taken at the 320-wide level when the feed-forward chain's conditions hold, no hypernetwork of that width is
+    // loaded and HW % 128 == 0; every other width and mode keeps the four launches.  Default 3: 70-75 us against 106-111 us for the four
+    // launches at the C1 level-0 shape, and the same-box forward / job A/Bs of profiles/xattn_chain_time.md.
+    int fuse_rows = [] { const char* e = getenv("SDMI_FUSE_ROWS"); return e ? atoi(e) : 3; }();
     // Accuracy mode (option "residual_fp32", off by default — the engine's counterpart of the reference's --no-half / upcast options,
     // modules/devices.py:284-295, modules/sd_hijack_optimizations.py:232-233): the UNet's carried stream — conv_in / ResBlock /
     // transformer-block / proj_out / down- and upsample outputs and the skip_connection 1x1 — is kept as (hi, lo) fp16 pairs

@@ -196,6 +196,23 @@ def rowchain_ff(x: torch.Tensor, gamma, beta, packs: torch.Tensor, b2, hidden: i
     return out
 
 
+def xattn_chain(x: torch.Tensor, gamma, beta, wq: torch.Tensor, wo: torch.Tensor, bo, k: torch.Tensor, vt: torch.Tensor, L: int,
+                heads: int = 8, eps: float = 1e-5) -> torch.Tensor:
+    """x + attn2(LayerNorm(x), context) of a BasicTransformerBlock at the 320-wide level as one launch (csrc/xattn_chain.hip).
+    x [images, rows_per_image, C] fp16 (rows_per_image % 128 == 0); wq / wo [C, C]; bo [C] or None; k [images, L, C] = to_k(context);
+    vt [images, C, Lpad] = to_v(context) transposed, Lpad a multiple of 32 (the engine pads to 64)."""
+    _lib.require_device()
+    images, rpi, c = x.shape
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    wq, wo, k, vt = wq.half().contiguous(), wo.half().contiguous(), k.half().contiguous(), vt.half().contiguous()
+    bo = bo.float().contiguous() if bo is not None else None
+    check(lib.sdmi_xattn_chain(ptr(x), ptr(out), ptr(gamma.float().contiguous()), ptr(beta.float().contiguous()), ptr(wq), ptr(wo),
+                               ptr(bo) if bo is not None else None, ptr(k), ptr(vt), images * rpi, rpi, c, heads, int(L), vt.shape[-1],
+                               float(eps), stream_ptr()), "sdmi_xattn_chain")
+    return out
+
+
 def philox_randn(shape, seed: int, offset: int, device) -> torch.Tensor:
     """One draw of rng_philox.Generator(seed) at ``offset`` (modules/rng_philox.py:84-102), generated on the GPU."""
     _lib.require_device()

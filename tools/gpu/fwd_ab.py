@@ -33,7 +33,7 @@ import numpy as np  # noqa: E402
 hipmem = None                   # tools/gpu/hipmem.py, imported by main(): tools/cpu/fwd_parity.py imports this module for its weights only
 
 PKG = "stable-diffusion-webui_amd"
-FUSE_ROWS_DEFAULT = 2           # the engine's default for option "fuse_rows" (engine.h)
+FUSE_ROWS_DEFAULT = 3           # the engine's default for option "fuse_rows" (engine.h)
 ENGINE_OPTS = ("ln_fold", "streams", "arena_reuse", "cfg_pairs", "uniform_t", "gn_cat", "fuse_rows", "residual_fp32")
 DEFAULTS = {"gemm_cfg": -1, "gemm_shortk_cfg": -1, "gemm_shortk_maxk": 448, "gemm_geglu_cfg": -1, "vt_mode": 1, "attn_kvt": 0, "attn_occ": 15, "attn_tau": 8, "attn_fold_min_m": 1024,
             "tile_order": -1, "conv_korder": -1, "small_linear_lds": 1, "gemm_split": 0, "gemm_pipe": -1, "gemm_lin": 1, "gn_fuse": 1, "gn_small": 1, "ep_wide": 1,
@@ -57,7 +57,7 @@ def classify(name):
         if re.search(r" x\d+$", name):
             return "1x1_batched"
         return "1x1"
-    for p in ("attention_mfma_self", "attention_mfma_cross", "groupnorm", "layernorm", "splitk", "small_linear", "rowchain_ff"):
+    for p in ("attention_mfma_self", "attention_mfma_cross", "groupnorm", "layernorm", "splitk", "small_linear", "rowchain_ff", "rowchain_xattn"):
         if name.startswith(p):
             return p
     return "other"
@@ -215,7 +215,7 @@ def build(args):
             if rc and v == DEFAULTS.get(k):                   # an older library (SDMI_LIB two-builds A/B) does not know this knob
                 continue
             _lib.check(rc, k)
-        # cached K / V^T of the text context depend on nothing a knob changes — except "fuse_rows", whose per-image matrices live beside them
+        # cached K / V^T of the text context depend on nothing a knob changes; re-projecting them per setting keeps the settings independent
         if args.what == "unet":
             _lib.check(lib.sdmi_unet_set_context(handle, dctx.ptr, _lib.F32, B, L, None), "set_context")
 
