@@ -489,7 +489,8 @@ enum {
     SDMI_RRDB_EP_NONE = 0,   /* acc + bias */
     SDMI_RRDB_EP_LRELU = 1,  /* LeakyReLU(0.2) */
     SDMI_RRDB_EP_RES1 = 2,   /* alpha * v + r1                  (RDB exit x5 * 0.2 + x; alpha = 1: feat + conv_body(...)) */
-    SDMI_RRDB_EP_RES2 = 3    /* beta * (alpha * v + r1) + r2    (third RDB of an RRDB: also the RRDB's out * 0.2 + x) */
+    SDMI_RRDB_EP_RES2 = 3,   /* beta * (alpha * v + r1) + r2    (third RDB of an RRDB: also the RRDB's out * 0.2 + x) */
+    SDMI_RRDB_EP_RELU = 4    /* ReLU                            (the conv_block of a ScuNET ConvTransBlock) */
 };
 enum {
     SDMI_RRDB_ST_F16 = 0,       /* fp16 NHWC rows of stride ldo, `out` already offset to the first output channel */
@@ -633,6 +634,69 @@ int64_t sdmi_swinir_scratch_bytes(sdmi_swinir* h, int B, int H, int W);
 /* in / out as sdmi_esrgan_run: uint8 HWC or fp32 NCHW in, fp32 NCHW or uint8 HWC [B][H s][W s][3] out (device memory).  Any H, W >= 8: the
  * image is reflect-padded to multiples of 8 on the way in and the output cropped.  Refused: a side below 8, tensors of 2^31 elements. */
 int sdmi_swinir_run(sdmi_swinir* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
+
+/* ---- ScuNET denoisers / upscalers ------------------------------------------------------------------------------------------------------ */
+
+/* The transformer `Block` of one ConvTransBlock (csrc/scunet.hip), window size 8, head dim 32, trans_dim C = 32 (1 head) or 64 (2 heads),
+ * as ONE launch: a workgroup per 8 x 8 window.  Replaces, in Block.forward / WMSA.forward of network_scunet.py,
+ *   x = x + msa(ln1(x));  x = x + mlp(ln2(x))
+ * with msa = roll by (-shift, -shift), window partition, embedding_layer, `einsum(q, k) * 32^-1/2 + relative bias`, the 'SW' mask,
+ * softmax, `@ v`, linear, window merge, roll back, and mlp = Linear, exact GELU, Linear.  The roll and the partition are index arithmetic
+ * (a token is read from and written back to its own row), the mask is computed (shift 4: in the last row of windows pairs with
+ * (ya < 4) != (yb < 4) get -inf, in the last column pairs with (xa < 4) != (xb < 4)).  LN statistics, scores, softmax, GELU and the
+ * residual sums are fp32; normalised rows, q / k / v, probabilities, the intermediate x and the hidden layer are rounded to fp16 on chip
+ * and never written to memory.  `out` may alias `x` (a window loads its 64 rows before it stores any).
+ * Refused (non-zero, message in sdmi_last_error, nothing written): null descriptor or pointers; C not 32 or 64; shift not 0 or 4; H or W
+ * not a positive multiple of 8; ldx or ldo below C; x / out / packs / bias not 16-byte aligned, ldx or ldo not a multiple of 8;
+ * B*H*W of 2^31 tokens. */
+typedef struct sdmi_scu_block_desc {
+    const void* x;         /* fp16 token rows [B*H*W][ldx]; columns 0 .. C-1 are the input (offset the pointer to read a column range) */
+    void* out;             /* fp16 token rows [B*H*W][ldo]; columns 0 .. C-1 are written, the rest of a row is untouched */
+    const void* packs;     /* sdmi_scu_block_pack's output for this C */
+    const void* bias;      /* fp32 [C / 32][64][64]: bias[h][a][b] = relative_position_params[h][ya - yb + 7][xa - xb + 7] */
+    int32_t B, H, W;       /* the token grid (row-major rows) */
+    int32_t C;             /* 32 | 64 */
+    int32_t ldx, ldo;
+    int32_t shift;         /* 0 ('W' blocks) | 4 ('SW' blocks) */
+} sdmi_scu_block_desc;
+int sdmi_scu_block(const sdmi_scu_block_desc* d, void* stream);
+/* The Block's weights (device memory, torch layouts: fp16 [out][in] matrices, fp32 vectors) -> the operand image the kernel stages:
+ *   ln1.weight, ln1.bias [C]; msa.embedding_layer [3C][C] + [3C]; msa.linear [C][C] + [C]; ln2.weight, ln2.bias [C];
+ *   mlp.0 [4C][C] + [4C]; mlp.2 [C][4C] + [C]  ->  packs (sdmi_scu_block_pack_bytes(C) bytes, 16-byte aligned; 0 bytes for a refused C).
+ * Refused: C not 32 or 64, a null pointer, misaligned packs. */
+int64_t sdmi_scu_block_pack_bytes(int C);
+int sdmi_scu_block_pack(const void* ln1_g, const void* ln1_b, const void* wqkv_f16, const void* bqkv, const void* wproj_f16, const void* bproj,
+                        const void* ln2_g, const void* ln2_b, const void* w1_f16, const void* b1, const void* w2_f16, const void* b2,
+                        void* packs, int C, void* stream);
+
+/* A whole SCUNet (in_nc 3, dim 64, head dim 32, window 8; "ScuNET GAN" / "ScuNET PSNR" are depths 4 x 7) held by an engine (scratch from
+ * the engine's arena, a fixed set of buffers whatever the depths).  Replaces the model call inside UpscalerScuNET.do_upscale
+ * (extensions-builtin/ScuNET/scripts/scunet_model.py), run on the image whole instead of in SCUNET_tile tiles.  Scale 1.
+ * blob: host fp32, every tensor flattened in checkpoint layout, in this order:
+ *   m_head.0.weight [64][3][3][3];
+ *   for the stages m_down1, m_down2, m_down3, m_body, m_up3, m_up2, m_up1 (conv_dim = trans_dim = 32, 64, 128, 256, 128, 64, 32):
+ *     (m_up* only, first) the ConvTranspose2d weight [4c][2c][2][2];
+ *     per block: trans_block.ln1.weight, .bias; msa.relative_position_params [c/32][15][15]; msa.embedding_layer.weight, .bias;
+ *       msa.linear.weight, .bias; ln2.weight, .bias; mlp.0.weight, .bias; mlp.2.weight, .bias; conv1_1.weight, .bias; conv1_2.weight, .bias;
+ *       conv_block.0.weight; conv_block.2.weight;
+ *     (m_down* only, last) the stride-2 Conv2d weight [4c][2c][2][2];
+ *   m_tail.0.weight [3][64][3][3].
+ * Block i of a stage is 'W' for even i, 'SW' for odd i.  sdmi_scunet_blob_floats gives the blob's length (0 for a config the engine
+ * refuses).  dim is fixed at 64: a checkpoint of another width has a blob of another length.  NULL on error: a null argument, a depth
+ * outside 1..64, a blob of another length. */
+typedef struct sdmi_scunet_config {
+    int32_t depths[7];     /* blocks of m_down1, m_down2, m_down3, m_body, m_up3, m_up2, m_up1, each 1 .. 64 */
+} sdmi_scunet_config;
+typedef struct sdmi_scunet sdmi_scunet;
+int64_t sdmi_scunet_blob_floats(const sdmi_scunet_config* cfg);
+sdmi_scunet* sdmi_scunet_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_scunet_config* cfg);
+void sdmi_scunet_destroy(sdmi_scunet* h);
+/* arena bytes a run on B images of H x W needs (0 for a refused size) */
+int64_t sdmi_scunet_scratch_bytes(sdmi_scunet* h, int B, int H, int W);
+/* in / out as sdmi_esrgan_run: uint8 HWC or fp32 NCHW in, fp32 NCHW or uint8 HWC [B][H][W][3] out (device memory).  Any H, W >= 1: the
+ * image is padded right / bottom to multiples of 64 by replication on the way in and the output cropped.  Refused: null pointers, an
+ * empty image, tensors of 2^31 elements (B * roundup(H, 64) * roundup(W, 64) * 64). */
+int sdmi_scunet_run(sdmi_scunet* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
 
 #ifdef __cplusplus
 }

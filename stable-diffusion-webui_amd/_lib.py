@@ -15,7 +15,7 @@ F16, F32 = 0, 1
 EP_OUT_F32, EP_GEGLU, EP_NCHW, EP_BIAS_ROW = 1, 2, 4, 8
 EP_TRANSPOSE = 64
 EP_WRAP = 128
-RRDB_EP_NONE, RRDB_EP_LRELU, RRDB_EP_RES1, RRDB_EP_RES2 = 0, 1, 2, 3
+RRDB_EP_NONE, RRDB_EP_LRELU, RRDB_EP_RES1, RRDB_EP_RES2, RRDB_EP_RELU = 0, 1, 2, 3, 4
 RRDB_ST_F16, RRDB_ST_F32_NCHW, RRDB_ST_U8_HWC = 0, 1, 2
 COMPACT_EP_NONE, COMPACT_EP_PRELU, COMPACT_EP_TAIL = 0, 1, 2
 
@@ -67,6 +67,18 @@ class SwinAttnDesc(C.Structure):
 class SwinIRConfigC(C.Structure):
     _fields_ = [("embed_dim", C.c_int32), ("num_layers", C.c_int32), ("depths", C.c_int32 * 16), ("num_heads", C.c_int32),
                 ("mlp_hidden", C.c_int32), ("resi_3conv", C.c_int32), ("scale", C.c_int32)]
+
+
+class ScuBlockDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("out", C.c_void_p), ("packs", C.c_void_p), ("bias", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+        ("ldx", C.c_int32), ("ldo", C.c_int32), ("shift", C.c_int32),
+    ]
+
+
+class ScuNETConfigC(C.Structure):
+    _fields_ = [("depths", C.c_int32 * 7)]
 
 
 class UNetConfigC(C.Structure):
@@ -201,6 +213,14 @@ _SIGS = {
     "sdmi_swinir_destroy": (None, [_vp]),
     "sdmi_swinir_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
     "sdmi_swinir_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "sdmi_scu_block": (_i, [C.POINTER(ScuBlockDesc), _vp]),
+    "sdmi_scu_block_pack_bytes": (_i64, [_i]),
+    "sdmi_scu_block_pack": (_i, [_vp] * 13 + [_i, _vp]),
+    "sdmi_scunet_blob_floats": (_i64, [C.POINTER(ScuNETConfigC)]),
+    "sdmi_scunet_create": (_vp, [_vp, _vp, _i64, C.POINTER(ScuNETConfigC)]),
+    "sdmi_scunet_destroy": (None, [_vp]),
+    "sdmi_scunet_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
+    "sdmi_scunet_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)       # AttributeError here == the .so does not export a declared symbol

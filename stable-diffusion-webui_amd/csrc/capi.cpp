@@ -38,6 +38,10 @@ int64_t swinir_blob_floats(const sdmi_swinir_config* cfg);
 int swinir_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swinir_config* cfg, sdmi_swinir** out);
 int64_t swinir_scratch_bytes(const sdmi_swinir* n, int B, int H, int W);
 int swinir_run(sdmi_swinir* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
+int64_t scunet_blob_floats(const sdmi_scunet_config* cfg);
+int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_scunet_config* cfg, sdmi_scunet** out);
+int64_t scunet_scratch_bytes(const sdmi_scunet* n, int B, int H, int W);
+int scunet_run(sdmi_scunet* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
 }  // namespace sdmi
 
 using namespace sdmi;
@@ -729,6 +733,52 @@ int64_t sdmi_swinir_scratch_bytes(sdmi_swinir* h, int B, int H, int W) { return 
 int sdmi_swinir_run(sdmi_swinir* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
     API_GUARD_BEGIN
     return swinir_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_scu_block(const sdmi_scu_block_desc* d, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(d, "null descriptor");
+    ScuBlockP p{};
+    p.x = (const half_t*)d->x; p.out = (half_t*)d->out; p.packs = d->packs; p.bias = (const float*)d->bias;
+    p.B = d->B; p.H = d->H; p.W = d->W; p.ldx = d->ldx; p.ldo = d->ldo; p.shift = d->shift;
+    return launch_scu_block(p, d->C, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int64_t sdmi_scu_block_pack_bytes(int C) { return (int64_t)scu_block_pack_bytes(C); }
+int sdmi_scu_block_pack(const void* ln1_g, const void* ln1_b, const void* wqkv, const void* bqkv, const void* wproj, const void* bproj,
+                        const void* ln2_g, const void* ln2_b, const void* w1, const void* b1, const void* w2, const void* b2, void* packs, int C,
+                        void* stream) {
+    API_GUARD_BEGIN
+    ScuPackP p{};
+    p.ln1_g = (const float*)ln1_g; p.ln1_b = (const float*)ln1_b; p.wqkv = (const half_t*)wqkv; p.bqkv = (const float*)bqkv;
+    p.wproj = (const half_t*)wproj; p.bproj = (const float*)bproj; p.ln2_g = (const float*)ln2_g; p.ln2_b = (const float*)ln2_b;
+    p.w1 = (const half_t*)w1; p.b1 = (const float*)b1; p.w2 = (const half_t*)w2; p.b2 = (const float*)b2; p.packs = packs;
+    return launch_scu_block_pack(p, C, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int64_t sdmi_scunet_blob_floats(const sdmi_scunet_config* cfg) { return scunet_blob_floats(cfg); }
+
+sdmi_scunet* sdmi_scunet_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_scunet_config* cfg) {
+    try {
+        sdmi_scunet* n = nullptr;
+        if (scunet_create(e, (const float*)blob_f32, blob_floats, cfg, &n) != 0) return nullptr;
+        return n;
+    } catch (const std::exception& ex) {
+        set_error(std::string("exception: ") + ex.what());
+        return nullptr;
+    }
+}
+
+void sdmi_scunet_destroy(sdmi_scunet* h) { delete h; }
+
+int64_t sdmi_scunet_scratch_bytes(sdmi_scunet* h, int B, int H, int W) { return scunet_scratch_bytes(h, B, H, W); }
+
+int sdmi_scunet_run(sdmi_scunet* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
+    API_GUARD_BEGIN
+    return scunet_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
     API_GUARD_END
 }
 

@@ -241,7 +241,8 @@ int launch_xattn_chain(const half_t* x, half_t* out, const float* gamma, const f
 // ---- RRDBNet 3x3 conv (rrdb.hip) -----------------------------------------------------------------------------
 enum { RRDB_EP_NONE = 0, RRDB_EP_LRELU = 1,      // v = acc + bias;  LeakyReLU(0.2)(v)
        RRDB_EP_RES1 = 2,                         // alpha * v + r1                   (RDB exit x5 * 0.2 + x; alpha = 1: feat + conv_body)
-       RRDB_EP_RES2 = 3 };                       // beta * (alpha * v + r1) + r2     (third RDB of an RRDB: also closes the RRDB residual)
+       RRDB_EP_RES2 = 3,                         // beta * (alpha * v + r1) + r2     (third RDB of an RRDB: also closes the RRDB residual)
+       RRDB_EP_RELU = 4 };                       // ReLU(v)                          (ScuNET's conv_block)
 enum { RRDB_ST_F16 = 0, RRDB_ST_F32_NCHW = 1, RRDB_ST_U8_HWC = 2 };
 struct RrdbP {
     const half_t* in;      // NHWC rows of stride lda; the first cin channels are read.  With up: the (H/2) x (W/2) low-resolution tensor
@@ -302,6 +303,40 @@ int launch_swin_input(const void* in, int u8, half_t* out, int B, int H, int W, 
 int launch_swin_lrelu(half_t* x, int64_t n, float slope, hipStream_t s);               // in place
 // fp32 [B][3][Hp][Wp] cropped to H x W -> fp32 NCHW or (out_u8) uint8 HWC
 int launch_swin_output(const float* src, void* out, int out_u8, int B, int H, int W, int Hp, int Wp, hipStream_t s);
+
+// ---- ScuNET: the transformer Block of one 8 x 8 window per workgroup (scunet.hip) ------------------------------
+struct ScuBlockP {
+    const half_t* x;       // token rows [B*H*W][ldx], the first C columns are the block's input
+    half_t* out;           // token rows [B*H*W][ldo], the first C columns are written (may alias x)
+    const void* packs;     // launch_scu_block_pack's output
+    const float* bias;     // [C / 32][64][64]: relative-position bias of (query, key) inside a window
+    int B, H, W;           // token grid; H, W multiples of 8
+    int ldx, ldo;
+    int shift;             // 0 ('W') | 4 ('SW': the last row / column of windows is masked)
+    long long windows;     // set by the launcher
+};
+int launch_scu_block(const ScuBlockP& p, int C, hipStream_t s);
+struct ScuPackP {          // torch layouts: fp16 [out][in] matrices, fp32 vectors
+    const float *ln1_g, *ln1_b;
+    const half_t* wqkv;    // embedding_layer [3C][C]
+    const float* bqkv;
+    const half_t* wproj;   // linear [C][C]
+    const float* bproj;
+    const float *ln2_g, *ln2_b;
+    const half_t* w1;      // mlp.0 [4C][C]
+    const float* b1;
+    const half_t* w2;      // mlp.2 [C][4C]
+    const float* b2;
+    void* packs;
+};
+size_t scu_block_pack_bytes(int C);
+int launch_scu_block_pack(const ScuPackP& p, int C, hipStream_t s);
+// RGB image (uint8 HWC / 255, or fp32 NCHW) -> replicate-padded right / bottom to Hp x Wp -> NHWC fp16 rows of cpad channels
+int launch_scu_input(const void* in, int u8, half_t* out, int B, int H, int W, int Hp, int Wp, int cpad, hipStream_t s);
+// hi [B][2h][2w][C] <-> lo [B][h][w][4][C] (slot dy * 2 + dx): to_lo gathers the 2 x 2 patches of a stride-2 conv into GEMM rows,
+// otherwise the 4 C columns of a transposed conv's GEMM are scattered to their pixels
+int launch_scu_patch2(const half_t* src, half_t* dst, int B, int h, int w, int C, int to_lo, hipStream_t s);
+int launch_scu_add(half_t* x, const half_t* y, int64_t n, hipStream_t s);            // x += y (a skip connection)
 
 // ---- norms ------------------------------------------------------------------------------------------------
 // pre_nchunk > 0: `ws` already holds (mean, M2) [B][pre_nchunk][groups][2] of HW / pre_nchunk rows each (written by the producing GEMM): skip the statistics pass

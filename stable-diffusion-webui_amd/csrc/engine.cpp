@@ -365,6 +365,7 @@ struct ConvArgs {
     const half_t* a0 = nullptr;
     const half_t* a1 = nullptr;
     int c0 = 0, c1 = 0;
+    int lda0 = 0;                 // row stride of a0 when its rows are wider than c0 (0 = c0)
     int B = 1, Hi = 1, Wi = 1, Ho = 1, Wo = 1;
     int stride = 1, pad = 0, up = 0;
     const float* rowbias = nullptr;
@@ -409,7 +410,7 @@ static int run_conv(Run& r, const ConvW& W, const ConvArgs& a) {
     p.splitk_ws = splitk_ws;
     p.lnp_out = lnp_ws;
     p.a0 = a.a0; p.a1 = a.a1; p.w = W.w; p.bias = W.b; p.rowbias = a.rowbias; p.resid = a.resid; p.out = a.out;
-    p.c0 = a.c0; p.c1 = a.c1; p.cin = a.c0 + a.c1; p.lda0 = a.c0; p.lda1 = a.c1;
+    p.c0 = a.c0; p.c1 = a.c1; p.cin = a.c0 + a.c1; p.lda0 = a.lda0 ? a.lda0 : a.c0; p.lda1 = a.c1;
     SDMI_REQUIRE(p.cin == W.cin_pad, "conv input channels do not match the packed weight");
     p.Hi = a.Hi; p.Wi = a.Wi; p.Ho = a.Ho; p.Wo = a.Wo;
     p.taps = W.taps; p.stride = a.stride; p.pad = a.pad; p.up = a.up;
@@ -2492,7 +2493,316 @@ int swinir_run(sdmi_swinir* n, const void* in, int in_u8, int B, int H, int W, v
     return swinir_pass(run, *n, in, in_u8, B, H, W, out, out_u8);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// ScuNET (SCUNet.forward of network_scunet.py, dim 64): the transformer Block of the 32- and 64-wide levels as scu_block launches
+// (scunet.hip), of the 128- and 256-wide levels as swin_layernorm + GEMMs + swin_window_attn, the 1x1 convs and the 2x2 stride-2 /
+// transposed convs as GEMMs (the latter through scu_patch2), the 3x3 pairs on rrdb_conv (32 / 64) or the GEMMs (128 / 256)
+// ------------------------------------------------------------------------------------------------------------
+// blob: fp32, in the order include/sdmi.h documents at sdmi_scunet_config.
+static bool scunet_config_ok(const sdmi_scunet_config& c, std::string* why) {
+    for (int i = 0; i < 7; ++i)
+        if (c.depths[i] < 1 || c.depths[i] > 64) { if (why) *why = "depths[i] in 1..64"; return false; }
+    return true;
+}
+static int scunet_stage_c(int st) { return 32 << (st < 4 ? st : 6 - st); }       // conv_dim = trans_dim of m_down1 .. m_body .. m_up1
+
+int64_t scunet_blob_floats(const sdmi_scunet_config* c) {
+    if (!c || !scunet_config_ok(*c, nullptr)) return 0;
+    int64_t n = 64 * 3 * 9 + 3 * 64 * 9;
+    for (int st = 0; st < 7; ++st) {
+        const int64_t t = scunet_stage_c(st), D = 2 * t;
+        const int64_t block = 2 * t + 225 * (t / 32) + (3 * t * t + 3 * t) + (t * t + t) + 2 * t + (4 * t * t + 4 * t) + (4 * t * t + t) +
+                              2 * (D * D + D) + 2 * (t * t * 9);
+        n += c->depths[st] * block;
+        if (st < 3) n += 2 * D * D * 4;                     // Conv2d(D, 2 D, 2, 2)
+        if (st > 3) n += 2 * D * D * 4;                     // ConvTranspose2d(2 D, D, 2, 2)
+    }
+    return n;
+}
+
+int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_scunet_config* cfg, sdmi_scunet** out) {
+    SDMI_REQUIRE(e && blob && cfg && out, "null argument");
+    std::string why;
+    SDMI_REQUIRE(scunet_config_ok(*cfg, &why), "ScuNET config: " + why);
+    SDMI_REQUIRE(blob_floats == scunet_blob_floats(cfg), "weight blob size does not match the config");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    std::unique_ptr<sdmi_scunet> net(new sdmi_scunet);
+    net->e = e; net->cfg = *cfg;
+    const float* src = blob;
+    auto upload = [&](const void* host, size_t bytes, void** dev) -> int {
+        SDMI_CHECK_HIP(hipMalloc(dev, std::max<size_t>(bytes, 256)));
+        net->owned.push_back(*dev);
+        SDMI_CHECK_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+        return 0;
+    };
+    // one conv / linear off the blob -> [O][taps][I] fp16 (+ [O] fp32 bias).  at(o, i, t): where the checkpoint keeps that weight
+    auto pack = [&](ConvW* c, int O, int I, int taps, bool bias, const std::function<size_t(int, int, int)>& at) -> int {
+        std::vector<half_t> w((size_t)O * taps * I);
+        for (int o = 0; o < O; ++o)
+            for (int t = 0; t < taps; ++t)
+                for (int i = 0; i < I; ++i) w[((size_t)o * taps + t) * I + i] = (half_t)src[at(o, i, t)];
+        src += (size_t)O * I * taps;
+        c->cin = c->cin_pad = I; c->cout = c->n_pad = O; c->taps = taps;
+        TRY(upload(w.data(), w.size() * sizeof(half_t), (void**)&c->w));
+        if (!bias) return 0;
+        TRY(upload(src, (size_t)O * sizeof(float), (void**)&c->b));
+        src += O;
+        return 0;
+    };
+    auto oihw = [](int I, int taps) { return [=](int o, int i, int t) { return ((size_t)o * I + i) * taps + t; }; };
+    auto norm = [&](NormW* n, int C) -> int {
+        n->c = C;
+        TRY(upload(src, (size_t)C * sizeof(float), (void**)&n->g));
+        TRY(upload(src + C, (size_t)C * sizeof(float), (void**)&n->b));
+        src += 2 * C;
+        return 0;
+    };
+    // m_head / m_tail on rrdb_conv: 3 input channels in a 32-wide row, 3 output channels of a 32-wide tile
+    {
+        std::vector<half_t> w((size_t)64 * 9 * 32, (half_t)0.f);
+        for (int o = 0; o < 64; ++o)
+            for (int i = 0; i < 3; ++i)
+                for (int t = 0; t < 9; ++t) w[((size_t)o * 9 + t) * 32 + i] = (half_t)src[((size_t)o * 3 + i) * 9 + t];
+        src += 64 * 3 * 9;
+        net->head.cin = 3; net->head.cin_pad = 32; net->head.cout = net->head.n_pad = 64; net->head.taps = 9;
+        TRY(upload(w.data(), w.size() * sizeof(half_t), (void**)&net->head.w));
+    }
+    std::vector<float> bias;
+    for (int st = 0; st < 7; ++st) {
+        const int t = scunet_stage_c(st), D = 2 * t, heads = t / 32;
+        if (st > 3)     // ConvTranspose2d(2 D, D, 2, 2) [2 D][D][2][2]: GEMM row (dy * 2 + dx) * D + o, column i
+            TRY(pack(&net->up[6 - st], 4 * D, 2 * D, 1, false, [=](int n, int i, int) { return ((size_t)i * D + n % D) * 4 + n / D; }));
+        net->stage[st].resize((size_t)cfg->depths[st]);
+        for (sdmi_scunet::Block& bk : net->stage[st]) {
+            bk.c = t;
+            const float* ln1 = src;
+            src += 2 * t;
+            bias.resize((size_t)heads * 4096);
+            for (int h = 0; h < heads; ++h)                 // bias[h][a][b] = params[h][ya - yb + 7][xa - xb + 7]
+                for (int a = 0; a < 64; ++a)
+                    for (int b = 0; b < 64; ++b)
+                        bias[((size_t)h * 64 + a) * 64 + b] = src[(size_t)h * 225 + ((a >> 3) - (b >> 3) + 7) * 15 + ((a & 7) - (b & 7) + 7)];
+            src += 225 * heads;
+            TRY(upload(bias.data(), bias.size() * sizeof(float), (void**)&bk.bias));
+            if (t <= 64) {
+                // the Block's tensors as the pack kernel wants them: fp16 matrices, fp32 vectors, all temporaries
+                std::vector<void*> tmp;
+                auto up16 = [&](int n, const half_t** dev) -> int {
+                    std::vector<half_t> w((size_t)n);
+                    for (int i = 0; i < n; ++i) w[(size_t)i] = (half_t)src[i];
+                    src += n;
+                    void* d = nullptr;
+                    SDMI_CHECK_HIP(hipMalloc(&d, std::max<size_t>((size_t)n * 2, 256)));
+                    tmp.push_back(d);
+                    SDMI_CHECK_HIP(hipMemcpy(d, w.data(), (size_t)n * 2, hipMemcpyHostToDevice));
+                    *dev = (const half_t*)d;
+                    return 0;
+                };
+                auto up32 = [&](const float* host, int n, const float** dev) -> int {
+                    void* d = nullptr;
+                    SDMI_CHECK_HIP(hipMalloc(&d, std::max<size_t>((size_t)n * 4, 256)));
+                    tmp.push_back(d);
+                    SDMI_CHECK_HIP(hipMemcpy(d, host, (size_t)n * 4, hipMemcpyHostToDevice));
+                    *dev = (const float*)d;
+                    return 0;
+                };
+                ScuPackP pp{};
+                int rc = up32(ln1, t, &pp.ln1_g) || up32(ln1 + t, t, &pp.ln1_b);
+                rc = rc || up16(3 * t * t, &pp.wqkv) || up32(src, 3 * t, &pp.bqkv); src += 3 * t;
+                rc = rc || up16(t * t, &pp.wproj) || up32(src, t, &pp.bproj); src += t;
+                rc = rc || up32(src, t, &pp.ln2_g) || up32(src + t, t, &pp.ln2_b); src += 2 * t;
+                rc = rc || up16(4 * t * t, &pp.w1) || up32(src, 4 * t, &pp.b1); src += 4 * t;
+                rc = rc || up16(4 * t * t, &pp.w2) || up32(src, t, &pp.b2); src += t;
+                if (!rc) {
+                    rc = hipMalloc(&bk.packs, scu_block_pack_bytes(t)) != hipSuccess;
+                    if (!rc) {
+                        net->owned.push_back(bk.packs);
+                        pp.packs = bk.packs;
+                        rc = launch_scu_block_pack(pp, t, nullptr) || hipDeviceSynchronize() != hipSuccess;
+                    }
+                }
+                for (void* d : tmp) (void)hipFree(d);
+                SDMI_REQUIRE(!rc, "packing a Block's weights failed");
+            } else {
+                bk.n1.c = t;
+                TRY(upload(ln1, (size_t)t * sizeof(float), (void**)&bk.n1.g));
+                TRY(upload(ln1 + t, (size_t)t * sizeof(float), (void**)&bk.n1.b));
+                TRY(pack(&bk.qkv, 3 * t, t, 1, true, oihw(t, 1)));
+                TRY(pack(&bk.proj, t, t, 1, true, oihw(t, 1)));
+                TRY(norm(&bk.n2, t));
+                TRY(pack(&bk.fc1, 4 * t, t, 1, true, oihw(t, 1)));
+                TRY(pack(&bk.fc2, t, 4 * t, 1, true, oihw(4 * t, 1)));
+            }
+            TRY(pack(&bk.c11, D, D, 1, true, oihw(D, 1)));
+            TRY(pack(&bk.c12, D, D, 1, true, oihw(D, 1)));
+            TRY(pack(&bk.cb0, t, t, 9, false, oihw(t, 9)));
+            TRY(pack(&bk.cb2, t, t, 9, false, oihw(t, 9)));
+        }
+        if (st < 3)     // Conv2d(D, 2 D, 2, 2) [2 D][D][2][2]: GEMM column (dy * 2 + dx) * D + i
+            TRY(pack(&net->down[st], 2 * D, 4 * D, 1, false, [=](int o, int k, int) { return ((size_t)o * D + k % D) * 4 + k / D; }));
+    }
+    {
+        std::vector<half_t> w((size_t)32 * 9 * 64, (half_t)0.f);
+        for (int o = 0; o < 3; ++o)
+            for (int i = 0; i < 64; ++i)
+                for (int t = 0; t < 9; ++t) w[((size_t)o * 9 + t) * 64 + i] = (half_t)src[((size_t)o * 64 + i) * 9 + t];
+        src += 3 * 64 * 9;
+        net->tail.cin = net->tail.cin_pad = 64; net->tail.cout = 3; net->tail.n_pad = 32; net->tail.taps = 9;
+        TRY(upload(w.data(), w.size() * sizeof(half_t), (void**)&net->tail.w));
+    }
+    SDMI_REQUIRE(src - blob == blob_floats, "internal: blob walk does not end at its length");
+    SDMI_CHECK_HIP(hipDeviceSynchronize());
+    *out = net.release();
+    return 0;
+}
+
+// One pass over the network (dry: the arena layout alone).  A fixed set of buffers whatever the depths: the four skip tensors, and
+// level-1-sized work buffers that every level reuses (a level's tensors are half the size of the level above).
+static int scunet_pass(Run& r, const sdmi_scunet& n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8) {
+    const int Hp = rup(H, 64), Wp = rup(W, 64);
+    const size_t M1 = (size_t)B * Hp * Wp;
+    r.ar->reset();
+    half_t* in0 = r.H(M1 * 32);
+    half_t* skip[4] = {r.H(M1 * 64), r.H(M1 * 32), r.H(M1 * 16), r.H(M1 * 8)};      // x1 .. x4: [M1 / 4^l][64 << l]
+    half_t* pool[2] = {r.H(M1 * 64), r.H(M1 * 64)};          // a stage's ping-pong
+    half_t* Y = r.H(M1 * 64);                                 // conv1_1's output: conv_x | trans_x
+    half_t* Z = r.H(M1 * 64);                                 // cat(conv_x, trans_x) that conv1_2 reads; the 2x2 patches of the resampling convs
+    half_t* T = r.H(M1 * 32);                                 // between the two 3x3 convs
+    // the Block at trans_dim 128 / 256 (levels 3 and 4; sized for level 3, M1 / 16 rows)
+    half_t* lnb = r.H(M1 * 16);                               // [M][2 t]: swin_layernorm writes rows as wide as it reads
+    half_t* qkv = r.H(M1 * 24);
+    half_t* att = r.H(M1 * 8);
+    half_t* mid = r.H(M1 * 8);
+    half_t* hid = r.H(M1 * 32);
+    float* full = r.F(M1 * 3);                                // m_tail on the padded grid, cropped by swin_output
+
+    auto gemm = [&](const ConvW& w, const half_t* a, int lda, int h, int wd, const half_t* resid, int ldr, half_t* o, int ldo, int flags = 0) -> int {
+        ConvArgs c;
+        c.a0 = a; c.c0 = w.cin_pad; c.lda0 = lda; c.B = B; c.Hi = c.Ho = h; c.Wi = c.Wo = wd; c.pad = w.taps == 9 ? 1 : 0;
+        c.resid = resid; c.ldr = ldr; c.out = o; c.ldo = ldo; c.flags = flags;
+        const size_t mark = r.ar->mark();                     // a split-K workspace lives for its launch only
+        const int rc = run_conv(r, w, c);
+        r.ar->rewind(mark);
+        return rc;
+    };
+    auto conv3 = [&](const ConvW& w, const half_t* src, int cin, int lda, int h, int wd, void* dst, int ldo, int ep, const half_t* r1, int ldr1,
+                     int store = RRDB_ST_F16) -> int {
+        if (r.dry) return 0;
+        RrdbP p{};
+        p.in = src; p.w = w.w; p.bias = nullptr; p.r1 = r1; p.out = dst;
+        p.B = B; p.H = h; p.W = wd; p.cin = cin; p.lda = lda; p.ldo = ldo; p.n_real = w.cout; p.ldr1 = ldr1; p.ep = ep; p.store = store;
+        p.alpha = 1.f; p.beta = 1.f;
+        return launch_rrdb_conv(p, w.n_pad, r.s);
+    };
+    // one ConvTransBlock: x [M][D] -> o [M][D]
+    auto ctb = [&](const sdmi_scunet::Block& bk, int type_sw, const half_t* x, half_t* o, int h, int wd) -> int {
+        const int t = bk.c, D = 2 * t;
+        const size_t M = (size_t)B * h * wd;
+        TRY(gemm(bk.c11, x, D, h, wd, nullptr, 0, Y, D));
+        if (t <= 64) {
+            TRY(conv3(bk.cb0, Y, t, D, h, wd, T, t, RRDB_EP_RELU, nullptr, 0));
+            TRY(conv3(bk.cb2, T, t, t, h, wd, Z, D, RRDB_EP_RES1, Y, D));
+            if (!r.dry) {
+                ScuBlockP p{};
+                p.x = Y + t; p.out = Z + t; p.packs = bk.packs; p.bias = bk.bias; p.B = B; p.H = h; p.W = wd; p.ldx = D; p.ldo = D;
+                p.shift = type_sw ? 4 : 0;
+                TRY(launch_scu_block(p, t, r.s));
+            }
+        } else {
+            TRY(gemm(bk.cb0, Y, D, h, wd, nullptr, 0, T, t));
+            if (!r.dry) TRY(launch_swin_lrelu(T, (int64_t)(M * t), 0.f, r.s));       // slope 0: ReLU
+            TRY(gemm(bk.cb2, T, t, h, wd, Y, D, Z, D));
+            if (!r.dry) TRY(launch_swin_layernorm(Y + t, bk.n1.g, bk.n1.b, lnb, (int64_t)M, t, D, 1e-5f, r.s));
+            TRY(gemm(bk.qkv, lnb, D, h, wd, nullptr, 0, qkv, 3 * t));
+            if (!r.dry) {
+                SwinAttnP a{};                                // -100 where the reference has -inf: the same probabilities after an fp32 softmax
+                a.qkv = qkv; a.bias = bk.bias; a.out = att; a.B = B; a.H = h; a.W = wd; a.heads = t / 32; a.D = 32;
+                a.ldq = 3 * t; a.ldo = t; a.shift = type_sw ? 4 : 0; a.scale = 0.17677669529663689f;
+                TRY(launch_swin_attention(a, r.s));
+            }
+            TRY(gemm(bk.proj, att, t, h, wd, Y + t, D, mid, t));
+            if (!r.dry) TRY(launch_swin_layernorm(mid, bk.n2.g, bk.n2.b, att, (int64_t)M, t, t, 1e-5f, r.s));
+            TRY(gemm(bk.fc1, att, t, h, wd, nullptr, 0, hid, 4 * t, EP_GELU));
+            TRY(gemm(bk.fc2, hid, 4 * t, h, wd, mid, t, Z + t, D));
+        }
+        return gemm(bk.c12, Z, D, h, wd, x, D, o, D);
+    };
+    // the blocks of a stage through the ping-pong, block i into pool[(first + i) % 2] (the caller keeps `x` out of pool[first]);
+    // *res: the buffer the result is in
+    auto stage = [&](int st, const half_t* x, int h, int wd, int first, half_t** res) -> int {
+        const half_t* cur = x;
+        for (size_t i = 0; i < n.stage[st].size(); ++i) {
+            half_t* o = pool[(first + i) & 1];
+            TRY(ctb(n.stage[st][i], (int)(i & 1), cur, o, h, wd));
+            cur = o;
+        }
+        *res = const_cast<half_t*>(cur);
+        return 0;
+    };
+
+    if (!r.dry) TRY(launch_scu_input(in, in_u8, in0, B, H, W, Hp, Wp, 32, r.s));
+    TRY(conv3(n.head, in0, 32, 32, Hp, Wp, skip[0], 64, RRDB_EP_NONE, nullptr, 0));
+    half_t* x = nullptr;
+    for (int l = 0; l < 3; ++l) {                             // m_down1 .. m_down3
+        const int h = Hp >> l, wd = Wp >> l, D = 64 << l;
+        TRY(stage(l, skip[l], h, wd, 0, &x));
+        if (!r.dry) TRY(launch_scu_patch2(x, Z, B, h / 2, wd / 2, D, 1, r.s));
+        TRY(gemm(n.down[l], Z, 4 * D, h / 2, wd / 2, nullptr, 0, skip[l + 1], 2 * D));
+    }
+    TRY(stage(3, skip[3], Hp >> 3, Wp >> 3, 0, &x));
+    for (int l = 2; l >= 0; --l) {                            // m_up3 .. m_up1 at level l: x + skip, the transposed conv, the blocks
+        const int h = Hp >> l, wd = Wp >> l, D = 64 << l;
+        if (!r.dry) TRY(launch_scu_add(x, skip[l + 1], (int64_t)B * (h / 2) * (wd / 2) * 2 * D, r.s));
+        TRY(gemm(n.up[l], x, 2 * D, h / 2, wd / 2, nullptr, 0, Z, 4 * D));
+        if (!r.dry) TRY(launch_scu_patch2(Z, x, B, h / 2, wd / 2, D, 0, r.s));       // over the GEMM's input: it is dead
+        TRY(stage(6 - l, x, h, wd, x == pool[0] ? 1 : 0, &x));
+    }
+    if (r.dry) return 0;
+    TRY(launch_scu_add(x, skip[0], (int64_t)M1 * 64, r.s));
+    TRY(conv3(n.tail, x, 64, 64, Hp, Wp, full, 0, RRDB_EP_NONE, nullptr, 0, RRDB_ST_F32_NCHW));
+    return launch_swin_output(full, out, out_u8, B, H, W, Hp, Wp, r.s);
+}
+
+static bool scunet_size_ok(int B, int H, int W) {
+    if (B <= 0 || H < 1 || W < 1) return false;
+    return (long long)B * rup(H, 64) * rup(W, 64) * 64 < (1ll << 31) - 256;
+}
+
+int64_t scunet_scratch_bytes(const sdmi_scunet* n, int B, int H, int W) {
+    if (!n || !scunet_size_ok(B, H, W)) return 0;
+    Arena ar;
+    ar.dry = true;
+    Run dry(n->e, nullptr, true, &ar);
+    if (scunet_pass(dry, *n, nullptr, 0, B, H, W, nullptr, 0) != 0) return 0;
+    return (int64_t)ar.high;
+}
+
+// in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
+// out: [B][3][H][W] fp32 NCHW, or (out_u8) uint8 HWC [B][H][W][3] = round_half_even(clamp(y, 0, 1) * 255).
+int scunet_run(sdmi_scunet* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s) {
+    SDMI_REQUIRE(n && in && out, "null argument");
+    sdmi_engine* e = n->e;
+    SDMI_REQUIRE(B > 0 && H >= 1 && W >= 1, "empty image");
+    SDMI_REQUIRE(scunet_size_ok(B, H, W), "image too large: every intermediate tensor must stay below 2^31 elements");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    const bool tiling = e->tiling;                            // p.tiling belongs to the diffusion model's convs, not to an upscaler's
+    e->tiling = false;
+    struct Restore { sdmi_engine* e; bool v; ~Restore() { e->tiling = v; } } restore{e, tiling};
+    Run dry{e, s, true};
+    e->arena.dry = true; e->arena.high = 0;
+    const int rc = scunet_pass(dry, *n, in, in_u8, B, H, W, out, out_u8);
+    e->arena.dry = false;
+    TRY(rc);
+    TRY(ensure_arena(e, e->arena.high, s));
+    Run run{e, s, false};
+    return scunet_pass(run, *n, in, in_u8, B, H, W, out, out_u8);
+}
+
 }  // namespace sdmi
+
+sdmi_scunet::~sdmi_scunet() {
+    for (void* p : owned) (void)hipFree(p);
+}
 
 sdmi_swinir::~sdmi_swinir() {
     for (void* p : owned) (void)hipFree(p);
@@ -2526,11 +2836,12 @@ sdmi_engine::~sdmi_engine() {
 }
 
 // The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units; there the upscalers'
-// and the cross-attention chain's kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip, swinir.hip and
-// xattn_chain.hip on their own (build.sh).
+// and the cross-attention chain's kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip, swinir.hip, scunet.hip
+// and xattn_chain.hip on their own (build.sh).
 #ifndef __HIP__
 #include "rrdb.hip"
 #include "compact.hip"
 #include "swinir.hip"
+#include "scunet.hip"
 #include "xattn_chain.hip"
 #endif

@@ -295,3 +295,24 @@ struct sdmi_swinir {
     std::vector<void*> owned;
     ~sdmi_swinir();
 };
+
+// ScuNET (Swin-Conv-UNet, dim 64): per ConvTransBlock the two 1x1 convs as GEMM weights, the 3x3 pair as rrdb_conv (widths 32 / 64) or
+// GEMM (128 / 256) weights, and the transformer Block either as one scu_block pack (trans_dim 32 / 64) or as the GEMM weights of the
+// swin_layernorm + conv_gemm + swin_window_attn route (128 / 256).  Activations come from the owning engine's arena; the net is immutable
+// after sdmi_scunet_create.
+struct sdmi_scunet {
+    struct Block {
+        int c = 0;                            // conv_dim = trans_dim
+        sdmi::ConvW c11, c12, cb0, cb2;
+        float* bias = nullptr;                // [c / 32][64][64]
+        void* packs = nullptr;                // c <= 64
+        sdmi::NormW n1, n2;                   // c >= 128
+        sdmi::ConvW qkv, proj, fc1, fc2;
+    };
+    sdmi_engine* e = nullptr;
+    sdmi_scunet_config cfg{};
+    sdmi::ConvW head, tail, down[3], up[3];   // down[l]: level l -> l + 1 (K = 4 Cin); up[l]: level l + 1 -> l (N = 4 Cout)
+    std::vector<Block> stage[7];              // m_down1, m_down2, m_down3, m_body, m_up3, m_up2, m_up1
+    std::vector<void*> owned;
+    ~sdmi_scunet();
+};

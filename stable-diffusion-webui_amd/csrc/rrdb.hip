@@ -1,6 +1,7 @@
 // rrdb.hip — the 3x3 convolution of the RRDBNet upscalers (ESRGAN / Real-ESRGAN; BasicSR basicsr/archs/rrdbnet_arch.py) for gfx950.
 //
-// One shape family: stride 1, pad 1, at most 192 input channels, 32 or 64 output channels, LeakyReLU(0.2) or a scaled residual after it.
+// One shape family: stride 1, pad 1, at most 192 input channels, 32 or 64 output channels, LeakyReLU(0.2), ReLU (ScuNET's conv_block) or a
+// scaled residual after it.
 // A dense block's cat(x, x1, ..., xk) is never built: the block lives in ONE 192-channel NHWC buffer, a conv reads the first `cin`
 // channels of its rows (row stride lda) and writes its NOUT channels at a channel offset into rows of stride ldo.
 //
@@ -154,6 +155,9 @@ __global__ __launch_bounds__(256) void rrdb_conv_kernel(const RrdbP p) {
             if (p.ep == RRDB_EP_LRELU) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.2f * v[r];
+            } else if (p.ep == RRDB_EP_RELU) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
             } else if (p.ep >= RRDB_EP_RES1) {
                 const h4 r1 = *reinterpret_cast<const h4*>(p.r1 + m * p.ldr1 + n0);
 #pragma unroll
@@ -228,11 +232,11 @@ int launch_rrdb_conv(const RrdbP& pin, int nout, hipStream_t s) {
     SDMI_REQUIRE(!p.up || (p.H % 2 == 0 && p.W % 2 == 0), "the x2 gather writes an even output grid");
     SDMI_REQUIRE((long long)p.B * p.H * p.W < (1ll << 31) - 256, "B*H*W must stay below 2^31 pixels");
     SDMI_REQUIRE(p.n_real >= 1 && p.n_real <= nout, "n_real in [1, NOUT]");
-    SDMI_REQUIRE(p.ep >= RRDB_EP_NONE && p.ep <= RRDB_EP_RES2, "unknown epilogue");
+    SDMI_REQUIRE(p.ep >= RRDB_EP_NONE && p.ep <= RRDB_EP_RELU, "unknown epilogue");
     SDMI_REQUIRE(p.store >= RRDB_ST_F16 && p.store <= RRDB_ST_U8_HWC, "unknown store form");
     if (p.store == RRDB_ST_F16)
         SDMI_REQUIRE(p.ldo >= p.n_real && p.ldo % 4 == 0 && ((uintptr_t)p.out & 7) == 0, "fp16 output rows: 8-byte aligned channel slots");
-    if (p.ep >= RRDB_EP_RES1)
+    if (p.ep == RRDB_EP_RES1 || p.ep == RRDB_EP_RES2)
         SDMI_REQUIRE(p.r1 && p.ldr1 >= nout && p.ldr1 % 4 == 0 && ((uintptr_t)p.r1 & 7) == 0 && p.n_real == nout,
                      "residual r1: 8-byte aligned rows of at least NOUT channels, all NOUT channels stored");
     if (p.ep == RRDB_EP_RES2)

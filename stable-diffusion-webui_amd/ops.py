@@ -317,7 +317,8 @@ def rrdb_conv(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tens
             setattr(d, "ld" + name, r.shape[3])
     d.B, d.H, d.W, d.cin, d.lda, d.up = b, ho, wo, cin, lda, 1 if up else 0
     d.nout, d.n_real = nout, n_real
-    d.ep = {"none": _lib.RRDB_EP_NONE, "lrelu": _lib.RRDB_EP_LRELU, "res1": _lib.RRDB_EP_RES1, "res2": _lib.RRDB_EP_RES2}[ep]
+    d.ep = {"none": _lib.RRDB_EP_NONE, "lrelu": _lib.RRDB_EP_LRELU, "res1": _lib.RRDB_EP_RES1, "res2": _lib.RRDB_EP_RES2,
+            "relu": _lib.RRDB_EP_RELU}[ep]
     d.store = {"f16": _lib.RRDB_ST_F16, "f32_nchw": _lib.RRDB_ST_F32_NCHW, "u8_hwc": _lib.RRDB_ST_U8_HWC}[store]
     d.alpha, d.beta = alpha, beta
     if store == "f16":
@@ -427,4 +428,42 @@ def swin_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps
     assert out.dtype == torch.float16 and out.is_contiguous() and out.shape == x.shape
     check(lib.sdmi_swin_layernorm(ptr(x), ptr(gamma.float().contiguous()), ptr(beta.float().contiguous()), ptr(out), x.numel() // ld, c, ld,
                                   float(eps), stream_ptr()), "sdmi_swin_layernorm")
+    return out
+
+
+def scu_block_pack(ln1_g, ln1_b, wqkv, bqkv, wproj, bproj, ln2_g, ln2_b, w1, b1, w2, b2) -> torch.Tensor:
+    """The weights of one ScuNET transformer Block (torch layouts; C = len(ln1_g) in {32, 64}) -> the uint8 operand image scu_block reads
+    (sdmi_scu_block_pack): matrices as fp16, vectors as fp32."""
+    _lib.require_device()
+    c = ln1_g.numel()
+    n = int(lib.sdmi_scu_block_pack_bytes(c))
+    if n <= 0:
+        raise _lib.SdmiError(f"sdmi_scu_block_pack_bytes: scu_block is built for C = 32 and 64, not {c}")
+    mats = [t.half().contiguous() for t in (wqkv, wproj, w1, w2)]
+    vecs = [t.float().contiguous() for t in (ln1_g, ln1_b, bqkv, bproj, ln2_g, ln2_b, b1, b2)]
+    packs = torch.empty(n, dtype=torch.uint8, device=wqkv.device)
+    check(lib.sdmi_scu_block_pack(ptr(vecs[0]), ptr(vecs[1]), ptr(mats[0]), ptr(vecs[2]), ptr(mats[1]), ptr(vecs[3]), ptr(vecs[4]), ptr(vecs[5]),
+                                  ptr(mats[2]), ptr(vecs[6]), ptr(mats[3]), ptr(vecs[7]), ptr(packs), c, stream_ptr()), "sdmi_scu_block_pack")
+    return packs
+
+
+def scu_block(x: torch.Tensor, packs: torch.Tensor, bias: torch.Tensor, c: int, shift: int = 0, col: int = 0,
+              out: Optional[torch.Tensor] = None, out_col: int = 0) -> torch.Tensor:
+    """The transformer Block of a ScuNET ConvTransBlock as one launch (csrc/scunet.hip; window 8, head dim 32, trans_dim c = 32 | 64):
+    x + msa(ln1(x)), then + mlp(ln2(.)), of Block.forward.  x fp16 [B, H, W, ldx]: columns col .. col + c - 1 are the input; bias fp32
+    [c / 32, 64, 64]; shift 0 ('W') | 4 ('SW') -> fp16 [B, H, W, ldo], the result in columns out_col .. out_col + c - 1 (a fresh dense
+    [B, H, W, c] tensor without `out`; the other columns of `out` keep their bits; `out` may be `x`)."""
+    _lib.require_device()
+    assert x.dtype == torch.float16 and x.dim() == 4 and x.is_contiguous()
+    b, h, w, ldx = x.shape
+    bias = bias.float().contiguous()
+    if out is None:
+        out = torch.empty((b, h, w, c), dtype=torch.float16, device=x.device)
+    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape[:3]) == (b, h, w)
+    desc = _lib.ScuBlockDesc()
+    desc.x, desc.out = x.data_ptr() + 2 * col, out.data_ptr() + 2 * out_col
+    desc.packs, desc.bias = packs.data_ptr(), bias.data_ptr()
+    desc.B, desc.H, desc.W, desc.C = b, h, w, c
+    desc.ldx, desc.ldo, desc.shift = ldx, out.shape[3], shift
+    check(lib.sdmi_scu_block(C.byref(desc), stream_ptr()), "sdmi_scu_block")
     return out

@@ -6,7 +6,7 @@ up in (modules/images.py:276, modules/modelloader.py:136), the ``Upscaler.upscal
 the three built-in PIL scalers (None / Lanczos / Nearest, modules/upscaler.py:107-154).  The RRDBNet family (ESRGAN, Real-ESRGAN) and the
 compact Real-ESRGAN models (SRVGGNetCompact: General 4xV3, General WDN 4xV3, AnimeVideo) run on the engine (``UpscalerESRGAN`` /
 ``register_esrgan`` below, csrc/rrdb.hip and csrc/compact.hip), and so do the SwinIR models with the nearest+conv upsampler
-(``SwinIRNet``, csrc/swinir.hip); other model upscalers register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)``
+(``SwinIRNet``, csrc/swinir.hip) and the ScuNET models (``ScuNETNet``, csrc/scunet.hip); other model upscalers register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)``
 is called as in the reference.
 """
 from __future__ import annotations
@@ -303,11 +303,75 @@ def parse_swinir_state_dict(sd):
     return np.ascontiguousarray(np.concatenate(parts)), config
 
 
+SCUNET_MARKS = ("m_head.0.weight", "m_down1.0.trans_block.msa.relative_position_params")
+SCUNET_STAGES = ("m_down1", "m_down2", "m_down3", "m_body", "m_up3", "m_up2", "m_up1")
+
+
+def parse_scunet_state_dict(sd):
+    """Checkpoint state dict of a SCUNet (network_scunet.py; the webui's "ScuNET GAN" / "ScuNET PSNR": in_nc 3, dim 64, config [4] * 7) ->
+    (blob, config): the engine's weight blob (fp32, every tensor flattened in the order include/sdmi.h documents at sdmi_scunet_config:
+    m_head; per stage the ConvTranspose2d (m_up*), its blocks' ln1, relative_position_params, embedding_layer, linear, ln2, mlp.0,
+    mlp.2, conv1_1, conv1_2, conv_block.0, conv_block.2, the stride-2 Conv2d (m_down*); m_tail) and config = dict(depths, dim, scale),
+    the depths read by counting blocks.  Host only.  Raises ValueError on what the engine's kernels are not built for: dim other than
+    64, a window other than 8, in_nc other than 3, and on missing or misshapen tensors."""
+    sd = _unwrap_state_dict(sd)
+    if any(k not in sd for k in SCUNET_MARKS):
+        raise ValueError(f"not a ScuNET checkpoint: no {' / '.join(k for k in SCUNET_MARKS if k not in sd)}")
+    head = sd["m_head.0.weight"]
+    dim, in_nc = int(head.shape[0]), int(head.shape[1])
+    if in_nc != 3:
+        raise ValueError(f"ScuNET m_head takes in_nc = {in_nc} channels: the engine runs the colour models (3)")
+    if dim != 64:
+        raise ValueError(f"ScuNET dim = {dim}: the engine's kernels are built for 64")
+    params = sd[SCUNET_MARKS[1]]
+    if tuple(params.shape[1:]) != (15, 15):
+        side = int(params.shape[-1])
+        raise ValueError(f"ScuNET window_size {(side + 1) // 2} (relative_position_params {tuple(params.shape)}): the engine's kernels are "
+                         f"built for 8 ([heads][15][15])")
+    depths = []
+    for st, stem in enumerate(SCUNET_STAGES):
+        first = 1 if st > 3 else 0                           # m_up*: the ConvTranspose2d sits at index 0
+        blocks = sorted({int(m.group(1)) for k in sd for m in [re.match(rf"{stem}\.(\d+)\.conv1_1\.weight$", k)] if m})
+        if not blocks or blocks != list(range(first, first + len(blocks))):
+            raise ValueError(f"ScuNET {stem}: blocks are not {first}..n: {blocks}")
+        depths.append(len(blocks))
+    want = [("m_head.0.weight", (64, 3, 3, 3))]
+    for st, (stem, depth) in enumerate(zip(SCUNET_STAGES, depths)):
+        c = 32 << (st if st < 4 else 6 - st)
+        d = 2 * c
+        first = 1 if st > 3 else 0
+        if st > 3:
+            want.append((f"{stem}.0.weight", (2 * d, d, 2, 2)))
+        for i in range(first, first + depth):
+            b, t = f"{stem}.{i}.", f"{stem}.{i}.trans_block."
+            want += [(t + "ln1.weight", (c,)), (t + "ln1.bias", (c,)), (t + "msa.relative_position_params", (c // 32, 15, 15)),
+                     (t + "msa.embedding_layer.weight", (3 * c, c)), (t + "msa.embedding_layer.bias", (3 * c,)),
+                     (t + "msa.linear.weight", (c, c)), (t + "msa.linear.bias", (c,)), (t + "ln2.weight", (c,)), (t + "ln2.bias", (c,)),
+                     (t + "mlp.0.weight", (4 * c, c)), (t + "mlp.0.bias", (4 * c,)), (t + "mlp.2.weight", (c, 4 * c)), (t + "mlp.2.bias", (c,)),
+                     (b + "conv1_1.weight", (d, d, 1, 1)), (b + "conv1_1.bias", (d,)), (b + "conv1_2.weight", (d, d, 1, 1)),
+                     (b + "conv1_2.bias", (d,)), (b + "conv_block.0.weight", (c, c, 3, 3)), (b + "conv_block.2.weight", (c, c, 3, 3))]
+        if st < 3:
+            want.append((f"{stem}.{depth}.weight", (2 * d, d, 2, 2)))
+    want.append(("m_tail.0.weight", (3, 64, 3, 3)))
+    parts = []
+    for name, shape in want:
+        t = sd.get(name)
+        if t is None:
+            raise ValueError(f"ScuNET checkpoint lacks {name}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"ScuNET {name}: {tuple(t.shape)}, expected {shape}")
+        parts.append(_as_f32(t))
+    return np.ascontiguousarray(np.concatenate(parts)), dict(depths=tuple(depths), dim=dim, scale=1)
+
+
 def upscaler_family(sd):
-    """"rrdb" | "compact" | "swinir" by the key layout: the first block's attn.qkv.weight marks a SwinIR network (it has a conv_first.weight
-    too, so this test comes first); conv_first.weight / model.0.weight mark an RRDBNet, a 4-d body.0.weight without them a compact
-    network.  Anything else counts as "rrdb" and gets that loader's refusal."""
+    """"scunet" | "swinir" | "rrdb" | "compact" by the key layout: m_head.0.weight together with the first block's
+    relative_position_params marks a ScuNET; the first block's attn.qkv.weight marks a SwinIR network (it has a conv_first.weight
+    too, so this test comes before the next); conv_first.weight / model.0.weight mark an RRDBNet, a 4-d body.0.weight without them a
+    compact network.  Anything else counts as "rrdb" and gets that loader's refusal."""
     keys = _unwrap_state_dict(sd)
+    if all(k in keys for k in SCUNET_MARKS):
+        return "scunet"
     if SWINIR_MARK in keys:
         return "swinir"
     if "conv_first.weight" not in keys and "model.0.weight" not in keys and len(getattr(keys.get("body.0.weight"), "shape", ())) == 4:
@@ -317,10 +381,11 @@ def upscaler_family(sd):
 
 def parse_upscaler_state_dict(sd):
     """The dispatcher over the checkpoints the engine runs -> ("rrdb", parse_esrgan_state_dict(sd)), ("compact",
-    parse_compact_state_dict(sd)) or ("swinir", (blob, config, scale)); the scale is the last member of each tuple."""
+    parse_compact_state_dict(sd)), ("swinir", (blob, config, scale)) or ("scunet", (blob, config, 1)); the scale is the last member of
+    each tuple."""
     family = upscaler_family(sd)
-    if family == "swinir":
-        blob, config = parse_swinir_state_dict(sd)
+    if family in ("swinir", "scunet"):
+        blob, config = (parse_swinir_state_dict if family == "swinir" else parse_scunet_state_dict)(sd)
         return family, (blob, config, config["scale"])
     return family, (parse_compact_state_dict if family == "compact" else parse_esrgan_state_dict)(sd)
 
@@ -535,9 +600,73 @@ class SwinIRNet:
         return out
 
 
+class ScuNETNet:
+    """One SCUNet (dim 64) resident on an engine (sdmi_scunet_*): the twin of EsrganNet, scale 1."""
+
+    def __init__(self, state_dict, device=0, engine=None):
+        from . import _lib
+        from .engine import Engine
+        blob, self.config = parse_scunet_state_dict(state_dict)
+        self.scale = 1
+        self.device = int(device)
+        self.engine = engine or Engine(self.device)
+        cfg = _lib.ScuNETConfigC()
+        for i, d in enumerate(self.config["depths"]):
+            cfg.depths[i] = d
+        import ctypes
+        self.handle = _lib.lib.sdmi_scunet_create(self.engine.handle, blob.ctypes.data, blob.size, ctypes.byref(cfg))
+        if not self.handle:
+            raise _lib.SdmiError("sdmi_scunet_create failed: " + _lib.last_error())
+
+    def close(self):
+        if getattr(self, "handle", None):
+            from . import _lib
+            _lib.lib.sdmi_scunet_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def scratch_bytes(self, b, h, w):
+        """Arena bytes of one run, from the engine's own layout (sdmi_scunet_scratch_bytes; 0 for a size the engine refuses)."""
+        from . import _lib
+        return int(_lib.lib.sdmi_scunet_scratch_bytes(self.handle, b, h, w))
+
+    def check_fits(self, b, h, w):
+        """Refuse an input whose intermediates (the skip tensors and the level-1 work buffers of the grid padded to multiples of 64) the
+        arena cannot hold, or one of whose tensors passes 2^31 elements."""
+        need = self.scratch_bytes(b, h, w)
+        limit = arena_limit_bytes(self.device) + self.engine.arena_bytes()
+        if need <= 0 or need > limit:
+            raise EsrganInputTooLarge(f"image {w}x{h} (batch {b}) is too large for ScuNET: its intermediates need "
+                                      f"{need / 2 ** 30:.1f} GiB of engine arena, {limit / 2 ** 30:.1f} GiB are available"
+                                      if need > 0 else
+                                      f"image {w}x{h} (batch {b}) is too large for ScuNET: a tensor passes 2^31 elements")
+
+    def run(self, x, out_u8=False):
+        """x: uint8 [B,H,W,3] (RGB; divided by 255 on the way in) or fp32 [B,3,H,W] in [0, 1], on the engine's device ->
+        fp32 [B,3,H,W], or with out_u8 uint8 [B,H,W,3] (clamp, x255, round half to even).  Any H, W >= 1: the replicate padding to
+        multiples of 64 and the crop happen on the device."""
+        import torch
+        from . import _lib
+        in_u8 = x.dtype == torch.uint8
+        x = x.contiguous() if in_u8 else x.float().contiguous()
+        b, h, w = (x.shape[0], x.shape[1], x.shape[2]) if in_u8 else (x.shape[0], x.shape[2], x.shape[3])
+        assert x.shape[3 if in_u8 else 1] == 3
+        self.check_fits(b, h, w)
+        out = (torch.empty((b, h, w, 3), dtype=torch.uint8, device=x.device) if out_u8
+               else torch.empty((b, 3, h, w), dtype=torch.float32, device=x.device))
+        _lib.check(_lib.lib.sdmi_scunet_run(self.handle, _lib.ptr(x), 1 if in_u8 else 0, b, h, w, _lib.ptr(out), 1 if out_u8 else 0,
+                                            _lib.stream_ptr()), "sdmi_scunet_run")
+        return out
+
+
 def make_upscaler_net(state_dict, device=0, engine=None):
-    """EsrganNet, CompactNet or SwinIRNet, by the checkpoint's key layout (upscaler_family)."""
-    cls = {"compact": CompactNet, "swinir": SwinIRNet}.get(upscaler_family(state_dict), EsrganNet)
+    """EsrganNet, CompactNet, SwinIRNet or ScuNETNet, by the checkpoint's key layout (upscaler_family)."""
+    cls = {"compact": CompactNet, "swinir": SwinIRNet, "scunet": ScuNETNet}.get(upscaler_family(state_dict), EsrganNet)
     return cls(state_dict, device=device, engine=engine)
 
 
@@ -547,7 +676,9 @@ class UpscalerESRGAN(Upscaler):
     VRAM this card does not lack), with the uint8 hand-off of modules/upscaler_utils.py.  RRDBNet checkpoints run as EsrganNet, the
     compact Real-ESRGAN models (General 4xV3, General WDN 4xV3, AnimeVideo) as CompactNet.  SwinIR checkpoints (nearest+conv upsampler)
     run as SwinIRNet: what extensions-builtin/SwinIR's UpscalerSwinIR.do_upscale computes with the image in one tile (SWIN_tile exists
-    for the same VRAM reason as ESRGAN_tile), the padding to the window size done on the device."""
+    for the same VRAM reason as ESRGAN_tile), the padding to the window size done on the device.  ScuNET checkpoints run as ScuNETNet:
+    extensions-builtin/ScuNET's UpscalerScuNET.do_upscale with the image in one tile; the result has the input's size and the driver
+    loop of Upscaler.upscale fits it with Lanczos."""
     name = "ESRGAN"
 
     def __init__(self, device=0, engine=None):
@@ -585,8 +716,8 @@ class UpscalerESRGAN(Upscaler):
 def register_esrgan(paths, device=0, engine=None):
     """Append one ``UpscalerData(name, path, scaler, scale)`` per checkpoint to shared.sd_upscalers (after the built-ins, which are
     installed first if the list is empty): `paths` is a {name: path} mapping or a list of paths (name = the file's stem), so
-    hr_upscaler="R-ESRGAN 4x+" and opts.upscaler_for_img2img resolve through _resize_to.  RRDBNet, compact (SRVGGNetCompact) and SwinIR
-    checkpoints may be mixed; the scale is read from the checkpoint.
+    hr_upscaler="R-ESRGAN 4x+" and opts.upscaler_for_img2img resolve through _resize_to.  RRDBNet, compact (SRVGGNetCompact), SwinIR
+    and ScuNET checkpoints may be mixed; the scale is read from the checkpoint.
     engine: see UpscalerESRGAN (all entries of one call share one scaler object and so one engine)."""
     if not shared.sd_upscalers:
         shared.sd_upscalers = builtin_upscalers()

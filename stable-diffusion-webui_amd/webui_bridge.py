@@ -726,12 +726,27 @@ def install_swinir_hook(webui_shared, device_index: int = 0):
     instead of as a torch module in SWIN_tile tiles.  The same fall-back rules: a URL that is not on disk yet, a checkpoint the loader
     refuses (another upsampler or window size, ape, head dim > 32) or that fails to load or pack, and an image too large for the arena
     stay on the stock path.  Returns the names of the hooked entries."""
+    return _install_whole_image_hook(webui_shared, device_index, "UpscalerSwinIR")
+
+
+def install_scunet_hook(webui_shared, device_index: int = 0):
+    """Point the webui's ScuNET scaler objects (extensions-builtin/ScuNET/scripts/scunet_model.py: "ScuNET GAN", "ScuNET PSNR") at the
+    engine: install_swinir_hook for the entries of ``webui_shared.sd_upscalers`` whose scaler class is UpscalerScuNET.
+    ``do_upscale(img, selected_file)`` runs the checkpoint as sdmi_scunet_run on the image whole instead of as a torch module in
+    SCUNET_tile tiles; the result has the input's size, as the stock model's, and ``Upscaler.upscale`` fits it.  The same fall-back rules:
+    a URL that is not on disk yet, a checkpoint the loader refuses (dim other than 64, another window size, a grey-scale model) or that
+    fails to load or pack, and an image too large for the arena stay on the stock path.  Idempotent.  Returns the names of the hooked
+    entries."""
+    return _install_whole_image_hook(webui_shared, device_index, "UpscalerScuNET")
+
+
+def _install_whole_image_hook(webui_shared, device_index, scaler_class):
     from . import upscaler as amd_upscaler
     engine_scaler = amd_upscaler.UpscalerESRGAN(device_index)
     hooked = []
     for data in getattr(webui_shared, "sd_upscalers", []):
         scaler = getattr(data, "scaler", None)
-        if scaler is None or type(scaler).__name__ != "UpscalerSwinIR":
+        if scaler is None or type(scaler).__name__ != scaler_class:
             continue
         hooked.append(data.name)
         if hasattr(scaler.do_upscale, "_mi355x_stock"):
