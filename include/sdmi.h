@@ -69,6 +69,16 @@ int sdmi_attention_vt(const void* q, const void* k, const void* vt, void* out,
                       int B, int H, int N, int M, int D,
                       int ldq, int ldk, int vt_ld, int ldo, float scale, int force_generic, void* stream);
 
+/* sdmi_attention_vt with the operands' scaling and the kernel form stated by the caller (tests and timing tools).
+ *   prescaled != 0: q and k are ALREADY multiplied by sqrt(scale * log2(e)) each — as the engine's stacked q | k projection leaves them
+ *                   for the level-0 self-attention — and `scale` is ignored;
+ *   form:           0 = the default dispatch; otherwise an "attn_occ" value that holds for this call only (d = 40: 15, 16, 17, and 27 = 17 for pre-scaled
+ *                   operands with the staging address arithmetic out of the KV loop; 27 without prescaled is an error).  The form travels with the call: no
+ *                   process-wide knob is touched, other threads' launches are not affected. */
+int sdmi_attention_vt_ex(const void* q, const void* k, const void* vt, void* out,
+                         int B, int H, int N, int M, int D,
+                         int ldq, int ldk, int vt_ld, int ldo, float scale, int prescaled, int form, int force_generic, void* stream);
+
 /* Implicit-GEMM convolution / linear layer on NHWC fp16 activations (MFMA, LDS-staged):
  *   out[m, n] = epilogue( alpha * sum_{tap,c} A(m, tap, c) * W[n, tap*Cin + c] )
  * Replaces the torch ops issued by ldm's ResBlock / Downsample / Upsample / SpatialTransformer / FeedForward modules

@@ -61,6 +61,8 @@ __device__ __forceinline__ float tree_max(const f16v (&sc)[NKB]) {
 //      8 V^T fragments right after the last one, landing under the softmax): 14 exposed LDS latencies per KV tile become 2; the
 //      half-wave max exchange is one v_permlane32_swap instead of a ds_bpermute round trip; 160 VGPRs, 3 workgroups per CU.
 //      Same products in the same order per accumulator: bit-identical to 0 and 5 (tests/test_gpu_ops.py).
+//  17  15 with the softmax scale and shift folded into the S^T MFMA (FOLD, below); 27 = 17 for pre-scaled q and k with the staging address
+//      arithmetic out of the KV loop: where the engine's level-0 self-attention goes (attn_takes_prescaled)
 //  10..14, 18  (-DSDMI_ATTN_PARTS builds only, tools/gpu/attn_parts.py) 5 with one component removed / 15 with section timers
 // FOLD forms: the softmax scale c = scale * log2(e) is split as c = 2^e * fr, fr in [1, 2).  Q is multiplied by 2^e — EXACT in fp16, where
 // rounding Q * c to fp16 put a relative 2^-11 of every product q_i k_i into the score: 3.9e-3 on a query row that meets one key of 6x
@@ -69,15 +71,28 @@ __device__ __forceinline__ float tree_max(const f16v (&sc)[NKB]) {
 __device__ __forceinline__ float fold_p2(float c) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, c) & 0x7F800000u); }
 
 template <int D, int KVT, int VAR = 0>
-__global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR == 18) ? 3 : (VAR == 5 || VAR >= 10) ? 4 : D <= 80 ? 2 : 1)) void attn_mfma_kernel(AttnP p) {
+__global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR == 18 || VAR == 27) ? 3 : (VAR == 5 || VAR >= 10) ? 4 : D <= 80 ? 2 : 1)) void attn_mfma_kernel(AttnP p) {
     constexpr bool LAZY_RESCALE = VAR >= 5;
-    constexpr bool PREF = VAR == 15 || VAR == 16 || VAR == 17 || VAR == 18;
+    // 27 = 17 with everything the result does not need taken out of the KV loop (level-0 self-attention; profiles/attn_l0_time.md):
+    //  * STAGE: every thread's byte offsets inside a tile (row, chunk, clamped column) are computed once ahead of the loop and a full tile
+    //    is addressed as (block-uniform tile base) + (that 32-bit offset) — no per-tile clamp, no 64-bit row * ldk product per load.  Only a
+    //    ragged last tile (t >= nfull) still goes through the clamping load_tile.  Same MFMA operands in the same order as 17.
+    //  * PRESC: q and k arrive already multiplied by sqrt(scale * log2(e)) (AttnP::prescaled: the engine's stacked q | k projection applies
+    //    it to its fp32 accumulators, so both are still rounded to fp16 once): K Q^T is in the log2 domain as it leaves the MFMA, fr == 1,
+    //    and the 16 v_pk_mul_f32 per tile in front of exp2 disappear with the 2^e multiply of the Q fragments.  On the same pre-scaled
+    //    operands form 17 (scale left to apply: 1) computes the same bits.
+    // (STAGE alone, as a form 19 for unscaled operands, was bit-identical to 17 and 3 % shorter isolated, but -0.47 % on the forward did not
+    // clear the A/B margin by itself and it was taken out again.)
+    constexpr bool STAGE = VAR == 27;
+    constexpr bool PRESC = VAR == 27;
+    constexpr bool PREF = VAR == 15 || VAR == 16 || VAR == 17 || VAR == 18 || STAGE;
     // 17 = 15 with the softmax scale and shift folded into the S^T MFMA (head sizes with a spare contraction column: d = 40 -> 48), as in
     // attn_pp_kernel's FOLD form: Q is multiplied by the power-of-two part of scale * log2(e) when its fragments are loaded (fold_p2), K's
     // padding column holds 1.0 and Q's padding element -shift, so the accumulators ARE s * 2^e - shift and exp2 applies to fr times them:
     // the per-tile alpha bookkeeping disappears and the 16 v_pk_fma_f32 per tile become 16 v_pk_mul_f32.  shift is an fp16 number >= every score seen
     // so far (P <= 1); it is raised — scores re-based, O rescaled, Q's padding element rewritten — only when a tile's maximum exceeds it.
-    constexpr bool FOLD = VAR == 17 && ((D + 15) / 16 * 16) > D;
+    constexpr bool FOLD = (VAR == 17 || STAGE) && ((D + 15) / 16 * 16) > D;
+    static_assert(!STAGE || (FOLD && KVT == 64), "form 27: folded shift, 64-key tiles (no V^T column clamp)");
     constexpr bool TREEMAX = VAR == 16;      // 16 = 15 with the tile maximum taken as a v_max3 tree (serial depth 4 instead of 16)
     constexpr bool TIMING = VAR == 18;       // s_memtime stamps around the sections of an iteration (AttnP::dbg)
     long long tm[6] = {0, 0, 0, 0, 0, 0};
@@ -139,7 +154,7 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
             const int d = dc * 16 + half * 8;
             h8 v = {0, 0, 0, 0, 0, 0, 0, 0};
             if (qok && d < D) v = *reinterpret_cast<const h8*>(qptr + d);
-            if constexpr (FOLD) {
+            if constexpr (FOLD && !PRESC) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = (half_t)((float)v[e] * fold_p2(p.scale_log2));      // exact: a power of two
             }
@@ -179,6 +194,43 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
             int col = key0 + c * 8;
             if (KVT > 64) col = min(col, p.vt_ld - 8);
             vr[it] = *reinterpret_cast<const u4v*>(vbase + (long)min(row, D - 1) * p.vt_ld + col);
+        }
+    };
+    // STAGE: byte offsets of this thread's chunks inside a FULL tile, fixed for the whole launch (launch_attention admits the form only
+    // where they fit 32 bits).  Threads past the end of the K tile (idx >= KCH) re-read its last row: never a row of the next tile, which
+    // for the last full tile could lie past M.  V^T columns: key0 + 8c + 8 <= M <= vt_ld in a full tile.
+    [[maybe_unused]] unsigned koff[STAGE ? K_IT : 1], voff[STAGE ? V_IT : 1];
+    if constexpr (STAGE) {
+#pragma unroll
+        for (int it = 0; it < K_IT; ++it) {
+            const int idx = it * 256 + tid;
+            const int row = idx / KCPR, c = idx - row * KCPR;
+            const int cc = (DK == D || c * 8 < D) ? c : 0;
+            koff[it] = (unsigned)(min(row, KVT - 1) * p.ldk + cc * 8) * 2u;
+        }
+#pragma unroll
+        for (int it = 0; it < V_IT; ++it) {
+            const int idx = it * 256 + tid;
+            const int row = idx / VCPR, c = idx - row * VCPR;
+            voff[it] = (unsigned)(min(row, D - 1) * p.vt_ld + c * 8) * 2u;
+        }
+    }
+    auto load_full_tile = [&](int t) {
+        if constexpr (STAGE) {
+            const char* kt = reinterpret_cast<const char*>(kbase) + (long)t * KVT * p.ldk * 2;      // block-uniform: scalar arithmetic
+            const char* vt = reinterpret_cast<const char*>(vbase) + (long)t * KVT * 2;
+            // (the empty asm keeps the zero-extension of the offset beside its load: hoisted out of the loop it becomes a 64-bit register
+            // pair per load and the scalar-base + 32-bit-offset addressing mode of global_load is lost to a 64-bit add per load)
+#pragma unroll
+            for (int it = 0; it < K_IT; ++it) {
+                asm volatile("" : "+v"(koff[it]));
+                kr[it] = *reinterpret_cast<const u4v*>(kt + koff[it]);
+            }
+#pragma unroll
+            for (int it = 0; it < V_IT; ++it) {
+                asm volatile("" : "+v"(voff[it]));
+                vr[it] = *reinterpret_cast<const u4v*>(vt + voff[it]);
+            }
         }
     };
     auto write_tile = [&](int buf) {
@@ -241,6 +293,11 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
         const int cur = t & 1;
         const bool more = !NO_STAGE && t + 1 < ntiles;
         const long long ta = stamp();
+        if constexpr (STAGE) {
+            // block-uniform: the clamping loads only for a ragged last tile
+            if (t + 1 < nfull) load_full_tile(t + 1);
+            else if (more) load_tile(t + 1);
+        } else
         if (more) load_tile(t + 1);
         const char* tile = smem + (NO_STAGE ? 0 : cur) * TILE_BYTES;
 
@@ -300,8 +357,8 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
         h8 pb[NKB][2];
         long long tc = 0;
         if constexpr (FOLD) {
-            // the accumulators are t = s * 2^e - shift already; the exponent is fr * t
-            const float fr = p.scale_log2 / fold_p2(p.scale_log2);
+            // the accumulators are t = s * 2^e - shift already; the exponent is fr * t (PRESC: the exponent itself, fr == 1)
+            const float fr = PRESC ? 1.f : p.scale_log2 / fold_p2(p.scale_log2);
             const f2v fr2 = {fr, fr};
             float mx = -INFINITY;
 #pragma unroll
@@ -313,7 +370,9 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
             mx = fmaxf(mlo, mhi);
             // per query; the first tile always sets the shift (it may be negative); later tiles raise it only when a score exceeds it by
             // more than tau (AttnP::tau: P <= 2^tau until then)
-            const bool up = t == 0 || mx * fr > fmaxf(p.tau, 0.f);
+            bool up;
+            if constexpr (PRESC) up = t == 0 || mx > fmaxf(p.tau, 0.f);
+            else up = t == 0 || mx * fr > fmaxf(p.tau, 0.f);
             if (__builtin_amdgcn_ballot_w64(up) != 0) {
                 asm volatile("");                                 // a real (wave-uniform) branch: rare after the first few tiles
                 // new shift = the smallest fp16 number >= shift + mx (both halves of the wave compute the same value for a query)
@@ -328,7 +387,9 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
                 }
                 const float delta = up ? f - shift : 0.f;         // exact: both are fp16 numbers
                 if (up) shift = f;
-                const float alpha = __builtin_amdgcn_exp2f(-delta * fr);
+                float alpha;
+                if constexpr (PRESC) alpha = __builtin_amdgcn_exp2f(-delta);
+                else alpha = __builtin_amdgcn_exp2f(-delta * fr);
 #pragma unroll
                 for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
@@ -343,7 +404,8 @@ __global__ __launch_bounds__(256, ((VAR == 15 || VAR == 16 || VAR == 17 || VAR =
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
-                    const f2v y = f2v{sc[kb][r], sc[kb][r + 1]} * fr2;               // v_pk_mul_f32
+                    f2v y = f2v{sc[kb][r], sc[kb][r + 1]};
+                    if constexpr (!PRESC) y = y * fr2;                              // v_pk_mul_f32
                     pb[kb][r >> 3][r & 7] = (half_t)__builtin_amdgcn_exp2f(y.x);
                     pb[kb][r >> 3][(r & 7) + 1] = (half_t)__builtin_amdgcn_exp2f(y.y);
                 }
@@ -988,15 +1050,42 @@ static int launch_attn_pp(const AttnP& p, hipStream_t s) {
     return 0;
 }
 
+// 1 (default): the engine hands the level-0 self-attention q and k pre-scaled (form 27) wherever attn_takes_prescaled allows it; 0: never —
+// exactly the launches made before form 27 existed (SDMI_ATTN_PRESCALE / sdmi_debug_set("attn_prescale", v)).  Same-box A/Bs of the C1
+// forward and job: profiles/attn_l0_time.md
+int g_attn_prescale = [] { const char* e = getenv("SDMI_ATTN_PRESCALE"); return e ? atoi(e) : 1; }();
+
+// form 27 addresses a full tile as (uniform base) + (per-thread 32-bit byte offset)
+static bool attn_stage_fits(const AttnP& p) {
+    return 64.0 * p.ldk * 2 < 2147483648.0 && (double)p.D * p.vt_ld * 2 < 2147483648.0;
+}
+static bool attn_aligned(const AttnP& p) {
+    return (p.ldq % 8 == 0) && (p.ldk % 8 == 0) && (p.vt_ld % 8 == 0) && (p.ldo % 4 == 0) && (p.D % 8 == 0);
+}
+
+// The one rule by which a producer may hand launch_attention q and k already multiplied by sqrt(scale * log2(e)) (AttnP::prescaled):
+// exactly where the launch goes to form 27.  The engine asks before it scales the q | k projection; the dispatcher below takes the same
+// path for the same AttnP, so the two cannot disagree.  (Pre-scaled operands on any other path are still computed correctly — the scale
+// left to apply is 1 — but they are not what the other forms' numerics were measured with.)
+bool attn_takes_prescaled(const AttnP& p, bool force_generic) {
+    if (force_generic || !attn_aligned(p) || p.D != 40 || p.causal || g_attn_kvt == 128 || g_attn_kvt == 96) return false;
+    if (!g_attn_prescale || !attn_stage_fits(p)) return false;
+    if (g_attn_occ == 27) return true;
+    return g_attn_occ == 15 && g_attn_fold_min_m > 0 && p.M >= g_attn_fold_min_m && p.N >= g_attn_fold_min_m;
+}
+
 int launch_attention(const AttnP& p_in, bool force_generic, hipStream_t s) {
     AttnP p = p_in;
+    const bool pre = p.prescaled != 0;
+    const int occ = p.form > 0 ? p.form : g_attn_occ;      // AttnP::form: the form for this launch alone (sdmi_attention_vt_ex)
+    if (pre) p.scale_log2 = 1.f;                 // the operands carry the scale: what is left to apply in the log2 domain is 1
     p.tau = (float)(g_attn_tau < 0 ? -1 : g_attn_tau > 12 ? 12 : g_attn_tau);
     SDMI_REQUIRE(p.B > 0 && p.H > 0 && p.N > 0 && p.M > 0 && p.D > 0, "empty attention");
     SDMI_REQUIRE(p.vt_ld >= (p.M + 63) / 64 * 64, "vt_ld must be >= M rounded up to 64");
     const double pf_flops = 4.0 * p.B * p.H * (double)p.N * p.M * p.D;
     const double pf_bytes = 2.0 * p.B * p.H * ((double)p.N * p.D * 2 + (double)p.M * p.D * 2);
     ProfScope ps(force_generic ? "attention_generic" : (p.M > 128 ? "attention_mfma_self" : "attention_mfma_cross"), pf_flops, pf_bytes, s);
-    const bool aligned = (p.ldq % 8 == 0) && (p.ldk % 8 == 0) && (p.vt_ld % 8 == 0) && (p.ldo % 4 == 0) && (p.D % 8 == 0);
+    const bool aligned = attn_aligned(p);
     const bool kvt128 = g_attn_kvt == 128;       // measured: 64-key tiles win for every head size (profiles/)
     if (!force_generic && aligned) {
         // knob attn_kvt = 96: the text context (77 keys; M in (64, 96]) as ONE 96-key tile — three 32-key blocks — instead of a 64-key tile
@@ -1016,37 +1105,50 @@ int launch_attention(const AttnP& p_in, bool force_generic, hipStream_t s) {
             // overhead is amortised over twice the MFMA work), 64 otherwise or when the key sequence is short
             case 40:
                 // 20 / 21: the role-offset 8-wave kernel (21: softmax shift folded into the S^T MFMA) for the long self-attention launches
-                if ((g_attn_occ == 20 || g_attn_occ == 21) && p.M >= g_attn_pp_min_m && p.N >= 256)
-                    return g_attn_occ == 21 ? launch_attn_pp<40, true>(p, s) : launch_attn_pp<40, false>(p, s);
-                if ((g_attn_occ == 28 || g_attn_occ == 38) && p.M >= g_attn_pp_min_m && p.N >= 384) {      // section timers
+                if ((occ == 20 || occ == 21) && p.M >= g_attn_pp_min_m && p.N >= 256)
+                    return occ == 21 ? launch_attn_pp<40, true>(p, s) : launch_attn_pp<40, false>(p, s);
+                if ((occ == 28 || occ == 38) && p.M >= g_attn_pp_min_m && p.N >= 384) {      // section timers
                     AttnP q = p; q.dbg = (long long*)g_attn_dbg;
-                    return g_attn_occ == 38 ? launch_attn_pp<40, true, 3, true>(q, s) : launch_attn_pp<40, true, 2, true>(q, s);
+                    return occ == 38 ? launch_attn_pp<40, true, 3, true>(q, s) : launch_attn_pp<40, true, 2, true>(q, s);
                 }
                 // 30 / 31: the same with THREE groups (12 waves, 384 queries per workgroup; VALU work split over two sections)
-                if ((g_attn_occ == 30 || g_attn_occ == 31) && p.M >= g_attn_pp_min_m && p.N >= 384)
-                    return g_attn_occ == 31 ? launch_attn_pp<40, true, 3>(p, s) : launch_attn_pp<40, false, 3>(p, s);
+                if ((occ == 30 || occ == 31) && p.M >= g_attn_pp_min_m && p.N >= 384)
+                    return occ == 31 ? launch_attn_pp<40, true, 3>(p, s) : launch_attn_pp<40, false, 3>(p, s);
                 if (!(kvt128 && p.M > 64)) {
-                    if (g_attn_occ == 5) return launch_attn_d<40, 64, 5>(p, s);
+                    if (occ == 5) return launch_attn_d<40, 64, 5>(p, s);
                     // long self-attention (the 128x128-latent hires pass: N = M = 16384) takes the folded-shift form 17 by default: -4.2 % on
                     // the launch, -1.3 % on the c4a job in a same-box A/B, parity at those shapes re-measured with it
                     // (profiles/r03_parity_fullsize.json); at N = 4096 (C1) the two forms are within 1 % and 15 keeps the measured numerics
-                    if (g_attn_occ == 15 && g_attn_fold_min_m > 0 && p.M >= g_attn_fold_min_m && p.N >= g_attn_fold_min_m && !p.causal)
+                    if (occ == 15 && g_attn_fold_min_m > 0 && p.M >= g_attn_fold_min_m && p.N >= g_attn_fold_min_m && !p.causal) {
+                        // ... and pre-scaled operands (the engine's level-0 self-attention) from there to 27
+                        if (pre && attn_stage_fits(p)) return launch_attn_d<40, 64, 27>(p, s);
                         return launch_attn_d<40, 64, 17>(p, s);
-                    if (g_attn_occ == 15) return launch_attn_d<40, 64, 15>(p, s);
-                    if (g_attn_occ == 16) return launch_attn_d<40, 64, 16>(p, s);
-                    if (g_attn_occ == 17) return launch_attn_d<40, 64, 17>(p, s);
+                    }
+                    if (occ == 15) return launch_attn_d<40, 64, 15>(p, s);
+                    if (occ == 16) return launch_attn_d<40, 64, 16>(p, s);
+                    if (occ == 17) return launch_attn_d<40, 64, 17>(p, s);
+                    if (occ == 27) {
+                        // asked for by one launch (AttnP::form): unscaled operands are an error.  Forced for the process (knob attn_occ):
+                        // the launches that are not pre-scaled — cross-attention, the hypernetwork / ln_fold / bias branches,
+                        // sdmi_attention — run form 17, so a forward still runs, as it does with 17 forced
+                        if (p.form == 27) {
+                            SDMI_REQUIRE(pre, "attention form 27 takes pre-scaled q and k only");
+                            SDMI_REQUIRE(attn_stage_fits(p), "attention form 27: a tile's byte offsets must fit 32 bits");
+                        }
+                        return (pre && attn_stage_fits(p)) ? launch_attn_d<40, 64, 27>(p, s) : launch_attn_d<40, 64, 17>(p, s);
+                    }
 #ifdef SDMI_ATTN_PARTS
-                    if (g_attn_occ == 10) return launch_attn_d<40, 64, 10>(p, s);
-                    if (g_attn_occ == 11) return launch_attn_d<40, 64, 11>(p, s);
-                    if (g_attn_occ == 12) return launch_attn_d<40, 64, 12>(p, s);
-                    if (g_attn_occ == 13) return launch_attn_d<40, 64, 13>(p, s);
-                    if (g_attn_occ == 14) return launch_attn_d<40, 64, 14>(p, s);
-                    if (g_attn_occ == 18) { AttnP q = p; q.dbg = (long long*)g_attn_dbg; return launch_attn_d<40, 64, 18>(q, s); }
+                    if (occ == 10) return launch_attn_d<40, 64, 10>(p, s);
+                    if (occ == 11) return launch_attn_d<40, 64, 11>(p, s);
+                    if (occ == 12) return launch_attn_d<40, 64, 12>(p, s);
+                    if (occ == 13) return launch_attn_d<40, 64, 13>(p, s);
+                    if (occ == 14) return launch_attn_d<40, 64, 14>(p, s);
+                    if (occ == 18) { AttnP q = p; q.dbg = (long long*)g_attn_dbg; return launch_attn_d<40, 64, 18>(q, s); }
 #endif
                 }
                 return (kvt128 && p.M > 64) ? launch_attn_d<40, 128>(p, s) : launch_attn_d<40, 64>(p, s);
             case 64:
-                if ((g_attn_occ == 20 || g_attn_occ == 21) && p.M >= g_attn_pp_min_m && p.N >= 256) return launch_attn_pp<64, false>(p, s);
+                if ((occ == 20 || occ == 21) && p.M >= g_attn_pp_min_m && p.N >= 256) return launch_attn_pp<64, false>(p, s);
                 return (kvt128 && p.M > 64) ? launch_attn_d<64, 128>(p, s) : launch_attn_d<64, 64>(p, s);
             case 80: return launch_attn_d<80, 64>(p, s);
             case 128: return launch_attn_d<128, 64>(p, s);

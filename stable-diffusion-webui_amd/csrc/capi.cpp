@@ -87,6 +87,22 @@ int sdmi_attention_vt(const void* q, const void* k, const void* vt, void* out, i
     API_GUARD_END
 }
 
+// sdmi_attention_vt with the kernel form chosen by the caller: `prescaled` != 0 says q and k are already multiplied by
+// sqrt(scale * log2(e)) each (`scale` is then ignored); `form` is an attn_occ value for this one call (0: the default dispatch), carried in AttnP::form.
+int sdmi_attention_vt_ex(const void* q, const void* k, const void* vt, void* out, int B, int H, int N, int M, int D, int ldq,
+                         int ldk, int vt_ld, int ldo, float scale, int prescaled, int form, int force_generic, void* stream) {
+    API_GUARD_BEGIN
+    AttnP p{};
+    p.q = (const half_t*)q; p.k = (const half_t*)k; p.vt = (const half_t*)vt; p.out = (half_t*)out;
+    p.B = B; p.H = H; p.N = N; p.M = M; p.D = D; p.ldq = ldq; p.ldk = ldk; p.vt_ld = vt_ld; p.ldo = ldo;
+    p.scale_log2 = scale * 1.4426950408889634f;
+    p.prescaled = prescaled != 0;
+    SDMI_REQUIRE(form >= 0 && form < 100, "form: an attn_occ value");
+    p.form = (short)form;
+    return launch_attention(p, force_generic != 0, (hipStream_t)stream);
+    API_GUARD_END
+}
+
 int sdmi_attention(const void* q, const void* k, const void* v, void* out, int B, int H, int N, int M, int D, int ldq,
                    int ldk, int ldv, int ldo, float scale, void* workspace, int64_t workspace_bytes, void* stream) {
     API_GUARD_BEGIN
@@ -803,6 +819,7 @@ int sdmi_debug_set(const char* name, int value) {
     else if (n == "attn_lds_pad") g_attn_lds_pad = value;
     else if (n == "attn_fold_min_m") g_attn_fold_min_m = value;
     else if (n == "attn_tau") g_attn_tau = value;
+    else if (n == "attn_prescale") g_attn_prescale = value < 0 ? 1 : value;
     else if (n == "attn_dbg_lo") g_attn_dbg = (g_attn_dbg & 0xFFFFFFFF00000000ull) | (unsigned)value;
     else if (n == "attn_dbg_hi") g_attn_dbg = (g_attn_dbg & 0xFFFFFFFFull) | ((unsigned long long)(unsigned)value << 32);
     else if (n == "gemm_split") g_force_gemm_split = value;

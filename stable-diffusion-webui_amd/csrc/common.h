@@ -198,6 +198,7 @@ extern int g_attn_occ;
 extern int g_attn_lds_pad;
 extern int g_attn_fold_min_m;
 extern int g_attn_tau;
+extern int g_attn_prescale;         // 1 (default): producers may pre-scale q and k for form 27 (attn_takes_prescaled); 0: never
 extern unsigned long long g_attn_dbg;   // device pointer (0 = off) for AttnP::dbg
 extern int g_gemm_dbgflags;
 extern unsigned long long g_gemm_dbg;   // device pointer (0 = off): 5 x int64 per wave of section cycle sums
@@ -215,8 +216,13 @@ struct AttnP {
     long long* dbg;        // tuning only (SDMI_ATTN_PARTS builds, attn_occ = 18): per-wave section cycle sums, 8 x int64 per wave
     float tau;             // set by launch_attention from g_attn_tau: slack (log2 units) a score may exceed the exponent base by before
                            // the kernels re-base (0: re-base whenever some query's running maximum moves; -1: the round-1 form also rescales O^T in every tile)
+    // (two 16-bit fields in what was the struct's tail padding: the kernel arguments keep their size, so the hidden arguments behind
+    // them keep their offsets and every older kernel its exact instruction stream)
+    short form;            // 0: the dispatcher's choice (knob attn_occ); otherwise an attn_occ value for this launch alone (sdmi_attention_vt_ex)
+    short prescaled;       // 1: q and k are already multiplied by sqrt(scale * log2(e)) each; scale_log2 is ignored (see attn_takes_prescaled)
 };
 int launch_attention(const AttnP& p, bool force_generic, hipStream_t s);
+bool attn_takes_prescaled(const AttnP& p, bool force_generic);     // would this launch, with prescaled = 1, run the pre-scaled form (27)?
 // v [B, M, ldv] (head h at h*D) -> vt [B, H*D, Mpad] (zero padded)
 int launch_transpose_v(const half_t* v, half_t* vt, int B, int H, int M, int D, int ldv, int Mpad, hipStream_t s);
 

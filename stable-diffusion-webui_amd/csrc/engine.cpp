@@ -608,14 +608,25 @@ static int run_res(Run& r, const ResW& w, const half_t* x0, const half_t* x1, in
 }
 
 static int run_attn(Run& r, const half_t* q, const half_t* k, const half_t* vt, half_t* out, int B, int H, int N, int M,
-                    int D, int ldq, int ldk, int vt_ld, int ldo) {
+                    int D, int ldq, int ldk, int vt_ld, int ldo, bool prescaled = false) {
     if (r.dry) return 0;
     AttnP p{};
     p.q = q; p.k = k; p.vt = vt; p.out = out;
     p.B = B; p.H = H; p.N = N; p.M = M; p.D = D;
     p.ldq = ldq; p.ldk = ldk; p.vt_ld = vt_ld; p.ldo = ldo;
     p.scale_log2 = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
+    p.prescaled = prescaled;
     return launch_attention(p, r.e->force_generic, r.s);
+}
+// May the stacked q | k projection of a plain self-attention carry sqrt(scale * log2(e)) in its epilogue (on the fp32 accumulators: q and
+// k are rounded to fp16 once, as before, and K Q^T arrives in the log2 domain)?  Only where the attention launch takes the pre-scaled form
+// (attn_takes_prescaled: the dispatcher's own rule) and the projection has no bias.
+static bool attn_prescale_ok(const Run& r, const ConvW& qk, int B, int H, int N, int D, int ld, int vt_ld, int ldo) {
+    if (qk.b != nullptr || r.e->residual_fp32) return false;       // (the accuracy mode keeps its measured numerics)
+    AttnP p{};
+    p.B = B; p.H = H; p.N = N; p.M = N; p.D = D;
+    p.ldq = ld; p.ldk = ld; p.vt_ld = vt_ld; p.ldo = ldo;
+    return attn_takes_prescaled(p, r.e->force_generic);
 }
 
 // V^T[b] = Wv x X[b]^T :  the weight matrix plays the "activation" role, the tokens of image b the "weight" role.
@@ -766,11 +777,15 @@ static int run_st(Run& r, const STW& st, const half_t* x, int B, int H, int Wd, 
         if (fold) {
         } else if (!hn_has_dim(e, C)) {
             half_t* qk = r.H(M * 2 * C);
-            TRY(run_linear(r, b.qk1, n1, (int)M1, nullptr, qk, 2 * C));
+            // level 0 (d = 40, 1024 keys or more): q and k leave the projection times sqrt(scale * log2(e)) and the attention kernel
+            // applies no scale of its own (form 27, attention.hip)
+            const bool pre = attn_prescale_ok(r, b.qk1, B1, st.heads, HW, st.dhead, 2 * C, Npad, C);
+            const float qk_ss = pre ? sqrtf((1.0f / sqrtf((float)st.dhead)) * 1.4426950408889634f) : 1.f;
+            TRY(run_linear(r, b.qk1, n1, (int)M1, nullptr, qk, 2 * C, qk_ss));
             half_t* vt = r.H((size_t)B * C * Npad);
             TRY(run_vt(r, b.v1, n1, C, B1, HW, Npad, vt, false));
             a1 = r.H(M * C);
-            TRY(run_attn(r, qk, qk + C, vt, a1, B1, st.heads, HW, HW, st.dhead, 2 * C, 2 * C, Npad, C));
+            TRY(run_attn(r, qk, qk + C, vt, a1, B1, st.heads, HW, HW, st.dhead, 2 * C, 2 * C, Npad, C, pre));
         } else {
             // hypernetworks loaded for this width: K and V are projected from their own transformed copies of the context (= n1),
             // so the stacked q|k GEMM splits into its two halves (views into the same packed weight)

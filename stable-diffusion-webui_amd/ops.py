@@ -53,6 +53,19 @@ def attention_vt(q, k, vt, heads, m, scale=None, force_generic=False):
     return out
 
 
+def attention_vt_ex(q, k, vt, heads, m, scale=None, prescaled=False, form=0, force_generic=False):
+    """attention_vt with the kernel form chosen by the caller (an "attn_occ" value, 0 = default dispatch); prescaled: q and k already
+    carry sqrt(scale * log2(e)) each.  q and k may be views into a stacked q | k tensor (their row stride is passed on)."""
+    b, n, _ = q.shape
+    d = vt.shape[1] // heads
+    out = torch.empty((b, n, heads * d), dtype=torch.float16, device=q.device)
+    scale = d ** -0.5 if scale is None else scale
+    check(lib.sdmi_attention_vt_ex(ptr(q), ptr(k), ptr(vt), ptr(out), b, heads, n, m, d, q.stride(1), k.stride(1), vt.shape[2],
+                                   out.stride(1), float(scale), 1 if prescaled else 0, int(form), 1 if force_generic else 0, stream_ptr()),
+          "sdmi_attention_vt_ex")
+    return out
+
+
 def pack_conv_weight(w: torch.Tensor, geglu: bool = False, pad: int = 64) -> torch.Tensor:
     """OIHW / [O,I] weight -> packed fp16 [O_pad][taps][I_pad] on the weight's device."""
     _lib.require_device()
