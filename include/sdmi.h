@@ -645,6 +645,68 @@ int64_t sdmi_swinir_scratch_bytes(sdmi_swinir* h, int B, int H, int W);
  * image is reflect-padded to multiples of 8 on the way in and the output cropped.  Refused: a side below 8, tensors of 2^31 elements. */
 int sdmi_swinir_run(sdmi_swinir* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
 
+/* ---- Swin2SR upscalers --------------------------------------------------------------------------------------------------------------- */
+
+/* Cosine window attention of one Swin-V2 block (csrc/swin2sr.hip), window size 8, head dim <= 32: sdmi_swin_attention's geometry,
+ * layout, roll / partition / mask handling (-100, not -inf) and refusals, with WindowAttention.forward of Swin2SR's
+ * network_swin2sr.py between its qkv and proj linears:
+ *   softmax(normalize(q) normalize(k)^T * exp(min(logit_scale, ln 100)) + 16 sigmoid(cpb_mlp(coords))[index] + mask) v.
+ * The first product runs on the fp16 q / k as stored; the fp32 score is multiplied by 1 / max(|q|, 1e-12), 1 / max(|k|, 1e-12) (fp32,
+ * from the same values) and head_scale[h].  A token whose q or k slot is all zero scores bias + mask.  Refused in addition: a null or
+ * misaligned (4 bytes) head_scale. */
+typedef struct sdmi_swin2_attn_desc {
+    const void* qkv;       /* as sdmi_swin_attn_desc */
+    const void* bias;      /* fp32 [heads][64][64]: bias[h][a][b] = 16 sigmoid(table)[(ya - yb + 7) * 15 + (xa - xb + 7)][h] */
+    void* out;
+    int32_t B, H, W;
+    int32_t heads, D;
+    int32_t ldq, ldo;
+    int32_t shift;         /* 0 | 4 */
+    const void* head_scale;    /* fp32 [heads]: exp(min(logit_scale, ln 100)) */
+} sdmi_swin2_attn_desc;
+int sdmi_swin2_attention(const sdmi_swin2_attn_desc* d, void* stream);
+
+/* res-post-norm of a Swin-V2 block: out = resid + nn.LayerNorm(C)(y) over the first C columns of fp16 rows of stride ld, fp32 statistics,
+ * centred variance, the fp32 sum rounded once.  Columns C .. roundup(C, 64) - 1 of `out` are written as zeros; out == resid is allowed
+ * (the stream updated in place), y == out is not.  Refused: null pointers, ld < roundup(C, 64), odd ld, y == out. */
+int sdmi_swin_layernorm_add(const void* y, const void* gamma, const void* beta, const void* resid, void* out, int64_t rows, int C, int ld,
+                            float eps, void* stream);
+
+/* A whole Swin2SR network (Swin2SR.forward of network_swin2sr.py; the webui's swinir_model_arch_v2.py for *.v2.pth files) held by an
+ * engine, the twin of sdmi_swinir_*: the trunk is SwinIR's with Swin-V2 blocks (x = x + norm1(attn(x)); x = x + norm2(mlp(x))).
+ * Fixed: window_size 8, head dim <= 32, 3 channels in / out, num_feat 64, img_range 1.
+ * upsampler 0 `nearest+conv` (scale 4): SwinIR's tail.  1 `pixelshuffle` (scale 2, 3, 4): conv_before_upsample.0 + LeakyReLU(0.01),
+ * per step a 3x3 conv 64 -> 4*64 (9*64 for x3) and PixelShuffle, conv_last.  2 `pixelshuffledirect` (scale 2, 3, 4): one 3x3 conv
+ * C -> 3 scale^2 and PixelShuffle(scale).
+ * blob: host fp32, every tensor flattened, in this order (weight then bias for convs, linears and norms):
+ *   conv_first; patch_embed.proj (the 1x1 conv C -> C of Swin2SR's PatchEmbed; the identity for a network without one); patch_embed.norm;
+ *   per layer i, per block j: attn.qkv weight, a [3C] bias (q_bias | 0 | v_bias); the bias table 16 sigmoid(cpb_mlp(coords)) [225][heads];
+ *     head_scale [heads] = exp(min(logit_scale, ln 100)); attn.proj; norm1; mlp.fc1; mlp.fc2; norm2;
+ *     then the layer's conv (resi_3conv: conv.0, conv.2, conv.4), the layer's own patch_embed.proj already multiplied into the last;
+ *   norm; conv_after_body (resi_3conv: .0, .2, .4);
+ *   upsampler 0: conv_before_upsample.0; conv_up1; conv_up2; conv_hr; conv_last
+ *   upsampler 1: conv_before_upsample.0; upsample.0; upsample.2 (scale 4 only); conv_last
+ *   upsampler 2: upsample.0
+ * sdmi_swin2sr_blob_floats gives its length (0 for a config the engine refuses).  NULL on error: sdmi_swinir_create's refusals, an
+ * upsampler outside 0..2, a scale its upsampler does not have. */
+typedef struct sdmi_swin2sr_config {
+    int32_t embed_dim;
+    int32_t num_layers;
+    int32_t depths[16];
+    int32_t num_heads;
+    int32_t mlp_hidden;
+    int32_t resi_3conv;
+    int32_t upsampler;     /* 0: nearest+conv; 1: pixelshuffle; 2: pixelshuffledirect */
+    int32_t scale;         /* 4 for upsampler 0; 2 | 3 | 4 otherwise */
+} sdmi_swin2sr_config;
+typedef struct sdmi_swin2sr sdmi_swin2sr;
+int64_t sdmi_swin2sr_blob_floats(const sdmi_swin2sr_config* cfg);
+sdmi_swin2sr* sdmi_swin2sr_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_swin2sr_config* cfg);
+void sdmi_swin2sr_destroy(sdmi_swin2sr* h);
+int64_t sdmi_swin2sr_scratch_bytes(sdmi_swin2sr* h, int B, int H, int W);
+/* in / out, padding, crop and refusals as sdmi_swinir_run */
+int sdmi_swin2sr_run(sdmi_swin2sr* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
+
 /* ---- ScuNET denoisers / upscalers ------------------------------------------------------------------------------------------------------ */
 
 /* The transformer `Block` of one ConvTransBlock (csrc/scunet.hip), window size 8, head dim 32, trans_dim C = 32 (1 head) or 64 (2 heads),

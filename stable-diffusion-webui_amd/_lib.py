@@ -69,6 +69,19 @@ class SwinIRConfigC(C.Structure):
                 ("mlp_hidden", C.c_int32), ("resi_3conv", C.c_int32), ("scale", C.c_int32)]
 
 
+class Swin2AttnDesc(C.Structure):
+    _fields_ = [
+        ("qkv", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("heads", C.c_int32), ("D", C.c_int32),
+        ("ldq", C.c_int32), ("ldo", C.c_int32), ("shift", C.c_int32), ("head_scale", C.c_void_p),
+    ]
+
+
+class Swin2SRConfigC(C.Structure):
+    _fields_ = [("embed_dim", C.c_int32), ("num_layers", C.c_int32), ("depths", C.c_int32 * 16), ("num_heads", C.c_int32),
+                ("mlp_hidden", C.c_int32), ("resi_3conv", C.c_int32), ("upsampler", C.c_int32), ("scale", C.c_int32)]
+
+
 class ScuBlockDesc(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("out", C.c_void_p), ("packs", C.c_void_p), ("bias", C.c_void_p),
@@ -214,6 +227,13 @@ _SIGS = {
     "sdmi_swinir_destroy": (None, [_vp]),
     "sdmi_swinir_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
     "sdmi_swinir_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "sdmi_swin2_attention": (_i, [C.POINTER(Swin2AttnDesc), _vp]),
+    "sdmi_swin_layernorm_add": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _vp]),
+    "sdmi_swin2sr_blob_floats": (_i64, [C.POINTER(Swin2SRConfigC)]),
+    "sdmi_swin2sr_create": (_vp, [_vp, _vp, _i64, C.POINTER(Swin2SRConfigC)]),
+    "sdmi_swin2sr_destroy": (None, [_vp]),
+    "sdmi_swin2sr_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
+    "sdmi_swin2sr_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "sdmi_scu_block": (_i, [C.POINTER(ScuBlockDesc), _vp]),
     "sdmi_scu_block_pack_bytes": (_i64, [_i]),
     "sdmi_scu_block_pack": (_i, [_vp] * 13 + [_i, _vp]),

@@ -38,6 +38,8 @@ int64_t swinir_blob_floats(const sdmi_swinir_config* cfg);
 int swinir_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swinir_config* cfg, sdmi_swinir** out);
 int64_t swinir_scratch_bytes(const sdmi_swinir* n, int B, int H, int W);
 int swinir_run(sdmi_swinir* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
+int64_t swin2sr_blob_floats(const sdmi_swin2sr_config* cfg);
+int swin2sr_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swin2sr_config* cfg, sdmi_swin2sr** out);
 int64_t scunet_blob_floats(const sdmi_scunet_config* cfg);
 int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_scunet_config* cfg, sdmi_scunet** out);
 int64_t scunet_scratch_bytes(const sdmi_scunet* n, int B, int H, int W);
@@ -747,6 +749,47 @@ void sdmi_swinir_destroy(sdmi_swinir* h) { delete h; }
 int64_t sdmi_swinir_scratch_bytes(sdmi_swinir* h, int B, int H, int W) { return swinir_scratch_bytes(h, B, H, W); }
 
 int sdmi_swinir_run(sdmi_swinir* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
+    API_GUARD_BEGIN
+    return swinir_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_swin2_attention(const sdmi_swin2_attn_desc* d, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(d, "null descriptor");
+    Swin2AttnP p{};
+    p.qkv = (const half_t*)d->qkv; p.bias = (const float*)d->bias; p.out = (half_t*)d->out; p.head_scale = (const float*)d->head_scale;
+    p.B = d->B; p.H = d->H; p.W = d->W; p.heads = d->heads; p.D = d->D; p.ldq = d->ldq; p.ldo = d->ldo; p.shift = d->shift;
+    return launch_swin2_attention(p, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_swin_layernorm_add(const void* y, const void* gamma, const void* beta, const void* resid, void* out, int64_t rows, int C, int ld,
+                            float eps, void* stream) {
+    API_GUARD_BEGIN
+    return launch_swin2_layernorm_add((const half_t*)y, (const float*)gamma, (const float*)beta, (const half_t*)resid, (half_t*)out, rows, C, ld,
+                                      eps, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int64_t sdmi_swin2sr_blob_floats(const sdmi_swin2sr_config* cfg) { return swin2sr_blob_floats(cfg); }
+
+sdmi_swin2sr* sdmi_swin2sr_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_swin2sr_config* cfg) {
+    try {
+        sdmi_swin2sr* n = nullptr;
+        if (swin2sr_create(e, (const float*)blob_f32, blob_floats, cfg, &n) != 0) return nullptr;
+        return n;
+    } catch (const std::exception& ex) {
+        set_error(std::string("exception: ") + ex.what());
+        return nullptr;
+    }
+}
+
+void sdmi_swin2sr_destroy(sdmi_swin2sr* h) { delete h; }
+
+int64_t sdmi_swin2sr_scratch_bytes(sdmi_swin2sr* h, int B, int H, int W) { return swinir_scratch_bytes(h, B, H, W); }
+
+int sdmi_swin2sr_run(sdmi_swin2sr* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
     API_GUARD_BEGIN
     return swinir_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
     API_GUARD_END

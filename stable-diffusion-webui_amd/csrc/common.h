@@ -310,6 +310,26 @@ int launch_swin_lrelu(half_t* x, int64_t n, float slope, hipStream_t s);        
 // fp32 [B][3][Hp][Wp] cropped to H x W -> fp32 NCHW or (out_u8) uint8 HWC
 int launch_swin_output(const float* src, void* out, int out_u8, int B, int H, int W, int Hp, int Wp, hipStream_t s);
 
+// ---- Swin2SR: cosine window attention, res-post-norm LayerNorm, pixel shuffles (swin2sr.hip) --------------------
+struct Swin2AttnP {        // SwinAttnP's layout; the score is cos(q, k) head_scale[h] + bias + mask
+    const half_t* qkv;
+    const float* bias;     // [heads][64][64]: 16 sigmoid(cpb_mlp(coords)), expanded
+    half_t* out;
+    int B, H, W;
+    int heads, D, ldq, ldo;
+    int shift;
+    const float* head_scale;   // [heads]: exp(min(logit_scale, ln 100))
+};
+int launch_swin2_attention(const Swin2AttnP& p, hipStream_t s);
+// out = resid + LayerNorm(y) over the first C columns of ld-wide rows; columns C .. roundup(C, 64) - 1 of out are written as zeros;
+// out == resid is allowed
+int launch_swin2_layernorm_add(const half_t* y, const float* gamma, const float* beta, const half_t* resid, half_t* out, int64_t rows, int C,
+                               int ld, float eps, hipStream_t s);
+// PixelShuffle(f), f = 2 | 3: src [B*H*W][f*f*64] with the channels in (i, j, c) order -> dst [B][H f][W f][64]
+int launch_swin2_pixel_shuffle(const half_t* src, half_t* dst, int B, int H, int W, int f, hipStream_t s);
+// src [B*Hp*Wp][ld], channels c f^2 + i f + j -> PixelShuffle(f), + mean, cropped to (H f) x (W f) -> fp32 NCHW or (out_u8) uint8 HWC
+int launch_swin2_output_shuffle(const half_t* src, void* out, int out_u8, int B, int H, int W, int Hp, int Wp, int f, int ld, hipStream_t s);
+
 // ---- ScuNET: the transformer Block of one 8 x 8 window per workgroup (scunet.hip) ------------------------------
 struct ScuBlockP {
     const half_t* x;       // token rows [B*H*W][ldx], the first C columns are the block's input

@@ -2280,6 +2280,41 @@ int64_t swinir_blob_floats(const sdmi_swinir_config* c) {
     return n;
 }
 
+// Swin2SR: the SwinIR config its trunk shares (scale 3 and the pixel-shuffle tails are checked here, the rest by swinir_config_ok)
+static bool swin2sr_config_ok(const sdmi_swin2sr_config& c, sdmi_swinir_config* base, std::string* why) {
+    auto fail = [&](const char* m) { if (why) *why = m; return false; };
+    if (c.upsampler < 0 || c.upsampler > 2) return fail("upsampler 0 (nearest+conv) | 1 (pixelshuffle) | 2 (pixelshuffledirect)");
+    if (c.upsampler == 0 ? c.scale != 4 : (c.scale != 2 && c.scale != 3 && c.scale != 4))
+        return fail("scale 4 with the nearest+conv upsampler, 2 | 3 | 4 with pixelshuffle / pixelshuffledirect");
+    sdmi_swinir_config b{};
+    b.embed_dim = c.embed_dim; b.num_layers = c.num_layers; b.num_heads = c.num_heads; b.mlp_hidden = c.mlp_hidden;
+    b.resi_3conv = c.resi_3conv; b.scale = c.scale == 3 ? 4 : c.scale;
+    for (int i = 0; i < 16; ++i) b.depths[i] = c.depths[i];
+    if (!swinir_config_ok(b, why)) return false;
+    b.scale = c.scale;
+    if (base) *base = b;
+    return true;
+}
+
+int64_t swin2sr_blob_floats(const sdmi_swin2sr_config* c) {
+    sdmi_swinir_config b{};
+    if (!c || !swin2sr_config_ok(*c, &b, nullptr)) return 0;
+    const int64_t C = c->embed_dim, Hd = c->mlp_hidden, q = C / 4, s2 = c->scale == 3 ? 9 : 4;
+    auto lin = [](int64_t o, int64_t i, int64_t taps = 1) { return o * i * taps + o; };
+    const int64_t resi = c->resi_3conv ? lin(q, C, 9) + lin(q, q) + lin(C, q, 9) : lin(C, C, 9);
+    const int64_t block = lin(3 * C, C) + 226 * c->num_heads + lin(C, C) + 2 * C + lin(Hd, C) + lin(C, Hd) + 2 * C;
+    int64_t n = lin(C, 3, 9) + lin(C, C) + 2 * C;
+    for (int i = 0; i < c->num_layers; ++i) n += c->depths[i] * block + resi;
+    n += 2 * C + resi;
+    if (c->upsampler == 0) n += lin(64, C, 9) + 3 * lin(64, 64, 9) + lin(3, 64, 9);
+    else if (c->upsampler == 1) n += lin(64, C, 9) + (c->scale == 4 ? 2 : 1) * lin(s2 * 64, 64, 9) + lin(3, 64, 9);
+    else n += lin(3 * c->scale * c->scale, C, 9);
+    return n;
+}
+
+// Uploads and packs the weights of a SwinIR (net->v2 == 0) or Swin2SR network off its blob; net->cfg, v2 and upsampler are set
+static int swin_net_build(sdmi_swinir* net, const float* blob, int64_t blob_floats);
+
 int swinir_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swinir_config* cfg, sdmi_swinir** out) {
     SDMI_REQUIRE(e && blob && cfg && out, "null argument");
     std::string why;
@@ -2288,6 +2323,28 @@ int swinir_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const 
     SDMI_CHECK_HIP(hipSetDevice(e->device));
     std::unique_ptr<sdmi_swinir> net(new sdmi_swinir);
     net->e = e; net->cfg = *cfg;
+    TRY(swin_net_build(net.get(), blob, blob_floats));
+    *out = net.release();
+    return 0;
+}
+
+int swin2sr_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swin2sr_config* cfg, sdmi_swin2sr** out) {
+    SDMI_REQUIRE(e && blob && cfg && out, "null argument");
+    std::string why;
+    sdmi_swinir_config base{};
+    SDMI_REQUIRE(swin2sr_config_ok(*cfg, &base, &why), "Swin2SR config: " + why);
+    SDMI_REQUIRE(blob_floats == swin2sr_blob_floats(cfg), "weight blob size does not match the config");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    std::unique_ptr<sdmi_swin2sr> net(new sdmi_swin2sr);
+    net->e = e; net->cfg = base; net->cfg2 = *cfg; net->v2 = 1; net->upsampler = cfg->upsampler;
+    TRY(swin_net_build(net.get(), blob, blob_floats));
+    *out = net.release();
+    return 0;
+}
+
+static int swin_net_build(sdmi_swinir* net, const float* blob, int64_t blob_floats) {
+    const sdmi_swinir_config* cfg = &net->cfg;
+    const bool v2 = net->v2 != 0;
     const int C = cfg->embed_dim, heads = cfg->num_heads, D = C / heads, Hd = cfg->mlp_hidden, Cq = C / 4;
     const int Cp = rup(C, 64), hid_pad = rup(Hd, 64), ldq = rup(96 * heads, 64), lda = rup(32 * heads, 64);
     net->C = C; net->Cp = Cp; net->D = D; net->ldq = ldq; net->lda = lda; net->hid_pad = hid_pad;
@@ -2333,6 +2390,7 @@ int swinir_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const 
     auto slot = [&](int v) { return (v / D) * 32 + v % D; };          // feature h * D + d -> column h * 32 + d
 
     TRY(pack(&net->first, C, 3, 9, Cp, 64, ident, ident));
+    if (v2) TRY(pack(&net->pe_proj, C, C, 1, Cp, Cp, ident, ident));
     TRY(norm(&net->pe_norm));
     net->layers.resize((size_t)cfg->num_layers);
     std::vector<float> bias((size_t)heads * 4096);
@@ -2340,32 +2398,55 @@ int swinir_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const 
         sdmi_swinir::Layer& L = net->layers[(size_t)i];
         L.blocks.resize((size_t)cfg->depths[i]);
         for (sdmi_swinir::Block& bk : L.blocks) {
-            TRY(norm(&bk.n1));
-            for (int h = 0; h < heads; ++h)                            // bias[h][a][b] = table[(ya - yb + 7) * 15 + (xa - xb + 7)][h]
-                for (int a = 0; a < 64; ++a)
-                    for (int b = 0; b < 64; ++b)
-                        bias[((size_t)h * 64 + a) * 64 + b] = src[(size_t)(((a >> 3) - (b >> 3) + 7) * 15 + ((a & 7) - (b & 7) + 7)) * heads + h];
-            src += 225 * heads;
-            TRY(upload(bias.data(), bias.size() * sizeof(float), (void**)&bk.bias));
-            TRY(pack(&bk.qkv, 3 * C, C, 1, ldq, Cp, [&](int o) { return (o / C) * heads * 32 + slot(o % C); }, ident));
-            TRY(pack(&bk.proj, C, C, 1, Cp, lda, ident, slot));
-            TRY(norm(&bk.n2));
+            auto table = [&]() -> int {                                // bias[h][a][b] = table[(ya - yb + 7) * 15 + (xa - xb + 7)][h]
+                for (int h = 0; h < heads; ++h)
+                    for (int a = 0; a < 64; ++a)
+                        for (int b = 0; b < 64; ++b)
+                            bias[((size_t)h * 64 + a) * 64 + b] = src[(size_t)(((a >> 3) - (b >> 3) + 7) * 15 + ((a & 7) - (b & 7) + 7)) * heads + h];
+                src += 225 * heads;
+                return upload(bias.data(), bias.size() * sizeof(float), (void**)&bk.bias);
+            };
+            auto qkv = [&]() { return pack(&bk.qkv, 3 * C, C, 1, ldq, Cp, [&](int o) { return (o / C) * heads * 32 + slot(o % C); }, ident); };
+            if (!v2) {
+                TRY(norm(&bk.n1));
+                TRY(table());
+                TRY(qkv());
+                TRY(pack(&bk.proj, C, C, 1, Cp, lda, ident, slot));
+                TRY(norm(&bk.n2));
+            } else {
+                TRY(qkv());
+                TRY(table());
+                TRY(upload(src, (size_t)heads * sizeof(float), (void**)&bk.head_scale));
+                src += heads;
+                TRY(pack(&bk.proj, C, C, 1, Cp, lda, ident, slot));
+                TRY(norm(&bk.n1));
+            }
             TRY(pack(&bk.fc1, Hd, C, 1, hid_pad, Cp, ident, ident));
             TRY(pack(&bk.fc2, C, Hd, 1, Cp, hid_pad, ident, ident));
+            if (v2) TRY(norm(&bk.n2));
         }
         TRY(resi(L.conv));
     }
     TRY(norm(&net->norm));
     TRY(resi(net->after));
-    TRY(pack(&net->before, 64, C, 9, 64, Cp, ident, ident));
-    TRY(pack(&net->up1, 64, 64, 9, 64, 64, ident, ident));
-    if (cfg->scale == 4) TRY(pack(&net->up2, 64, 64, 9, 64, 64, ident, ident));
-    TRY(pack(&net->hr, 64, 64, 9, 64, 64, ident, ident));
     const float mean[3] = {0.4488f, 0.4371f, 0.4040f};                 // y / img_range + mean folds into conv_last's bias
-    TRY(pack(&net->last, 3, 64, 9, 32, 64, ident, ident, mean));
+    if (net->upsampler == 0) {
+        TRY(pack(&net->before, 64, C, 9, 64, Cp, ident, ident));
+        TRY(pack(&net->up1, 64, 64, 9, 64, 64, ident, ident));
+        if (cfg->scale == 4) TRY(pack(&net->up2, 64, 64, 9, 64, 64, ident, ident));
+        TRY(pack(&net->hr, 64, 64, 9, 64, 64, ident, ident));
+        TRY(pack(&net->last, 3, 64, 9, 32, 64, ident, ident, mean));
+    } else if (net->upsampler == 1) {
+        const int f2 = cfg->scale == 3 ? 9 : 4;                        // torch's channel c f^2 + (i f + j) -> row (i f + j) * 64 + c
+        TRY(pack(&net->before, 64, C, 9, 64, Cp, ident, ident));
+        for (int k = 0; k < (cfg->scale == 4 ? 2 : 1); ++k)
+            TRY(pack(&net->ps[k], f2 * 64, 64, 9, f2 * 64, 64, [&](int o) { return (o % f2) * 64 + o / f2; }, ident));
+        TRY(pack(&net->last, 3, 64, 9, 32, 64, ident, ident, mean));
+    } else {
+        TRY(pack(&net->direct, 3 * cfg->scale * cfg->scale, C, 9, 64, Cp, ident, ident));
+    }
     SDMI_REQUIRE(src - blob == blob_floats, "internal: blob walk does not end at its length");
     SDMI_CHECK_HIP(hipDeviceSynchronize());
-    *out = net.release();
     return 0;
 }
 
@@ -2385,12 +2466,18 @@ static int swinir_pass(Run& r, const sdmi_swinir& n, const void* in, int in_u8, 
     half_t* hid = r.H(M * n.hid_pad);
     half_t* c1 = r.H(M * 64);
     half_t* c2 = r.H(M * 64);
-    half_t* up[3] = {r.H(M * 4 * 64), sc == 4 ? r.H(M * 16 * 64) : nullptr, r.H(M * sc * sc * 64)};
-    float* full = r.F(M * sc * sc * 3);                       // conv_last on the padded grid, cropped by swin_output
+    half_t* up[3] = {nullptr, nullptr, nullptr};
+    float* full = nullptr;
+    if (n.upsampler == 0) {
+        up[0] = r.H(M * 4 * 64); up[1] = sc == 4 ? r.H(M * 16 * 64) : nullptr; up[2] = r.H(M * sc * sc * 64);
+    } else if (n.upsampler == 1) {                            // the step convs' outputs and their shuffles, ping-pong
+        up[0] = r.H(M * sc * sc * 64); up[1] = r.H(M * sc * sc * 64);
+    }
+    if (n.upsampler != 2) full = r.F(M * sc * sc * 3);        // conv_last on the padded grid, cropped by swin_output
 
-    auto conv = [&](const ConvW& w, const half_t* a, const half_t* resid, half_t* o, int flags = 0) -> int {      // 3x3 pad 1 / 1x1 / linear
+    auto conv = [&](const ConvW& w, const half_t* a, const half_t* resid, half_t* o, int flags = 0, int f = 1) -> int {      // 3x3 pad 1 / 1x1 / linear, on the grid x f
         ConvArgs c;
-        c.a0 = a; c.c0 = w.cin_pad; c.B = B; c.Hi = c.Ho = Hp; c.Wi = c.Wo = Wp; c.pad = w.taps == 9 ? 1 : 0;
+        c.a0 = a; c.c0 = w.cin_pad; c.B = B; c.Hi = c.Ho = Hp * f; c.Wi = c.Wo = Wp * f; c.pad = w.taps == 9 ? 1 : 0;
         c.resid = resid; c.ldr = w.n_pad; c.out = o; c.ldo = w.n_pad; c.flags = flags;
         const size_t mark = r.ar->mark();                     // a split-K workspace lives for its launch only
         const int rc = run_conv(r, w, c);
@@ -2419,11 +2506,39 @@ static int swinir_pass(Run& r, const sdmi_swinir& n, const void* in, int in_u8, 
     TRY(conv(n.first, x0, nullptr, feat));
     half_t* x = pool[0];
     std::vector<half_t*> free_ = {pool[1], pool[2], pool[3]};
-    TRY(lnorm(n.pe_norm, feat, x));
+    if (n.v2) {                                               // Swin2SR's PatchEmbed has a 1x1 projection in front of its norm; the skip stays conv_first's output
+        TRY(conv(n.pe_proj, feat, nullptr, ln));
+        TRY(lnorm(n.pe_norm, ln, x));
+    } else {
+        TRY(lnorm(n.pe_norm, feat, x));
+    }
     for (const sdmi_swinir::Layer& L : n.layers) {
         half_t* cur = x;
         for (size_t j = 0; j < L.blocks.size(); ++j) {
             const sdmi_swinir::Block& bk = L.blocks[j];
+            if (n.v2) {
+                // res-post-norm: no norm in front of qkv / fc1; the stream is updated in place by swin2_layernorm_add (the layer's
+                // first block writes a fresh buffer: x stays the skip of the layer's closing conv); `ln` holds the branch outputs
+                half_t* dst = cur;
+                if (cur == x) { dst = free_.back(); free_.pop_back(); }
+                auto lnadd = [&](const NormW& w, const half_t* resid, half_t* o) -> int {
+                    return r.dry ? 0 : launch_swin2_layernorm_add(ln, w.g, w.b, resid, o, (int64_t)M, n.C, Cp, 1e-5f, r.s);
+                };
+                TRY(conv(bk.qkv, cur, nullptr, qkv));
+                if (!r.dry) {
+                    Swin2AttnP a{};
+                    a.qkv = qkv; a.bias = bk.bias; a.out = att; a.B = B; a.H = Hp; a.W = Wp; a.heads = n.cfg.num_heads; a.D = n.D;
+                    a.ldq = n.ldq; a.ldo = n.lda; a.shift = (j & 1) ? 4 : 0; a.head_scale = bk.head_scale;
+                    TRY(launch_swin2_attention(a, r.s));
+                }
+                TRY(conv(bk.proj, att, nullptr, ln));
+                TRY(lnadd(bk.n1, cur, dst));
+                TRY(conv(bk.fc1, dst, nullptr, hid, EP_GELU));
+                TRY(conv(bk.fc2, hid, nullptr, ln));
+                TRY(lnadd(bk.n2, dst, dst));
+                cur = dst;
+                continue;
+            }
             half_t* mid = free_.back(); free_.pop_back();
             half_t* nxt = free_.back(); free_.pop_back();
             TRY(lnorm(bk.n1, cur, ln));
@@ -2451,8 +2566,30 @@ static int swinir_pass(Run& r, const sdmi_swinir& n, const void* in, int in_u8, 
     TRY(lnorm(n.norm, x, ln));
     half_t* trunk = free_.back();
     TRY(resi(n.after, ln, feat, trunk));
+    if (n.upsampler == 2) {                                   // pixelshuffledirect: one conv C -> 3 sc^2, the shuffle folded into the output pass
+        TRY(conv(n.direct, trunk, nullptr, c1));
+        return r.dry ? 0 : launch_swin2_output_shuffle(c1, out, out_u8, B, H, W, Hp, Wp, sc, 64, r.s);
+    }
     TRY(conv(n.before, trunk, nullptr, c1));
     TRY(lrelu(c1, M * 64, 0.01f));
+    if (n.upsampler == 1) {                                   // pixelshuffle: per step conv 64 -> f^2 64 (GEMM) and the shuffle, then conv_last
+        const int f = sc == 3 ? 3 : 2;
+        const half_t* t = c1;
+        int g = 1;                                            // the grid so far: (Hp g) x (Wp g)
+        for (int k = 0; k < (sc == 4 ? 2 : 1); ++k) {
+            TRY(conv(n.ps[k], t, nullptr, up[0], 0, g));
+            if (!r.dry) TRY(launch_swin2_pixel_shuffle(up[0], up[1], B, Hp * g, Wp * g, f, r.s));
+            t = up[1];
+            g *= f;
+        }
+        if (r.dry) return 0;
+        RrdbP p{};
+        p.in = up[1]; p.w = n.last.w; p.bias = n.last.b; p.out = full;
+        p.B = B; p.H = sc * Hp; p.W = sc * Wp; p.cin = 64; p.lda = 64; p.n_real = n.last.cout; p.ep = RRDB_EP_NONE; p.store = RRDB_ST_F32_NCHW;
+        p.alpha = 1.f; p.beta = 1.f;
+        TRY(launch_rrdb_conv(p, n.last.n_pad, r.s));
+        return launch_swin_output(full, out, out_u8, B, H * sc, W * sc, Hp * sc, Wp * sc, r.s);
+    }
     if (r.dry) return 0;
 
     auto tail = [&](const ConvW& w, const half_t* src, int hh, int ww, int upf, void* dst, int store) -> int {
@@ -2851,12 +2988,13 @@ sdmi_engine::~sdmi_engine() {
 }
 
 // The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units; there the upscalers'
-// and the cross-attention chain's kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip, swinir.hip, scunet.hip
-// and xattn_chain.hip on their own (build.sh).
+// and the cross-attention chain's kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip, swinir.hip,
+// swin2sr.hip, scunet.hip and xattn_chain.hip on their own (build.sh).
 #ifndef __HIP__
 #include "rrdb.hip"
 #include "compact.hip"
 #include "swinir.hip"
+#include "swin2sr.hip"
 #include "scunet.hip"
 #include "xattn_chain.hip"
 #endif

@@ -281,6 +281,7 @@ struct sdmi_swinir {
         sdmi::NormW n1, n2;
         sdmi::ConvW qkv, proj, fc1, fc2;
         float* bias = nullptr;                // [heads][64][64]
+        float* head_scale = nullptr;          // Swin2SR: [heads]
     };
     struct Layer {
         std::vector<Block> blocks;
@@ -293,7 +294,17 @@ struct sdmi_swinir {
     sdmi::NormW pe_norm, norm;
     std::vector<Layer> layers;
     std::vector<void*> owned;
+    // Swin2SR (v2): Swin-V2 blocks — cosine attention, res-post-norm — in the same trunk; upsampler 0 nearest+conv (the tail above),
+    // 1 pixelshuffle (before, ps[], last), 2 pixelshuffledirect (direct)
+    int v2 = 0, upsampler = 0;
+    sdmi::ConvW pe_proj;                      // patch_embed.proj: the 1x1 conv in front of patch_embed.norm
+    sdmi::ConvW ps[2], direct;                // ps: 64 -> f*f*64, output channels in (i, j, c) order; direct: C -> 3 scale^2 (padded to 64)
     ~sdmi_swinir();
+};
+
+// Swin2SR upscaler: SwinIR's trunk and buffers with v2 set (engine.cpp swinir_pass runs both)
+struct sdmi_swin2sr : sdmi_swinir {
+    sdmi_swin2sr_config cfg2{};
 };
 
 // ScuNET (Swin-Conv-UNet, dim 64): per ConvTransBlock the two 1x1 convs as GEMM weights, the 3x3 pair as rrdb_conv (widths 32 / 64) or

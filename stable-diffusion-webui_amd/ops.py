@@ -444,6 +444,45 @@ def swin_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps
     return out
 
 
+def swin2_attention(qkv: torch.Tensor, bias: torch.Tensor, head_scale: torch.Tensor, heads: int, d: int, shift: int = 0,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Cosine window attention of a Swin2SR (Swin-V2) block (csrc/swin2sr.hip; window 8, head dim d <= 32): swin_attention's layout and
+    geometry with the score cos(q, k) * head_scale[h] + bias + mask.  bias fp32 [heads, 64, 64] = 16 sigmoid(cpb_mlp(coords)) expanded;
+    head_scale fp32 [heads] = exp(min(logit_scale, ln 100)).  The norms are taken in fp32 from the fp16 q / k as stored; a token whose
+    q or k is all zero scores bias + mask."""
+    _lib.require_device()
+    assert qkv.dtype == torch.float16 and qkv.dim() == 4 and qkv.is_contiguous()
+    b, h, w, ldq = qkv.shape
+    bias = bias.float().contiguous()
+    head_scale = head_scale.float().contiguous()
+    assert tuple(bias.shape) == (heads, 64, 64) and head_scale.numel() == heads
+    if out is None:
+        out = torch.empty((b, h, w, 32 * heads), dtype=torch.float16, device=qkv.device)
+    assert out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape[:3]) == (b, h, w)
+    desc = _lib.Swin2AttnDesc()
+    desc.qkv, desc.bias, desc.out, desc.head_scale = qkv.data_ptr(), bias.data_ptr(), out.data_ptr(), head_scale.data_ptr()
+    desc.B, desc.H, desc.W, desc.heads, desc.D = b, h, w, heads, d
+    desc.ldq, desc.ldo, desc.shift = ldq, out.shape[3], shift
+    check(lib.sdmi_swin2_attention(C.byref(desc), stream_ptr()), "sdmi_swin2_attention")
+    return out
+
+
+def swin_layernorm_add(y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, resid: torch.Tensor, eps: float = 1e-5,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """resid + LayerNorm(y) over the first C = len(gamma) columns of fp16 rows [..., ld] (ld >= C rounded up to 64), the res-post-norm
+    of a Swin-V2 block (csrc/swin2sr.hip): columns C .. roundup(C, 64) - 1 of the result are zeros, columns past that keep `out`'s bits.
+    `out` may be `resid` (in place), not `y`."""
+    _lib.require_device()
+    assert y.dtype == torch.float16 and y.is_contiguous() and resid.dtype == torch.float16 and resid.is_contiguous() and resid.shape == y.shape
+    c, ld = gamma.numel(), y.shape[-1]
+    if out is None:
+        out = torch.zeros_like(y)
+    assert out.dtype == torch.float16 and out.is_contiguous() and out.shape == y.shape
+    check(lib.sdmi_swin_layernorm_add(ptr(y), ptr(gamma.float().contiguous()), ptr(beta.float().contiguous()), ptr(resid), ptr(out),
+                                      y.numel() // ld, c, ld, float(eps), stream_ptr()), "sdmi_swin_layernorm_add")
+    return out
+
+
 def scu_block_pack(ln1_g, ln1_b, wqkv, bqkv, wproj, bproj, ln2_g, ln2_b, w1, b1, w2, b2) -> torch.Tensor:
     """The weights of one ScuNET transformer Block (torch layouts; C = len(ln1_g) in {32, 64}) -> the uint8 operand image scu_block reads
     (sdmi_scu_block_pack): matrices as fp16, vectors as fp32."""

@@ -6,7 +6,7 @@ up in (modules/images.py:276, modules/modelloader.py:136), the ``Upscaler.upscal
 the three built-in PIL scalers (None / Lanczos / Nearest, modules/upscaler.py:107-154).  The RRDBNet family (ESRGAN, Real-ESRGAN) and the
 compact Real-ESRGAN models (SRVGGNetCompact: General 4xV3, General WDN 4xV3, AnimeVideo) run on the engine (``UpscalerESRGAN`` /
 ``register_esrgan`` below, csrc/rrdb.hip and csrc/compact.hip), and so do the SwinIR models with the nearest+conv upsampler
-(``SwinIRNet``, csrc/swinir.hip) and the ScuNET models (``ScuNETNet``, csrc/scunet.hip); other model upscalers register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)``
+(``SwinIRNet``, csrc/swinir.hip), the Swin2SR models (``Swin2SRNet``, csrc/swin2sr.hip) and the ScuNET models (``ScuNETNet``, csrc/scunet.hip); other model upscalers register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)``
 is called as in the reference.
 """
 from __future__ import annotations
@@ -303,6 +303,183 @@ def parse_swinir_state_dict(sd):
     return np.ascontiguousarray(np.concatenate(parts)), config
 
 
+SWIN2SR_MARK = "layers.0.residual_group.blocks.0.attn.logit_scale"
+SWIN2SR_UPSAMPLERS = ("nearest+conv", "pixelshuffle", "pixelshuffledirect")
+
+
+def swin2sr_coords_table():
+    """[225, 2] fp32: the log-spaced relative coordinates of an 8 x 8 window (WindowAttention of network_swin2sr.py): offsets -7..7
+    / 7 * 8, then sign(x) log2(|x| + 1) / log2(8); row (dy + 7) * 15 + (dx + 7) = (y, x)."""
+    d = np.arange(-7, 8, dtype=np.float32) / np.float32(7) * np.float32(8)
+    t = np.stack(np.meshgrid(d, d, indexing="ij"), axis=-1).reshape(225, 2).astype(np.float32)
+    return (np.sign(t) * np.log2(np.abs(t) + np.float32(1)) / np.float32(np.log2(8.0))).astype(np.float32)
+
+
+def swin2sr_bias_table(w0, b0, w2):
+    """16 sigmoid(cpb_mlp(coords)) -> [225, heads] fp32, computed in fp32: cpb_mlp = Linear(2, hidden) + ReLU + Linear(hidden, heads,
+    bias=False)."""
+    w0, b0, w2 = (np.asarray(t, dtype=np.float32) for t in (w0, b0, w2))
+    hid = np.maximum(swin2sr_coords_table() @ w0.T + b0, np.float32(0))
+    z = (hid @ w2.T).astype(np.float32)
+    return (np.float32(16) / (np.float32(1) + np.exp(-z))).astype(np.float32)
+
+
+def swin2sr_head_scale(logit_scale):
+    """exp(min(logit_scale, ln 100)) -> [heads] fp32."""
+    return np.exp(np.minimum(np.asarray(logit_scale, dtype=np.float32).ravel(), np.float32(np.log(100.0)))).astype(np.float32)
+
+
+def parse_swin2sr_state_dict(sd):
+    """Checkpoint state dict of a Swin2SR network (network_swin2sr.py; the webui's swinir_model_arch_v2.py) -> (blob, config): the
+    engine's weight blob (fp32, in the order include/sdmi.h documents at sdmi_swin2sr_config: conv_first; patch_embed.proj (the identity
+    where a checkpoint has none); patch_embed.norm; per block
+    attn.qkv with the bias (q_bias | 0 | v_bias), the ready bias table 16 sigmoid(cpb_mlp(coords)) [225][heads], head_scale =
+    exp(min(logit_scale, ln 100)), attn.proj, norm1, mlp.fc1, mlp.fc2, norm2; the layer's conv(s), the last with the layer's patch_embed.proj folded in (P W, P b + p:
+    nothing else reads that conv); norm; conv_after_body; the tail) and
+    config = dict(embed_dim, depths, num_heads, mlp_hidden, resi_3conv, upsampler, scale), upsampler one of SWIN2SR_UPSAMPLERS, read
+    from the tail keys.  The buffers relative_coords_table / relative_position_index / attn_mask are ignored.  Host only.  Raises
+    ValueError on what the engine's kernels are not built for."""
+    sd = _unwrap_state_dict(sd)
+    if SWIN2SR_MARK not in sd or "conv_first.weight" not in sd:
+        raise ValueError(f"not a Swin2SR checkpoint: no {SWIN2SR_MARK}")
+    if "absolute_pos_embed" in sd:
+        raise ValueError("Swin2SR with ape (absolute_pos_embed): the engine runs the models without it")
+    if "conv_bicubic.weight" in sd or "conv_aux.weight" in sd:
+        raise ValueError("Swin2SR upsampler 'pixelshuffle_aux' (conv_bicubic / conv_aux): the engine runs nearest+conv, pixelshuffle and "
+                         "pixelshuffledirect")
+    if "conv_up1.weight" in sd and "conv_hr.weight" in sd and "conv_before_upsample.0.weight" in sd:
+        upsampler = 0
+    elif "upsample.0.weight" in sd:
+        upsampler = 1 if "conv_before_upsample.0.weight" in sd else 2
+    else:
+        raise ValueError("Swin2SR without an upsampler (no conv_up1 / conv_hr, no upsample.0: a denoising / JPEG model): the engine runs "
+                         "the super-resolution models")
+    c, in_ch = int(sd["conv_first.weight"].shape[0]), int(sd["conv_first.weight"].shape[1])
+    if in_ch != 3 or tuple(sd["conv_first.weight"].shape[2:]) != (3, 3):
+        raise ValueError(f"Swin2SR conv_first takes {in_ch} input channels: expected 3")
+    layers = sorted({int(m.group(1)) for k in sd for m in [re.match(r"layers\.(\d+)\.residual_group\.blocks\.0\.attn\.qkv\.weight$", k)] if m})
+    if not layers or layers != list(range(len(layers))) or len(layers) > 16:
+        raise ValueError(f"Swin2SR layers are not 0..n-1 with 1 <= n <= 16: {layers}")
+    depths = []
+    for i in layers:
+        blocks = sorted({int(m.group(1)) for k in sd for m in [re.match(rf"layers\.{i}\.residual_group\.blocks\.(\d+)\.attn\.qkv\.weight$", k)] if m})
+        if blocks != list(range(len(blocks))):
+            raise ValueError(f"Swin2SR layers.{i}: blocks are not 0..n-1: {blocks}")
+        depths.append(len(blocks))
+    heads = int(sd[SWIN2SR_MARK].shape[0])
+    for k, v in sd.items():                                  # the cpb grid is computed, not stored: the window shows in the buffers
+        side = None
+        if k.endswith("attn.relative_position_index") and tuple(v.shape) != (64, 64):
+            side = int(round(int(v.shape[0]) ** 0.5))
+        elif k.endswith("attn_mask") and tuple(v.shape[1:]) != (64, 64):
+            side = int(round(int(v.shape[-1]) ** 0.5))
+        elif k.endswith("attn.relative_coords_table") and tuple(v.shape[1:3]) != (15, 15):
+            side = (int(v.shape[1]) + 1) // 2
+        if side is not None:
+            raise ValueError(f"Swin2SR window_size {side} ({k} {tuple(v.shape)}): the engine's attention kernel is built for 8")
+    if c % heads or c // heads > 32:
+        raise ValueError(f"Swin2SR head_dim = {c}/{heads} = {c / heads:g}: the engine's attention kernel is built for head_dim <= 32")
+    b0 = "layers.0.residual_group.blocks.0."
+    if b0 + "mlp.fc1.weight" not in sd:
+        raise ValueError(f"Swin2SR checkpoint lacks {b0}mlp.fc1.weight")
+    hidden = int(sd[b0 + "mlp.fc1.weight"].shape[0])
+    resi3 = "layers.0.conv.0.weight" in sd
+    if not resi3 and "layers.0.conv.weight" not in sd:
+        raise ValueError("Swin2SR checkpoint lacks layers.0.conv (.weight for 1conv, .0 / .2 / .4 for 3conv)")
+    if resi3 and (c % 4 or c // 4 > 64):
+        raise ValueError(f"Swin2SR 3conv with embed_dim {c}: the engine packs embed_dim / 4 <= 64 channels")
+    if upsampler != 2 and int(sd["conv_before_upsample.0.weight"].shape[0]) != 64:
+        raise ValueError(f"Swin2SR num_feat = {int(sd['conv_before_upsample.0.weight'].shape[0])}: the engine's tail kernels are built for 64")
+    if upsampler == 0:
+        if "conv_up2.weight" not in sd:
+            raise ValueError("Swin2SR nearest+conv without conv_up2 (scale 2): the architecture has this upsampler at scale 4 only")
+        scale = 4
+        tail = [("conv_before_upsample.0", (64, c, 3, 3)), ("conv_up1", (64, 64, 3, 3)), ("conv_up2", (64, 64, 3, 3)),
+                ("conv_hr", (64, 64, 3, 3)), ("conv_last", (3, 64, 3, 3))]
+    elif upsampler == 1:
+        n0 = int(sd["upsample.0.weight"].shape[0])
+        scale = {(256, False): 2, (576, False): 3, (256, True): 4}.get((n0, "upsample.2.weight" in sd))
+        if scale is None or any(f"upsample.{k}.weight" in sd for k in (4, 6)):
+            raise ValueError(f"Swin2SR pixelshuffle with upsample.0 writing {n0} channels"
+                             f"{' and further steps' if 'upsample.2.weight' in sd else ''}: the engine runs scales 2, 3 and 4")
+        tail = [("conv_before_upsample.0", (64, c, 3, 3)), ("upsample.0", (n0, 64, 3, 3))]
+        tail += ([("upsample.2", (256, 64, 3, 3))] if scale == 4 else []) + [("conv_last", (3, 64, 3, 3))]
+    else:
+        n0 = int(sd["upsample.0.weight"].shape[0])
+        scale = {12: 2, 27: 3, 48: 4}.get(n0)
+        if scale is None:
+            raise ValueError(f"Swin2SR pixelshuffledirect with upsample.0 writing {n0} channels: the engine runs scales 2, 3 and 4 "
+                             f"(12, 27, 48 channels)")
+        tail = [("upsample.0", (n0, c, 3, 3))]
+    q = c // 4
+    resi = (lambda stem: [(stem + ".0", (q, c, 3, 3)), (stem + ".2", (q, q, 1, 1)), (stem + ".4", (c, q, 3, 3))]) if resi3 \
+        else (lambda stem: [(stem, (c, c, 3, 3))])
+    parts = []
+
+    def wb(name, shape):
+        w, b = sd.get(name + ".weight"), sd.get(name + ".bias")
+        if w is None or b is None:
+            raise ValueError(f"Swin2SR checkpoint lacks {name}.{'weight' if w is None else 'bias'}")
+        if tuple(w.shape) != shape or tuple(b.shape) != (shape[0],):
+            raise ValueError(f"Swin2SR {name}: weight {tuple(w.shape)}, expected {shape}")
+        parts.extend([_as_f32(w), _as_f32(b)])
+
+    def tensor(name, shape=None):
+        t = sd.get(name)
+        if t is None or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"Swin2SR {name}: {None if t is None else tuple(t.shape)}, expected {shape}")
+        return _as_f32(t)
+
+    def proj_of(stem):
+        """PatchEmbed.proj of network_swin2sr.py, a 1x1 conv C -> C, as ([C, C], [C]) float64; the identity where a checkpoint has none."""
+        if stem + ".weight" not in sd:
+            return np.eye(c, dtype=np.float64), np.zeros(c, dtype=np.float64)
+        w, b = tensor(stem + ".weight", (c, c, 1, 1)), tensor(stem + ".bias", (c,))
+        return w.reshape(c, c).astype(np.float64), b.astype(np.float64)
+
+    def wb_then_proj(name, shape, stem):
+        """A conv whose output feeds only the 1x1 conv `stem`: the two are one conv, P W and P b + p (float64 on the host)."""
+        wb(name, shape)
+        if stem + ".weight" in sd:
+            pw, pb = proj_of(stem)
+            w, b = parts[-2].astype(np.float64).reshape(shape[0], -1), parts[-1].astype(np.float64)
+            parts[-2:] = [(pw @ w).astype(np.float32).ravel(), (pw @ b + pb).astype(np.float32)]
+
+    wb("conv_first", (c, 3, 3, 3))
+    pw, pb = proj_of("patch_embed.proj")
+    parts.extend([pw.astype(np.float32).ravel(), pb.astype(np.float32)])
+    wb("patch_embed.norm", (c,))
+    for i, depth in enumerate(depths):
+        for j in range(depth):
+            b = f"layers.{i}.residual_group.blocks.{j}."
+            qb, vb = sd.get(b + "attn.q_bias"), sd.get(b + "attn.v_bias")
+            zeros = np.zeros(c, dtype=np.float32)
+            parts += [tensor(b + "attn.qkv.weight", (3 * c, c)), zeros if qb is None else tensor(b + "attn.q_bias", (c,)), zeros,
+                      zeros if vb is None else tensor(b + "attn.v_bias", (c,))]
+            w0 = tensor(b + "attn.cpb_mlp.0.weight")
+            if w0.size % 2:
+                raise ValueError(f"Swin2SR {b}attn.cpb_mlp.0.weight: {tuple(sd[b + 'attn.cpb_mlp.0.weight'].shape)}, expected (hidden, 2)")
+            hid = w0.size // 2
+            table = swin2sr_bias_table(w0.reshape(hid, 2), tensor(b + "attn.cpb_mlp.0.bias", (hid,)),
+                                       tensor(b + "attn.cpb_mlp.2.weight", (heads, hid)).reshape(heads, hid))
+            parts += [table.ravel(), swin2sr_head_scale(tensor(b + "attn.logit_scale", (heads, 1, 1)))]
+            wb(b + "attn.proj", (c, c))
+            wb(b + "norm1", (c,))
+            wb(b + "mlp.fc1", (hidden, c))
+            wb(b + "mlp.fc2", (c, hidden))
+            wb(b + "norm2", (c,))
+        convs = resi(f"layers.{i}.conv")
+        for name, shape in convs[:-1]:
+            wb(name, shape)
+        wb_then_proj(*convs[-1], f"layers.{i}.patch_embed.proj")
+    wb("norm", (c,))
+    for name, shape in resi("conv_after_body") + tail:
+        wb(name, shape)
+    config = dict(embed_dim=c, depths=tuple(depths), num_heads=heads, mlp_hidden=hidden, resi_3conv=int(resi3),
+                  upsampler=SWIN2SR_UPSAMPLERS[upsampler], scale=scale)
+    return np.ascontiguousarray(np.concatenate(parts)), config
+
+
 SCUNET_MARKS = ("m_head.0.weight", "m_down1.0.trans_block.msa.relative_position_params")
 SCUNET_STAGES = ("m_down1", "m_down2", "m_down3", "m_body", "m_up3", "m_up2", "m_up1")
 
@@ -365,13 +542,16 @@ def parse_scunet_state_dict(sd):
 
 
 def upscaler_family(sd):
-    """"scunet" | "swinir" | "rrdb" | "compact" by the key layout: m_head.0.weight together with the first block's
-    relative_position_params marks a ScuNET; the first block's attn.qkv.weight marks a SwinIR network (it has a conv_first.weight
+    """"scunet" | "swin2sr" | "swinir" | "rrdb" | "compact" by the key layout: m_head.0.weight together with the first block's
+    relative_position_params marks a ScuNET; the first block's attn.logit_scale marks a Swin2SR network (it has an attn.qkv.weight
+    too, so this test comes before the next); the first block's attn.qkv.weight marks a SwinIR network (it has a conv_first.weight
     too, so this test comes before the next); conv_first.weight / model.0.weight mark an RRDBNet, a 4-d body.0.weight without them a
     compact network.  Anything else counts as "rrdb" and gets that loader's refusal."""
     keys = _unwrap_state_dict(sd)
     if all(k in keys for k in SCUNET_MARKS):
         return "scunet"
+    if SWIN2SR_MARK in keys:
+        return "swin2sr"
     if SWINIR_MARK in keys:
         return "swinir"
     if "conv_first.weight" not in keys and "model.0.weight" not in keys and len(getattr(keys.get("body.0.weight"), "shape", ())) == 4:
@@ -381,11 +561,11 @@ def upscaler_family(sd):
 
 def parse_upscaler_state_dict(sd):
     """The dispatcher over the checkpoints the engine runs -> ("rrdb", parse_esrgan_state_dict(sd)), ("compact",
-    parse_compact_state_dict(sd)), ("swinir", (blob, config, scale)) or ("scunet", (blob, config, 1)); the scale is the last member of
-    each tuple."""
+    parse_compact_state_dict(sd)), ("swinir", (blob, config, scale)), ("swin2sr", (blob, config, scale)) or ("scunet", (blob, config, 1));
+    the scale is the last member of each tuple."""
     family = upscaler_family(sd)
-    if family in ("swinir", "scunet"):
-        blob, config = (parse_swinir_state_dict if family == "swinir" else parse_scunet_state_dict)(sd)
+    if family in ("swinir", "swin2sr", "scunet"):
+        blob, config = {"swinir": parse_swinir_state_dict, "swin2sr": parse_swin2sr_state_dict, "scunet": parse_scunet_state_dict}[family](sd)
         return family, (blob, config, config["scale"])
     return family, (parse_compact_state_dict if family == "compact" else parse_esrgan_state_dict)(sd)
 
@@ -533,6 +713,11 @@ class CompactNet:
 
 class SwinIRNet:
     """One SwinIR network (nearest+conv upsampler) resident on an engine (sdmi_swinir_*): the twin of EsrganNet."""
+    _abi = "sdmi_swinir"                                     # the C entries of this class: <_abi>_destroy / _scratch_bytes / _run
+
+    def _fn(self, name):
+        from . import _lib
+        return getattr(_lib.lib, f"{self._abi}_{name}")
 
     def __init__(self, state_dict, device=0, engine=None):
         from . import _lib
@@ -554,7 +739,7 @@ class SwinIRNet:
     def close(self):
         if getattr(self, "handle", None):
             from . import _lib
-            _lib.lib.sdmi_swinir_destroy(self.handle)
+            self._fn("destroy")(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -566,7 +751,7 @@ class SwinIRNet:
     def scratch_bytes(self, b, h, w):
         """Arena bytes of one run, from the engine's own layout (sdmi_swinir_scratch_bytes; 0 for a size the engine refuses)."""
         from . import _lib
-        return int(_lib.lib.sdmi_swinir_scratch_bytes(self.handle, b, h, w))
+        return int(self._fn("scratch_bytes")(self.handle, b, h, w))
 
     def check_fits(self, b, h, w):
         """Refuse an input whose intermediates (token tensors of the padded grid, the qkv and MLP rows, the (H s) x (W s) x 64 tail) the
@@ -595,9 +780,33 @@ class SwinIRNet:
         s = self.scale
         out = (torch.empty((b, h * s, w * s, 3), dtype=torch.uint8, device=x.device) if out_u8
                else torch.empty((b, 3, h * s, w * s), dtype=torch.float32, device=x.device))
-        _lib.check(_lib.lib.sdmi_swinir_run(self.handle, _lib.ptr(x), 1 if in_u8 else 0, b, h, w, _lib.ptr(out), 1 if out_u8 else 0,
-                                            _lib.stream_ptr()), "sdmi_swinir_run")
+        _lib.check(self._fn("run")(self.handle, _lib.ptr(x), 1 if in_u8 else 0, b, h, w, _lib.ptr(out), 1 if out_u8 else 0, _lib.stream_ptr()),
+                   self._abi + "_run")
         return out
+
+
+class Swin2SRNet(SwinIRNet):
+    """One Swin2SR network (nearest+conv, pixelshuffle or pixelshuffledirect upsampler) resident on an engine (sdmi_swin2sr_*): the
+    twin of SwinIRNet, whose size checks and run() it shares."""
+    _abi = "sdmi_swin2sr"
+
+    def __init__(self, state_dict, device=0, engine=None):
+        from . import _lib
+        from .engine import Engine
+        blob, self.config = parse_swin2sr_state_dict(state_dict)
+        self.scale = self.config["scale"]
+        self.device = int(device)
+        self.engine = engine or Engine(self.device)
+        cfg = _lib.Swin2SRConfigC()
+        cfg.embed_dim, cfg.num_layers, cfg.num_heads = self.config["embed_dim"], len(self.config["depths"]), self.config["num_heads"]
+        cfg.mlp_hidden, cfg.resi_3conv, cfg.scale = self.config["mlp_hidden"], self.config["resi_3conv"], self.scale
+        cfg.upsampler = SWIN2SR_UPSAMPLERS.index(self.config["upsampler"])
+        for i, d in enumerate(self.config["depths"]):
+            cfg.depths[i] = d
+        import ctypes
+        self.handle = _lib.lib.sdmi_swin2sr_create(self.engine.handle, blob.ctypes.data, blob.size, ctypes.byref(cfg))
+        if not self.handle:
+            raise _lib.SdmiError("sdmi_swin2sr_create failed: " + _lib.last_error())
 
 
 class ScuNETNet:
@@ -665,8 +874,8 @@ class ScuNETNet:
 
 
 def make_upscaler_net(state_dict, device=0, engine=None):
-    """EsrganNet, CompactNet, SwinIRNet or ScuNETNet, by the checkpoint's key layout (upscaler_family)."""
-    cls = {"compact": CompactNet, "swinir": SwinIRNet, "scunet": ScuNETNet}.get(upscaler_family(state_dict), EsrganNet)
+    """EsrganNet, CompactNet, SwinIRNet, Swin2SRNet or ScuNETNet, by the checkpoint's key layout (upscaler_family)."""
+    cls = {"compact": CompactNet, "swinir": SwinIRNet, "swin2sr": Swin2SRNet, "scunet": ScuNETNet}.get(upscaler_family(state_dict), EsrganNet)
     return cls(state_dict, device=device, engine=engine)
 
 
@@ -676,7 +885,8 @@ class UpscalerESRGAN(Upscaler):
     VRAM this card does not lack), with the uint8 hand-off of modules/upscaler_utils.py.  RRDBNet checkpoints run as EsrganNet, the
     compact Real-ESRGAN models (General 4xV3, General WDN 4xV3, AnimeVideo) as CompactNet.  SwinIR checkpoints (nearest+conv upsampler)
     run as SwinIRNet: what extensions-builtin/SwinIR's UpscalerSwinIR.do_upscale computes with the image in one tile (SWIN_tile exists
-    for the same VRAM reason as ESRGAN_tile), the padding to the window size done on the device.  ScuNET checkpoints run as ScuNETNet:
+    for the same VRAM reason as ESRGAN_tile), the padding to the window size done on the device; Swin2SR checkpoints (what the extension
+    builds from swinir_model_arch_v2.py) run as Swin2SRNet the same way.  ScuNET checkpoints run as ScuNETNet:
     extensions-builtin/ScuNET's UpscalerScuNET.do_upscale with the image in one tile; the result has the input's size and the driver
     loop of Upscaler.upscale fits it with Lanczos."""
     name = "ESRGAN"
@@ -716,8 +926,8 @@ class UpscalerESRGAN(Upscaler):
 def register_esrgan(paths, device=0, engine=None):
     """Append one ``UpscalerData(name, path, scaler, scale)`` per checkpoint to shared.sd_upscalers (after the built-ins, which are
     installed first if the list is empty): `paths` is a {name: path} mapping or a list of paths (name = the file's stem), so
-    hr_upscaler="R-ESRGAN 4x+" and opts.upscaler_for_img2img resolve through _resize_to.  RRDBNet, compact (SRVGGNetCompact), SwinIR
-    and ScuNET checkpoints may be mixed; the scale is read from the checkpoint.
+    hr_upscaler="R-ESRGAN 4x+" and opts.upscaler_for_img2img resolve through _resize_to.  RRDBNet, compact (SRVGGNetCompact), SwinIR,
+    Swin2SR and ScuNET checkpoints may be mixed; the scale is read from the checkpoint.
     engine: see UpscalerESRGAN (all entries of one call share one scaler object and so one engine)."""
     if not shared.sd_upscalers:
         shared.sd_upscalers = builtin_upscalers()

@@ -723,9 +723,11 @@ def install_swinir_hook(webui_shared, device_index: int = 0):
     """Point the webui's SwinIR scaler objects (extensions-builtin/SwinIR/scripts/swinir_model.py) at the engine: install_esrgan_hook for
     the entries of ``webui_shared.sd_upscalers`` whose scaler class is UpscalerSwinIR.  Name, path / download resolution and the
     ``Upscaler.upscale`` driver loop stay; ``do_upscale(img, model_file)`` runs the checkpoint as sdmi_swinir_run on the image whole
-    instead of as a torch module in SWIN_tile tiles.  The same fall-back rules: a URL that is not on disk yet, a checkpoint the loader
-    refuses (another upsampler or window size, ape, head dim > 32) or that fails to load or pack, and an image too large for the arena
-    stay on the stock path.  Returns the names of the hooked entries."""
+    instead of as a torch module in SWIN_tile tiles; a Swin2SR checkpoint (the ``*.v2.pth`` files the extension builds from
+    swinir_model_arch_v2.py, the classical / lightweight Swin2SR models) is recognised by its keys and runs as sdmi_swin2sr_run.  The
+    same fall-back rules: a URL that is not on disk yet, a checkpoint the loader refuses (another upsampler or window size, ape, head
+    dim > 32) or that fails to load or pack, and an image too large for the arena stay on the stock path.  Returns the names of the
+    hooked entries."""
     return _install_whole_image_hook(webui_shared, device_index, "UpscalerSwinIR")
 
 
