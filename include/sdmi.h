@@ -647,7 +647,7 @@ int sdmi_swinir_run(sdmi_swinir* h, const void* in, int in_u8, int B, int H, int
 
 /* ---- Swin2SR upscalers --------------------------------------------------------------------------------------------------------------- */
 
-/* Cosine window attention of one Swin-V2 block (csrc/swin2sr.hip), window size 8, head dim <= 32: sdmi_swin_attention's geometry,
+/* Cosine window attention of one Swin-V2 block (csrc/swinir.hip), window size 8, head dim <= 32: sdmi_swin_attention's geometry,
  * layout, roll / partition / mask handling (-100, not -inf) and refusals, with WindowAttention.forward of Swin2SR's
  * network_swin2sr.py between its qkv and proj linears:
  *   softmax(normalize(q) normalize(k)^T * exp(min(logit_scale, ln 100)) + 16 sigmoid(cpb_mlp(coords))[index] + mask) v.

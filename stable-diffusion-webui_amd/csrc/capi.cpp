@@ -757,10 +757,10 @@ int sdmi_swinir_run(sdmi_swinir* h, const void* in, int in_u8, int B, int H, int
 int sdmi_swin2_attention(const sdmi_swin2_attn_desc* d, void* stream) {
     API_GUARD_BEGIN
     SDMI_REQUIRE(d, "null descriptor");
-    Swin2AttnP p{};
+    SwinAttnP p{};
     p.qkv = (const half_t*)d->qkv; p.bias = (const float*)d->bias; p.out = (half_t*)d->out; p.head_scale = (const float*)d->head_scale;
-    p.B = d->B; p.H = d->H; p.W = d->W; p.heads = d->heads; p.D = d->D; p.ldq = d->ldq; p.ldo = d->ldo; p.shift = d->shift;
-    return launch_swin2_attention(p, (hipStream_t)stream);
+    p.B = d->B; p.H = d->H; p.W = d->W; p.heads = d->heads; p.D = d->D; p.ldq = d->ldq; p.ldo = d->ldo; p.shift = d->shift; p.cosine = 1;
+    return launch_swin_attention(p, (hipStream_t)stream);
     API_GUARD_END
 }
 

@@ -289,42 +289,34 @@ struct CompactP {
 };
 int launch_compact_conv(const CompactP& p, hipStream_t s);
 
-// ---- SwinIR: shifted-window attention, padded-row LayerNorm, input / output / activation passes (swinir.hip) --
+// ---- SwinIR / Swin2SR: shifted-window attention (scaled or cosine score), padded-row LayerNorm (plain or res-post-norm), input /
+// ---- output / activation passes, pixel shuffles (swinir.hip) ---------------------------------------------------
 struct SwinAttnP {
     const half_t* qkv;     // token rows [B*H*W][ldq]: head h has q / k / v in 32-wide slots at columns h*32, (heads + h)*32, (2 heads + h)*32;
                            // dims 0 .. D-1 are real, the slot's tail is zero
-    const float* bias;     // [heads][64][64]: relative-position bias of (query, key) inside a window
+    const float* bias;     // [heads][64][64]: relative-position bias of (query, key) inside a window (Swin2SR: 16 sigmoid(cpb_mlp(coords)), expanded)
     half_t* out;           // token rows [B*H*W][ldo]: head h at columns h*32, dims D .. 31 stored as zero
     int B, H, W;           // token grid; H, W multiples of the window size 8
     int heads, D, ldq, ldo;
     int shift;             // 0 | 4: cyclic shift of the window grid (with 4 the region mask is applied)
-    float scale;           // D^-1/2
+    float scale;           // !cosine: D^-1/2; the score is (q . k) scale + bias + mask
+    const float* head_scale;   // cosine: [heads], exp(min(logit_scale, ln 100)); the score is cos(q, k) head_scale[h] + bias + mask
+    int cosine;            // 0: SwinIR / ScuNET | 1: Swin-V2 (Swin2SR)
 };
 int launch_swin_attention(const SwinAttnP& p, hipStream_t s);
 // LayerNorm over the first C columns of ld-wide rows (ld >= C rounded up to 64); the columns up to that width are written as zeros
 int launch_swin_layernorm(const half_t* x, const float* gamma, const float* beta, half_t* out, int64_t rows, int C, int ld, float eps,
                           hipStream_t s);
+// out = resid + LayerNorm(y) over the first C columns of ld-wide rows; columns C .. roundup(C, 64) - 1 of out are written as zeros;
+// out == resid is allowed
+int launch_swin2_layernorm_add(const half_t* y, const float* gamma, const float* beta, const half_t* resid, half_t* out, int64_t rows, int C,
+                               int ld, float eps, hipStream_t s);
 // RGB image (uint8 HWC / 255, or fp32 NCHW) -> reflect-padded to Hp x Wp, minus the mean -> NHWC fp16 rows of cpad channels
 int launch_swin_input(const void* in, int u8, half_t* out, int B, int H, int W, int Hp, int Wp, int cpad, hipStream_t s);
 int launch_swin_lrelu(half_t* x, int64_t n, float slope, hipStream_t s);               // in place
 // fp32 [B][3][Hp][Wp] cropped to H x W -> fp32 NCHW or (out_u8) uint8 HWC
 int launch_swin_output(const float* src, void* out, int out_u8, int B, int H, int W, int Hp, int Wp, hipStream_t s);
 
-// ---- Swin2SR: cosine window attention, res-post-norm LayerNorm, pixel shuffles (swin2sr.hip) --------------------
-struct Swin2AttnP {        // SwinAttnP's layout; the score is cos(q, k) head_scale[h] + bias + mask
-    const half_t* qkv;
-    const float* bias;     // [heads][64][64]: 16 sigmoid(cpb_mlp(coords)), expanded
-    half_t* out;
-    int B, H, W;
-    int heads, D, ldq, ldo;
-    int shift;
-    const float* head_scale;   // [heads]: exp(min(logit_scale, ln 100))
-};
-int launch_swin2_attention(const Swin2AttnP& p, hipStream_t s);
-// out = resid + LayerNorm(y) over the first C columns of ld-wide rows; columns C .. roundup(C, 64) - 1 of out are written as zeros;
-// out == resid is allowed
-int launch_swin2_layernorm_add(const half_t* y, const float* gamma, const float* beta, const half_t* resid, half_t* out, int64_t rows, int C,
-                               int ld, float eps, hipStream_t s);
 // PixelShuffle(f), f = 2 | 3: src [B*H*W][f*f*64] with the channels in (i, j, c) order -> dst [B][H f][W f][64]
 int launch_swin2_pixel_shuffle(const half_t* src, half_t* dst, int B, int H, int W, int f, hipStream_t s);
 // src [B*Hp*Wp][ld], channels c f^2 + i f + j -> PixelShuffle(f), + mean, cropped to (H f) x (W f) -> fp32 NCHW or (out_u8) uint8 HWC

@@ -2512,6 +2512,15 @@ static int swinir_pass(Run& r, const sdmi_swinir& n, const void* in, int in_u8, 
     } else {
         TRY(lnorm(n.pe_norm, feat, x));
     }
+    auto attention = [&](const sdmi_swinir::Block& bk, size_t j) -> int {    // qkv -> att
+        if (r.dry) return 0;
+        SwinAttnP a{};
+        a.qkv = qkv; a.bias = bk.bias; a.out = att; a.B = B; a.H = Hp; a.W = Wp; a.heads = n.cfg.num_heads; a.D = n.D;
+        a.ldq = n.ldq; a.ldo = n.lda; a.shift = (j & 1) ? 4 : 0;
+        if (n.v2) { a.cosine = 1; a.head_scale = bk.head_scale; }
+        else a.scale = 1.0f / sqrtf((float)n.D);
+        return launch_swin_attention(a, r.s);
+    };
     for (const sdmi_swinir::Layer& L : n.layers) {
         half_t* cur = x;
         for (size_t j = 0; j < L.blocks.size(); ++j) {
@@ -2525,12 +2534,7 @@ static int swinir_pass(Run& r, const sdmi_swinir& n, const void* in, int in_u8, 
                     return r.dry ? 0 : launch_swin2_layernorm_add(ln, w.g, w.b, resid, o, (int64_t)M, n.C, Cp, 1e-5f, r.s);
                 };
                 TRY(conv(bk.qkv, cur, nullptr, qkv));
-                if (!r.dry) {
-                    Swin2AttnP a{};
-                    a.qkv = qkv; a.bias = bk.bias; a.out = att; a.B = B; a.H = Hp; a.W = Wp; a.heads = n.cfg.num_heads; a.D = n.D;
-                    a.ldq = n.ldq; a.ldo = n.lda; a.shift = (j & 1) ? 4 : 0; a.head_scale = bk.head_scale;
-                    TRY(launch_swin2_attention(a, r.s));
-                }
+                TRY(attention(bk, j));
                 TRY(conv(bk.proj, att, nullptr, ln));
                 TRY(lnadd(bk.n1, cur, dst));
                 TRY(conv(bk.fc1, dst, nullptr, hid, EP_GELU));
@@ -2543,12 +2547,7 @@ static int swinir_pass(Run& r, const sdmi_swinir& n, const void* in, int in_u8, 
             half_t* nxt = free_.back(); free_.pop_back();
             TRY(lnorm(bk.n1, cur, ln));
             TRY(conv(bk.qkv, ln, nullptr, qkv));
-            if (!r.dry) {
-                SwinAttnP a{};
-                a.qkv = qkv; a.bias = bk.bias; a.out = att; a.B = B; a.H = Hp; a.W = Wp; a.heads = n.cfg.num_heads; a.D = n.D;
-                a.ldq = n.ldq; a.ldo = n.lda; a.shift = (j & 1) ? 4 : 0; a.scale = 1.0f / sqrtf((float)n.D);
-                TRY(launch_swin_attention(a, r.s));
-            }
+            TRY(attention(bk, j));
             TRY(conv(bk.proj, att, cur, mid));
             TRY(lnorm(bk.n2, mid, ln));
             TRY(conv(bk.fc1, ln, nullptr, hid, EP_GELU));
@@ -2608,6 +2607,31 @@ static int swinir_pass(Run& r, const sdmi_swinir& n, const void* in, int in_u8, 
     return launch_swin_output(full, out, out_u8, B, H * sc, W * sc, Hp * sc, Wp * sc, r.s);
 }
 
+// The networks that are one pass over the arena (swinir_pass, scunet_pass), pass(Run&): what a dry walk takes from a private arena ...
+template <class Pass>
+static int64_t pass_scratch_bytes(sdmi_engine* e, Pass pass) {
+    Arena ar;
+    ar.dry = true;
+    Run dry(e, nullptr, true, &ar);
+    if (pass(dry) != 0) return 0;
+    return (int64_t)ar.high;
+}
+// ... and the run: a dry walk sizes the engine's arena, then the real one
+template <class Pass>
+static int run_pass(sdmi_engine* e, hipStream_t s, Pass pass) {
+    const bool tiling = e->tiling;                            // p.tiling belongs to the diffusion model's convs, not to an upscaler's
+    e->tiling = false;
+    struct Restore { sdmi_engine* e; bool v; ~Restore() { e->tiling = v; } } restore{e, tiling};
+    Run dry{e, s, true};
+    e->arena.dry = true; e->arena.high = 0;
+    const int rc = pass(dry);
+    e->arena.dry = false;
+    TRY(rc);
+    TRY(ensure_arena(e, e->arena.high, s));
+    Run run{e, s, false};
+    return pass(run);
+}
+
 static bool swinir_size_ok(const sdmi_swinir& n, int B, int H, int W) {
     if (B <= 0 || H < 8 || W < 8) return false;
     const long long M = (long long)B * rup(H, 8) * rup(W, 8);
@@ -2617,11 +2641,7 @@ static bool swinir_size_ok(const sdmi_swinir& n, int B, int H, int W) {
 
 int64_t swinir_scratch_bytes(const sdmi_swinir* n, int B, int H, int W) {
     if (!n || !swinir_size_ok(*n, B, H, W)) return 0;
-    Arena ar;
-    ar.dry = true;
-    Run dry(n->e, nullptr, true, &ar);
-    if (swinir_pass(dry, *n, nullptr, 0, B, H, W, nullptr, 0) != 0) return 0;
-    return (int64_t)ar.high;
+    return pass_scratch_bytes(n->e, [&](Run& r) { return swinir_pass(r, *n, nullptr, 0, B, H, W, nullptr, 0); });
 }
 
 // in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
@@ -2632,17 +2652,7 @@ int swinir_run(sdmi_swinir* n, const void* in, int in_u8, int B, int H, int W, v
     SDMI_REQUIRE(B > 0 && H >= 8 && W >= 8, "image sides must be at least 8 (a smaller side cannot be reflect-padded to a window)");
     SDMI_REQUIRE(swinir_size_ok(*n, B, H, W), "image too large: every intermediate tensor must stay below 2^31 elements");
     SDMI_CHECK_HIP(hipSetDevice(e->device));
-    const bool tiling = e->tiling;                            // p.tiling belongs to the diffusion model's convs, not to an upscaler's
-    e->tiling = false;
-    struct Restore { sdmi_engine* e; bool v; ~Restore() { e->tiling = v; } } restore{e, tiling};
-    Run dry{e, s, true};
-    e->arena.dry = true; e->arena.high = 0;
-    const int rc = swinir_pass(dry, *n, in, in_u8, B, H, W, out, out_u8);
-    e->arena.dry = false;
-    TRY(rc);
-    TRY(ensure_arena(e, e->arena.high, s));
-    Run run{e, s, false};
-    return swinir_pass(run, *n, in, in_u8, B, H, W, out, out_u8);
+    return run_pass(e, s, [&](Run& r) { return swinir_pass(r, *n, in, in_u8, B, H, W, out, out_u8); });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2922,11 +2932,7 @@ static bool scunet_size_ok(int B, int H, int W) {
 
 int64_t scunet_scratch_bytes(const sdmi_scunet* n, int B, int H, int W) {
     if (!n || !scunet_size_ok(B, H, W)) return 0;
-    Arena ar;
-    ar.dry = true;
-    Run dry(n->e, nullptr, true, &ar);
-    if (scunet_pass(dry, *n, nullptr, 0, B, H, W, nullptr, 0) != 0) return 0;
-    return (int64_t)ar.high;
+    return pass_scratch_bytes(n->e, [&](Run& r) { return scunet_pass(r, *n, nullptr, 0, B, H, W, nullptr, 0); });
 }
 
 // in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
@@ -2937,17 +2943,7 @@ int scunet_run(sdmi_scunet* n, const void* in, int in_u8, int B, int H, int W, v
     SDMI_REQUIRE(B > 0 && H >= 1 && W >= 1, "empty image");
     SDMI_REQUIRE(scunet_size_ok(B, H, W), "image too large: every intermediate tensor must stay below 2^31 elements");
     SDMI_CHECK_HIP(hipSetDevice(e->device));
-    const bool tiling = e->tiling;                            // p.tiling belongs to the diffusion model's convs, not to an upscaler's
-    e->tiling = false;
-    struct Restore { sdmi_engine* e; bool v; ~Restore() { e->tiling = v; } } restore{e, tiling};
-    Run dry{e, s, true};
-    e->arena.dry = true; e->arena.high = 0;
-    const int rc = scunet_pass(dry, *n, in, in_u8, B, H, W, out, out_u8);
-    e->arena.dry = false;
-    TRY(rc);
-    TRY(ensure_arena(e, e->arena.high, s));
-    Run run{e, s, false};
-    return scunet_pass(run, *n, in, in_u8, B, H, W, out, out_u8);
+    return run_pass(e, s, [&](Run& r) { return scunet_pass(r, *n, in, in_u8, B, H, W, out, out_u8); });
 }
 
 }  // namespace sdmi
@@ -2989,12 +2985,11 @@ sdmi_engine::~sdmi_engine() {
 
 // The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units; there the upscalers'
 // and the cross-attention chain's kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip, swinir.hip,
-// swin2sr.hip, scunet.hip and xattn_chain.hip on their own (build.sh).
+// scunet.hip and xattn_chain.hip on their own (build.sh).
 #ifndef __HIP__
 #include "rrdb.hip"
 #include "compact.hip"
 #include "swinir.hip"
-#include "swin2sr.hip"
 #include "scunet.hip"
 #include "xattn_chain.hip"
 #endif

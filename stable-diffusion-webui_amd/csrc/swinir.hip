@@ -1,6 +1,9 @@
-// swinir.hip — the kernels of the SwinIR upscalers (Liang et al., "SwinIR: Image Restoration Using Swin Transformer") that the rest of
-// the library has no form of, for gfx950: shifted-window attention, the row LayerNorm of padded token rows, and the small input / output /
-// activation passes.  The linears and convs of the network run on gemm.hip, the 64-channel tail on rrdb.hip (engine.cpp swinir_run).
+// swinir.hip — the kernels of the window-transformer upscalers that the rest of the library has no form of, for gfx950: SwinIR (Liang et
+// al., "SwinIR: Image Restoration Using Swin Transformer") and Swin2SR (Conde et al., "Swin2SR: SwinV2 Transformer for Compressed Image
+// Super-Resolution and Restoration"); ScuNET's wide levels use the attention and the LayerNorm as well.  Shifted-window attention with a
+// scaled or a cosine score, the row LayerNorm of padded token rows with or without the residual add of res-post-norm, the small input /
+// output / activation passes, and the pixel shuffles of Swin2SR's `pixelshuffle` / `pixelshuffledirect` tails.  The linears and convs of
+// the networks run on gemm.hip, the 64-channel tails on rrdb.hip (engine.cpp swinir_pass).
 //
 // swin_window_attn: one workgroup (4 waves) per 8 x 8 window, a wave per head, walking ceil(heads / 4) heads.  The cyclic shift
 // (torch.roll by -shift), the window partition and their inverses are index arithmetic: token a of window (wy, wx) sits at
@@ -18,6 +21,14 @@
 //                  operands alike.  V^T comes from LDS: each wave transposes its head's V [64 tokens][32] into its own [32][68] image.
 //                  A lane ends up with 4 consecutive dims of one query: 8-byte stores.
 // Scores, bias, mask and softmax are fp32; the normalised probabilities are rounded to fp16 for the second MFMA.
+//
+// The cosine form (template argument COSINE; Swin2SR's Swin-V2 blocks) has the same geometry and register layout with the score
+//   cos(q, k) tau_h + bias + mask = (q . k) / (max(|q|, 1e-12) max(|k|, 1e-12)) head_scale[h] + bias[h][a][b] + mask.
+// The MFMA runs on the fp16 q / k AS STORED; the two inverse norms are taken in fp32 from the same slot values and multiply the fp32
+// score.  (Normalising the operands first and rounding them to fp16 again would put the rounding of a unit vector, times tau up to 100,
+// into the logit.)  A lane's 8 q and 8 k values of token 16 j + l16 are a quarter of its slot: the squared norms are two shuffles over
+// {l, l + 16, l + 32, l + 48}.  The query norms are then where the S^T tiles want them (query 16 mi + l16); the norm of key
+// 16 nj + 4 g + r sits in lane 4 g + r: one __shfl each.  A zero row has score 0 x 1e12 = 0: bias and mask alone, never NaN.
 #include "common.h"
 #include "prof.h"
 
@@ -31,6 +42,7 @@ constexpr int SWIN_VLD = 68;                                // row stride (halfs
 __device__ __forceinline__ int swin_region(int u, int n) { return u < n - 8 ? 0 : (u < n - 4 ? 1 : 2); }
 }  // namespace
 
+template <bool COSINE>
 __global__ __launch_bounds__(256) void swin_window_attn_kernel(const SwinAttnP p) {
     __shared__ __attribute__((aligned(16))) half_t vt[4][32 * SWIN_VLD];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -86,11 +98,26 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const SwinAttnP p
         __syncthreads();
         if (act) {
             h8 qf[4], kf[4];
+            [[maybe_unused]] float iq[4], ik[4], tau = 0.f; // COSINE: head_scale / max(|q|, 1e-12) and 1 / max(|k|, 1e-12) of token 16 j + l16
+            if constexpr (COSINE) tau = p.head_scale[h];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const half_t* src = p.qkv + rq[j] * p.ldq + h * 32 + 8 * g;
                 qf[j] = *reinterpret_cast<const h8*>(src);
                 kf[j] = *reinterpret_cast<const h8*>(src + p.heads * 32);
+                if constexpr (COSINE) {
+                    float sq = 0.f, sk = 0.f;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float a = (float)qf[j][e], b = (float)kf[j][e];
+                        sq = fmaf(a, a, sq);
+                        sk = fmaf(b, b, sk);
+                    }
+                    sq += __shfl_xor(sq, 16); sk += __shfl_xor(sk, 16);
+                    sq += __shfl_xor(sq, 32); sk += __shfl_xor(sk, 32);
+                    iq[j] = tau / fmaxf(sqrtf(sq), 1e-12f);
+                    ik[j] = 1.0f / fmaxf(sqrtf(sk), 1e-12f);
+                }
             }
             f4 s[4][4];                                     // [nj][mi]: keys 16 nj + 4 g + r of query 16 mi + l16
 #pragma unroll
@@ -98,6 +125,13 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const SwinAttnP p
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi)
                     s[nj][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[nj], qf[mi], f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            [[maybe_unused]] f4 kn[4];                      // COSINE, [nj][r]: the inverse norm of key 16 nj + 4 g + r, from lane 4 g + r
+            if constexpr (COSINE) {
+#pragma unroll
+                for (int nj = 0; nj < 4; ++nj)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) kn[nj][r] = __shfl(ik[nj], 4 * g + r);
+            }
             const float* bh = p.bias + (long long)h * 4096;
             h8 pf[4][2];                                    // [mi][kk]: the B fragments of O^T = V^T P^T
 #pragma unroll
@@ -107,8 +141,9 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const SwinAttnP p
                 for (int nj = 0; nj < 4; ++nj) {
                     const f4 bv = *reinterpret_cast<const f4*>(bh + (16 * mi + l16) * 64 + 16 * nj + 4 * g);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float v = fmaf((float)((masked[mi] >> (4 * nj + r)) & 1u), -100.0f, fmaf(s[nj][mi][r], p.scale, bv[r]));
+                    for (int r = 0; r < 4; ++r) {                   // the multiplier of the raw score: a constant-folded ternary, evaluated where p.scale was
+                        const float v = fmaf((float)((masked[mi] >> (4 * nj + r)) & 1u), -100.0f,
+                                             fmaf(s[nj][mi][r], COSINE ? iq[mi] * kn[nj][r] : p.scale, bv[r]));
                         s[nj][mi][r] = v;
                         mx = fmaxf(mx, v);
                     }
@@ -160,20 +195,22 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const SwinAttnP p
 }
 
 int launch_swin_attention(const SwinAttnP& p, hipStream_t s) {
-    SDMI_REQUIRE(p.qkv && p.bias && p.out, "null qkv / bias / out");
+    SDMI_REQUIRE(p.qkv && p.bias && p.out && (!p.cosine || p.head_scale), "null qkv / bias / out / head_scale");
     SDMI_REQUIRE(p.B > 0 && p.H > 0 && p.W > 0 && p.H % 8 == 0 && p.W % 8 == 0, "H and W must be positive multiples of the window size 8");
     SDMI_REQUIRE(p.heads >= 1 && p.heads <= 1024, "heads");
     SDMI_REQUIRE(p.D >= 1 && p.D <= 32, "head dim D must be in 1..32 (one 32-wide slot per head)");
     SDMI_REQUIRE(p.shift == 0 || p.shift == 4, "shift must be 0 or 4 (half a window)");
     SDMI_REQUIRE(p.ldq >= 96 * p.heads, "qkv rows hold 3 x heads slots of 32: ldq >= 96 heads");
     SDMI_REQUIRE(p.ldo >= 32 * p.heads, "out rows hold heads slots of 32: ldo >= 32 heads");
-    SDMI_REQUIRE(p.ldq % 8 == 0 && p.ldo % 8 == 0 && ((uintptr_t)p.qkv & 15) == 0 && ((uintptr_t)p.out & 15) == 0 && ((uintptr_t)p.bias & 15) == 0,
-                 "misaligned: qkv / out / bias bases on 16 bytes, ldq and ldo multiples of 8");
+    SDMI_REQUIRE(p.ldq % 8 == 0 && p.ldo % 8 == 0 && ((uintptr_t)p.qkv & 15) == 0 && ((uintptr_t)p.out & 15) == 0 && ((uintptr_t)p.bias & 15) == 0 &&
+                     (!p.cosine || ((uintptr_t)p.head_scale & 3) == 0),
+                 "misaligned: qkv / out / bias bases on 16 bytes, head_scale on 4, ldq and ldo multiples of 8");
     SDMI_REQUIRE((long long)p.B * p.H * p.W < (1ll << 31) - 256, "B*H*W must stay below 2^31 tokens");
     const long long windows = (long long)p.B * (p.H / 8) * (p.W / 8);
     const double tokens = (double)windows * 64.0;
-    ProfScope ps("swin_window_attn", tokens * p.heads * (2.0 * 64 * 32 * 2), tokens * p.heads * 32 * 2.0 * 4 + (double)windows * p.heads * 16384.0, s);
-    hipLaunchKernelGGL(swin_window_attn_kernel, dim3((unsigned)windows), dim3(256), 0, s, p);
+    ProfScope ps(p.cosine ? "swin2_window_attn" : "swin_window_attn", tokens * p.heads * (2.0 * 64 * 32 * 2), tokens * p.heads * 32 * 2.0 * 4 + (double)windows * p.heads * 16384.0, s);
+    if (p.cosine) hipLaunchKernelGGL(swin_window_attn_kernel<true>, dim3((unsigned)windows), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(swin_window_attn_kernel<false>, dim3((unsigned)windows), dim3(256), 0, s, p);
     SDMI_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -217,19 +254,76 @@ __global__ __launch_bounds__(256) void swin_layernorm_kernel(const half_t* x, co
     }
 }
 
-int launch_swin_layernorm(const half_t* x, const float* gamma, const float* beta, half_t* out, int64_t rows, int C, int ld, float eps,
-                          hipStream_t s) {
-    SDMI_REQUIRE(x && gamma && beta && out, "null argument");
+// res-post-norm: out = resid + LN(y) over the first C columns of ld-wide fp16 rows, fp32 statistics, centred variance, one rounding of
+// the fp32 sum.  Columns C .. Cp - 1 of out are written as zeros.  swin_layernorm's form: a wave per row, three passes over y's row.
+// out == resid is allowed (a lane reads the two resid values it then writes); y must not be out.
+// A kernel of its own, not a template argument of swin_layernorm_kernel: with resid as a last parameter its kernarg load is sunk in front
+// of the third pass and waited for once per row, and the network's time on the MI355X fell outside the parent build's run-to-run spread
+// (profiles/swin_merge_time.md); with resid here, the plain form's code changes instead.
+__global__ __launch_bounds__(256) void swin2_layernorm_add_kernel(const half_t* y, const float* gamma, const float* beta, const half_t* resid,
+                                                                  half_t* out, long long rows, int C, int Cp, int ld, float eps) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                // wave-uniform
+    const half_t* yr = y + row * ld;
+    const half_t* rr = resid + row * ld;
+    half_t* orow = out + row * ld;
+    float sum = 0.f;
+    for (int c = 2 * lane; c < C; c += 128) {
+        const h2 v = *reinterpret_cast<const h2*>(yr + c);
+        sum += (float)v[0] + (c + 1 < C ? (float)v[1] : 0.f);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
+    const float mean = sum / (float)C;
+    float m2 = 0.f;
+    for (int c = 2 * lane; c < C; c += 128) {
+        const h2 v = *reinterpret_cast<const h2*>(yr + c);
+        const float d0 = (float)v[0] - mean, d1 = c + 1 < C ? (float)v[1] - mean : 0.f;
+        m2 += d0 * d0 + d1 * d1;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) m2 += __shfl_xor(m2, m);
+    const float rstd = 1.0f / sqrtf(m2 / (float)C + eps);
+    for (int c = 2 * lane; c < Cp; c += 128) {
+        h2 o = h2{(half_t)0.f, (half_t)0.f};
+        if (c < C) {
+            const h2 v = *reinterpret_cast<const h2*>(yr + c);
+            const h2 x = *reinterpret_cast<const h2*>(rr + c);
+            o[0] = (half_t)((float)x[0] + (((float)v[0] - mean) * rstd * gamma[c] + beta[c]));
+            if (c + 1 < C) o[1] = (half_t)((float)x[1] + (((float)v[1] - mean) * rstd * gamma[c + 1] + beta[c + 1]));
+        }
+        *reinterpret_cast<h2*>(orow + c) = o;
+    }
+}
+
+// one body for both forms: resid == nullptr is the plain LayerNorm
+static int swin_layernorm_launch(const half_t* x, const float* gamma, const float* beta, const half_t* resid, half_t* out, int64_t rows, int C,
+                                 int ld, float eps, hipStream_t s) {
     SDMI_REQUIRE(rows > 0 && C > 0, "empty tensor");
     const int Cp = (C + 63) / 64 * 64;
     SDMI_REQUIRE(ld >= Cp && ld % 2 == 0, "rows must be at least C rounded up to 64 wide (the pad columns are written as zeros)");
-    SDMI_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)out & 3) == 0, "x / out must be 4-byte aligned");
+    SDMI_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)resid & 3) == 0 && ((uintptr_t)out & 3) == 0, "x / resid / out must be 4-byte aligned");
     SDMI_REQUIRE(rows * (int64_t)ld < (1ll << 40), "tensor too large");
-    ProfScope ps("swin_layernorm", 8.0 * rows * C, 4.0 * rows * C, s);
-    hipLaunchKernelGGL(swin_layernorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, gamma, beta, out, (long long)rows, C, Cp,
-                       ld, eps);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    ProfScope ps(resid ? "swin2_layernorm_add" : "swin_layernorm", (resid ? 9.0 : 8.0) * rows * C, (resid ? 6.0 : 4.0) * rows * C, s);
+    if (resid) hipLaunchKernelGGL(swin2_layernorm_add_kernel, grid, dim3(256), 0, s, x, gamma, beta, resid, out, (long long)rows, C, Cp, ld, eps);
+    else hipLaunchKernelGGL(swin_layernorm_kernel, grid, dim3(256), 0, s, x, gamma, beta, out, (long long)rows, C, Cp, ld, eps);
     SDMI_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+int launch_swin_layernorm(const half_t* x, const float* gamma, const float* beta, half_t* out, int64_t rows, int C, int ld, float eps,
+                          hipStream_t s) {
+    SDMI_REQUIRE(x && gamma && beta && out, "null argument");
+    return swin_layernorm_launch(x, gamma, beta, nullptr, out, rows, C, ld, eps, s);
+}
+
+int launch_swin2_layernorm_add(const half_t* y, const float* gamma, const float* beta, const half_t* resid, half_t* out, int64_t rows, int C,
+                               int ld, float eps, hipStream_t s) {
+    SDMI_REQUIRE(y && gamma && beta && resid && out, "null argument");
+    SDMI_REQUIRE(y != out, "y must not be the output (resid may be)");
+    return swin_layernorm_launch(y, gamma, beta, resid, out, rows, C, ld, eps, s);
 }
 
 // The network's input: RGB as uint8 HWC (/ 255) or fp32 NCHW -> reflect-padded right / bottom to Hp x Wp (F.pad(..., 'reflect'):
@@ -303,6 +397,62 @@ int launch_swin_output(const float* src, void* out, int out_u8, int B, int H, in
     const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 65536);
     ProfScope ps("swin_output", 0.0, (out_u8 ? 5.0 : 8.0) * n, s);
     hipLaunchKernelGGL(swin_output_kernel, dim3(grid), dim3(256), 0, s, src, out, out_u8, H, W, Hp, Wp, n);
+    SDMI_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// PixelShuffle(f) of a 64-channel tensor whose producing conv was packed with its output channels in (i, j, c) order: src rows
+// [B*H*W][f*f*64] -> dst [B][H f][W f][64]; the 128 bytes of sub-pixel (i, j) of pixel (y, x) go to pixel (y f + i, x f + j).  A thread
+// per 16 bytes, the reads contiguous.
+__global__ __launch_bounds__(256) void swin2_pixel_shuffle_kernel(const half_t* src, half_t* dst, int H, int W, int f, long long n8) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
+        const int c8 = (int)(i & 7);
+        const int sub = (int)((i >> 3) % (f * f));
+        const long long pix = (i >> 3) / (f * f);
+        const int x = (int)(pix % W), y = (int)((pix / W) % H);
+        const long long b = pix / ((long long)W * H);
+        const long long row = (b * H * f + (long long)y * f + sub / f) * ((long long)W * f) + (long long)x * f + sub % f;
+        *reinterpret_cast<h8*>(dst + row * 64 + 8 * c8) = *reinterpret_cast<const h8*>(src + 8 * i);
+    }
+}
+int launch_swin2_pixel_shuffle(const half_t* src, half_t* dst, int B, int H, int W, int f, hipStream_t s) {
+    SDMI_REQUIRE(src && dst && src != dst && B > 0 && H > 0 && W > 0 && (f == 2 || f == 3), "pixel shuffle: null / empty tensor, or a factor other than 2 | 3");
+    SDMI_REQUIRE(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0, "pixel shuffle: 16-byte aligned tensors");
+    const long long n8 = (long long)B * H * W * f * f * 8;
+    SDMI_REQUIRE(n8 * 8 < (1ll << 40), "tensor too large");
+    const unsigned grid = (unsigned)std::min<long long>((n8 + 255) / 256, 65536);
+    ProfScope ps("swin2_pixel_shuffle", 0.0, 32.0 * n8, s);
+    hipLaunchKernelGGL(swin2_pixel_shuffle_kernel, dim3(grid), dim3(256), 0, s, src, dst, H, W, f, n8);
+    SDMI_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// The output pass of the `pixelshuffledirect` tail: src fp16 rows [B*Hp*Wp][ld] whose columns c f^2 + i f + j are nn.PixelShuffle(f)'s
+// input channels -> + mean, cropped to [H f][W f] -> fp32 NCHW, or uint8 HWC = round_half_even(clamp(y, 0, 1) * 255)
+__global__ __launch_bounds__(256) void swin2_output_shuffle_kernel(const half_t* src, void* out, int u8, int H, int W, int Hp, int Wp, int f, int ld,
+                                                                   long long n) {
+    const int Ho = H * f, Wo = W * f;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        int c, x, y;
+        long long b;
+        if (u8) {
+            c = (int)(i % 3); x = (int)((i / 3) % Wo); y = (int)((i / (3ll * Wo)) % Ho); b = i / (3ll * Wo * Ho);
+        } else {
+            x = (int)(i % Wo); y = (int)((i / Wo) % Ho); c = (int)((i / ((long long)Wo * Ho)) % 3); b = i / (3ll * Wo * Ho);
+        }
+        const float v = (float)src[((b * Hp + y / f) * Wp + x / f) * ld + c * f * f + (y % f) * f + x % f] +
+                        (c == 0 ? 0.4488f : (c == 1 ? 0.4371f : 0.4040f));
+        if (u8) reinterpret_cast<uint8_t*>(out)[i] = (uint8_t)rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f);
+        else reinterpret_cast<float*>(out)[i] = v;
+    }
+}
+int launch_swin2_output_shuffle(const half_t* src, void* out, int out_u8, int B, int H, int W, int Hp, int Wp, int f, int ld, hipStream_t s) {
+    SDMI_REQUIRE(src && out && B > 0 && H > 0 && W > 0 && Hp >= H && Wp >= W, "null / empty output");
+    SDMI_REQUIRE(f >= 2 && f <= 4 && ld >= 3 * f * f, "output shuffle: factor 2..4, rows of at least 3 f^2 channels");
+    const long long n = (long long)B * 3 * H * f * W * f;
+    const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 65536);
+    ProfScope ps("swin2_output_shuffle", 0.0, (out_u8 ? 3.0 : 6.0) * n, s);
+    hipLaunchKernelGGL(swin2_output_shuffle_kernel, dim3(grid), dim3(256), 0, s, src, out, out_u8, H, W, Hp, Wp, f, ld, n);
     SDMI_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -446,7 +446,7 @@ def swin_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps
 
 def swin2_attention(qkv: torch.Tensor, bias: torch.Tensor, head_scale: torch.Tensor, heads: int, d: int, shift: int = 0,
                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Cosine window attention of a Swin2SR (Swin-V2) block (csrc/swin2sr.hip; window 8, head dim d <= 32): swin_attention's layout and
+    """Cosine window attention of a Swin2SR (Swin-V2) block (csrc/swinir.hip; window 8, head dim d <= 32): swin_attention's layout and
     geometry with the score cos(q, k) * head_scale[h] + bias + mask.  bias fp32 [heads, 64, 64] = 16 sigmoid(cpb_mlp(coords)) expanded;
     head_scale fp32 [heads] = exp(min(logit_scale, ln 100)).  The norms are taken in fp32 from the fp16 q / k as stored; a token whose
     q or k is all zero scores bias + mask."""
@@ -470,7 +470,7 @@ def swin2_attention(qkv: torch.Tensor, bias: torch.Tensor, head_scale: torch.Ten
 def swin_layernorm_add(y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, resid: torch.Tensor, eps: float = 1e-5,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """resid + LayerNorm(y) over the first C = len(gamma) columns of fp16 rows [..., ld] (ld >= C rounded up to 64), the res-post-norm
-    of a Swin-V2 block (csrc/swin2sr.hip): columns C .. roundup(C, 64) - 1 of the result are zeros, columns past that keep `out`'s bits.
+    of a Swin-V2 block (csrc/swinir.hip): columns C .. roundup(C, 64) - 1 of the result are zeros, columns past that keep `out`'s bits.
     `out` may be `resid` (in place), not `y`."""
     _lib.require_device()
     assert y.dtype == torch.float16 and y.is_contiguous() and resid.dtype == torch.float16 and resid.is_contiguous() and resid.shape == y.shape

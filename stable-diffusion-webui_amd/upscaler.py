@@ -6,7 +6,7 @@ up in (modules/images.py:276, modules/modelloader.py:136), the ``Upscaler.upscal
 the three built-in PIL scalers (None / Lanczos / Nearest, modules/upscaler.py:107-154).  The RRDBNet family (ESRGAN, Real-ESRGAN) and the
 compact Real-ESRGAN models (SRVGGNetCompact: General 4xV3, General WDN 4xV3, AnimeVideo) run on the engine (``UpscalerESRGAN`` /
 ``register_esrgan`` below, csrc/rrdb.hip and csrc/compact.hip), and so do the SwinIR models with the nearest+conv upsampler
-(``SwinIRNet``, csrc/swinir.hip), the Swin2SR models (``Swin2SRNet``, csrc/swin2sr.hip) and the ScuNET models (``ScuNETNet``, csrc/scunet.hip); other model upscalers register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)``
+(``SwinIRNet``) and the Swin2SR models (``Swin2SRNet``; both csrc/swinir.hip) and the ScuNET models (``ScuNETNet``, csrc/scunet.hip); other model upscalers register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)``
 is called as in the reference.
 """
 from __future__ import annotations

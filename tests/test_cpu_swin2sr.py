@@ -412,21 +412,16 @@ def graph_no(G, case, shift, what):
 
 # ---- the kernels as compiled --------------------------------------------------------------------------------------------------------
 def test_swin2sr_kernels_compile_lean_for_gfx950():
-    """The gfx950 code objects of csrc/swin2sr.hip, from the metadata: no kernel has scratch or spills; swin2_layernorm_add stays within
-    128 VGPRs, swin2_window_attn within 256 (two workgroups of 4 waves per CU) with the MFMAs in its body."""
-    from test_cpu_host import _gfx950_assembly
-    asm = _gfx950_assembly("swin2sr")
-    meta = {}
-    for block in asm.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        meta[name] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\d+)", block)}
-    assert len(meta) == 4 and all("swin2_" in n for n in meta), sorted(meta)
-    for name, m in meta.items():
+    """The gfx950 code objects of csrc/swinir.hip (which holds Swin2SR's kernels too), from the metadata: no kernel has scratch or spills;
+    swin2_layernorm_add stays within 128 VGPRs, the cosine instantiation of swin_window_attn within 256 (two workgroups
+    of 4 waves per CU) with the MFMAs in its body."""
+    from test_cpu_swinir import swin_kernel_meta
+    asm, found = swin_kernel_meta()
+    for name, m in found.values():
         assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, (name, m)
-    lnadd = [n for n in meta if "swin2_layernorm_add" in n]
-    assert len(lnadd) == 1 and meta[lnadd[0]]["vgpr_count"] <= 128, meta
-    attn = [n for n in meta if "swin2_window_attn" in n]
-    assert len(attn) == 1 and meta[attn[0]]["vgpr_count"] <= 256, meta
+    assert found["layernorm_add"][1]["vgpr_count"] <= 128, found
+    attn = [found["cosine_attn"][0]]
+    assert found["cosine_attn"][1]["vgpr_count"] <= 256, found
     body = asm[asm.index(attn[0] + ":"):]
     body = body[:body.index("s_endpgm")]
     assert "scratch_" not in body and body.count("v_mfma_f32_16x16x32_f16") >= 32

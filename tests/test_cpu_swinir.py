@@ -375,20 +375,40 @@ def test_gpu_test_inputs_are_fit_for_the_comparison_rule():
 
 
 # ---- the kernels as compiled --------------------------------------------------------------------------------------------------------
-def test_swinir_kernels_compile_lean_for_gfx950():
-    """The gfx950 code objects of csrc/swinir.hip, from the metadata: no kernel has scratch or spills; swin_window_attn stays within 256
-    VGPRs (two workgroups of 4 waves per CU) and its body holds the MFMAs."""
+# csrc/swinir.hip holds exactly these kernels (fragments of the mangled names; ILb0E / ILb1E: the template argument COSINE false / true)
+SWIN_KERNELS = {"attn": "swin_window_attn_kernelILb0E", "cosine_attn": "swin_window_attn_kernelILb1E",
+                "layernorm": "swin_layernorm_kernelE", "layernorm_add": "swin2_layernorm_add_kernelE",
+                "input": "swin_input_kernelE", "lrelu": "swin_lrelu_kernelE", "output": "swin_output_kernelE",
+                "pixel_shuffle": "swin2_pixel_shuffle_kernelE", "output_shuffle": "swin2_output_shuffle_kernelE"}
+
+
+def swin_kernel_meta():
+    """-> (the gfx950 assembly of csrc/swinir.hip, {key of SWIN_KERNELS: (mangled name, its metadata counts)}); the file must hold the
+    nine kernels of SWIN_KERNELS and no other."""
     from test_cpu_host import _gfx950_assembly
     asm = _gfx950_assembly("swinir")
     meta = {}
     for block in asm.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)
         meta[name] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\d+)", block)}
-    assert len(meta) >= 5 and all("swin_" in n for n in meta), sorted(meta)
-    for name, m in meta.items():
+    assert len(meta) == 9, sorted(meta)
+    found = {}
+    for key, frag in SWIN_KERNELS.items():
+        names = [n for n in meta if frag in n]
+        assert len(names) == 1, (key, sorted(meta))
+        found[key] = (names[0], meta[names[0]])
+    assert len({n for n, _ in found.values()}) == 9, sorted(meta)
+    return asm, found
+
+
+def test_swinir_kernels_compile_lean_for_gfx950():
+    """The gfx950 code objects of csrc/swinir.hip, from the metadata: no kernel has scratch or spills; swin_window_attn (the plain
+    instantiation) stays within 256 VGPRs (two workgroups of 4 waves per CU) and its body holds the MFMAs."""
+    asm, found = swin_kernel_meta()
+    for name, m in found.values():
         assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, (name, m)
-    attn = [n for n in meta if "swin_window_attn" in n]
-    assert len(attn) == 1 and meta[attn[0]]["vgpr_count"] <= 256, meta
+    attn = [found["attn"][0]]
+    assert found["attn"][1]["vgpr_count"] <= 256, found
     body = asm[asm.index(attn[0] + ":"):]
     body = body[:body.index("s_endpgm")]
     assert "scratch_" not in body
