@@ -211,38 +211,27 @@ _SIGS = {
     "sdmi_rrdb_conv": (_i, [C.POINTER(RrdbDesc), _vp]),
     "sdmi_esrgan_blob_floats": (_i64, [_i, _i]),
     "sdmi_esrgan_create": (_vp, [_vp, _vp, _i64, _i, _i, _i]),
-    "sdmi_esrgan_destroy": (None, [_vp]),
-    "sdmi_esrgan_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
-    "sdmi_esrgan_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "sdmi_compact_conv": (_i, [C.POINTER(CompactDesc), _vp]),
     "sdmi_compact_blob_floats": (_i64, [_i, _i]),
     "sdmi_compact_create": (_vp, [_vp, _vp, _i64, _i, _i]),
-    "sdmi_compact_destroy": (None, [_vp]),
-    "sdmi_compact_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
-    "sdmi_compact_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "sdmi_swin_attention": (_i, [C.POINTER(SwinAttnDesc), _vp]),
     "sdmi_swin_layernorm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _f, _vp]),
     "sdmi_swinir_blob_floats": (_i64, [C.POINTER(SwinIRConfigC)]),
     "sdmi_swinir_create": (_vp, [_vp, _vp, _i64, C.POINTER(SwinIRConfigC)]),
-    "sdmi_swinir_destroy": (None, [_vp]),
-    "sdmi_swinir_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
-    "sdmi_swinir_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "sdmi_swin2_attention": (_i, [C.POINTER(Swin2AttnDesc), _vp]),
     "sdmi_swin_layernorm_add": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _vp]),
     "sdmi_swin2sr_blob_floats": (_i64, [C.POINTER(Swin2SRConfigC)]),
     "sdmi_swin2sr_create": (_vp, [_vp, _vp, _i64, C.POINTER(Swin2SRConfigC)]),
-    "sdmi_swin2sr_destroy": (None, [_vp]),
-    "sdmi_swin2sr_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
-    "sdmi_swin2sr_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "sdmi_scu_block": (_i, [C.POINTER(ScuBlockDesc), _vp]),
     "sdmi_scu_block_pack_bytes": (_i64, [_i]),
     "sdmi_scu_block_pack": (_i, [_vp] * 13 + [_i, _vp]),
     "sdmi_scunet_blob_floats": (_i64, [C.POINTER(ScuNETConfigC)]),
     "sdmi_scunet_create": (_vp, [_vp, _vp, _i64, C.POINTER(ScuNETConfigC)]),
-    "sdmi_scunet_destroy": (None, [_vp]),
-    "sdmi_scunet_scratch_bytes": (_i64, [_vp, _i, _i, _i]),
-    "sdmi_scunet_run": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
 }
+for _net in ("esrgan", "compact", "swinir", "swin2sr", "scunet"):       # the upscaler nets: create / blob_floats differ (above), the rest is one shape
+    _SIGS[f"sdmi_{_net}_destroy"] = (None, [_vp])
+    _SIGS[f"sdmi_{_net}_scratch_bytes"] = (_i64, [_vp, _i, _i, _i])
+    _SIGS[f"sdmi_{_net}_run"] = (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp])
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)       # AttributeError here == the .so does not export a declared symbol
     _fn.restype = _res

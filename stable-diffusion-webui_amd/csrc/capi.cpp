@@ -60,6 +60,18 @@ using namespace sdmi;
         return 1;                                                \
     }
 
+// The sdmi_*_create entries of the upscaler nets: the net, or null with the error set
+template <class Net, class Create>
+static Net* created(Create create) {
+    try {
+        Net* n = nullptr;
+        return create(&n) == 0 ? n : nullptr;
+    } catch (const std::exception& ex) {
+        set_error(std::string("exception: ") + ex.what());
+        return nullptr;
+    }
+}
+
 extern "C" {
 
 int sdmi_version(void) { return SDMI_VERSION; }
@@ -660,14 +672,7 @@ int sdmi_rrdb_conv(const sdmi_rrdb_desc* d, void* stream) {
 int64_t sdmi_esrgan_blob_floats(int num_block, int in_ch) { return esrgan_blob_floats(num_block, in_ch); }
 
 sdmi_esrgan* sdmi_esrgan_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, int num_block, int in_ch, int scale) {
-    try {
-        sdmi_esrgan* n = nullptr;
-        if (esrgan_create(e, (const float*)blob_f32, blob_floats, num_block, in_ch, scale, &n) != 0) return nullptr;
-        return n;
-    } catch (const std::exception& ex) {
-        set_error(std::string("exception: ") + ex.what());
-        return nullptr;
-    }
+    return created<sdmi_esrgan>([&](sdmi_esrgan** n) { return esrgan_create(e, (const float*)blob_f32, blob_floats, num_block, in_ch, scale, n); });
 }
 
 void sdmi_esrgan_destroy(sdmi_esrgan* h) { delete h; }
@@ -695,14 +700,7 @@ int sdmi_compact_conv(const sdmi_compact_desc* d, void* stream) {
 int64_t sdmi_compact_blob_floats(int num_conv, int scale) { return compact_blob_floats(num_conv, scale); }
 
 sdmi_compact* sdmi_compact_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, int num_conv, int scale) {
-    try {
-        sdmi_compact* n = nullptr;
-        if (compact_create(e, (const float*)blob_f32, blob_floats, num_conv, scale, &n) != 0) return nullptr;
-        return n;
-    } catch (const std::exception& ex) {
-        set_error(std::string("exception: ") + ex.what());
-        return nullptr;
-    }
+    return created<sdmi_compact>([&](sdmi_compact** n) { return compact_create(e, (const float*)blob_f32, blob_floats, num_conv, scale, n); });
 }
 
 void sdmi_compact_destroy(sdmi_compact* h) { delete h; }
@@ -734,14 +732,7 @@ int sdmi_swin_layernorm(const void* x, const void* gamma, const void* beta, void
 int64_t sdmi_swinir_blob_floats(const sdmi_swinir_config* cfg) { return swinir_blob_floats(cfg); }
 
 sdmi_swinir* sdmi_swinir_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_swinir_config* cfg) {
-    try {
-        sdmi_swinir* n = nullptr;
-        if (swinir_create(e, (const float*)blob_f32, blob_floats, cfg, &n) != 0) return nullptr;
-        return n;
-    } catch (const std::exception& ex) {
-        set_error(std::string("exception: ") + ex.what());
-        return nullptr;
-    }
+    return created<sdmi_swinir>([&](sdmi_swinir** n) { return swinir_create(e, (const float*)blob_f32, blob_floats, cfg, n); });
 }
 
 void sdmi_swinir_destroy(sdmi_swinir* h) { delete h; }
@@ -775,14 +766,7 @@ int sdmi_swin_layernorm_add(const void* y, const void* gamma, const void* beta, 
 int64_t sdmi_swin2sr_blob_floats(const sdmi_swin2sr_config* cfg) { return swin2sr_blob_floats(cfg); }
 
 sdmi_swin2sr* sdmi_swin2sr_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_swin2sr_config* cfg) {
-    try {
-        sdmi_swin2sr* n = nullptr;
-        if (swin2sr_create(e, (const float*)blob_f32, blob_floats, cfg, &n) != 0) return nullptr;
-        return n;
-    } catch (const std::exception& ex) {
-        set_error(std::string("exception: ") + ex.what());
-        return nullptr;
-    }
+    return created<sdmi_swin2sr>([&](sdmi_swin2sr** n) { return swin2sr_create(e, (const float*)blob_f32, blob_floats, cfg, n); });
 }
 
 void sdmi_swin2sr_destroy(sdmi_swin2sr* h) { delete h; }
@@ -821,14 +805,7 @@ int sdmi_scu_block_pack(const void* ln1_g, const void* ln1_b, const void* wqkv, 
 int64_t sdmi_scunet_blob_floats(const sdmi_scunet_config* cfg) { return scunet_blob_floats(cfg); }
 
 sdmi_scunet* sdmi_scunet_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_scunet_config* cfg) {
-    try {
-        sdmi_scunet* n = nullptr;
-        if (scunet_create(e, (const float*)blob_f32, blob_floats, cfg, &n) != 0) return nullptr;
-        return n;
-    } catch (const std::exception& ex) {
-        set_error(std::string("exception: ") + ex.what());
-        return nullptr;
-    }
+    return created<sdmi_scunet>([&](sdmi_scunet** n) { return scunet_create(e, (const float*)blob_f32, blob_floats, cfg, n); });
 }
 
 void sdmi_scunet_destroy(sdmi_scunet* h) { delete h; }

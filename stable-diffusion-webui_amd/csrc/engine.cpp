@@ -1245,19 +1245,26 @@ static int ensure_arena(Arena& ar, size_t need, hipStream_t s) {
     ar.cap = cap;
     return 0;
 }
-static int ensure_arena(sdmi_engine* e, size_t need, hipStream_t s) { return ensure_arena(e->arena, need, s); }
 
-// one UNet pass over rows [b0, b0 + Bn) of a call of Btot rows, on stream s out of arena ar: dry pass to size the arena (pure host
-// arithmetic), then the launches
+// Every forward is the same walk twice, walk(bool dry) -> int: dry to size the arena (pure host arithmetic: the walk only bump-allocates),
+// then, the arena grown to that, the launches.  A walk that fails dry leaves the arena out of dry mode.
+template <class Walk>
+static int two_pass(Arena& ar, hipStream_t s, Walk walk) {
+    ar.dry = true; ar.high = 0;
+    const int rc = walk(true);
+    ar.dry = false;
+    TRY(rc);
+    TRY(ensure_arena(ar, ar.high, s));
+    return walk(false);
+}
+
+// one UNet pass over rows [b0, b0 + Bn) of a call of Btot rows, on stream s out of arena ar
 static int unet_forward_slice(sdmi_engine* e, Arena& ar, const void* x, const void* t, const void* y, void* out, int io_dtype,
                               int Bn, int b0, int Btot, int h, int w, int L, hipStream_t s) {
-    Run dry(e, s, true, &ar, b0, Btot);
-    ar.dry = true; ar.high = 0;
-    TRY(unet_run(dry, x, t, y, out, io_dtype, Bn, h, w, L));
-    ar.dry = false;
-    TRY(ensure_arena(ar, ar.high, s));
-    Run run(e, s, false, &ar, b0, Btot);
-    return unet_run(run, x, t, y, out, io_dtype, Bn, h, w, L);
+    return two_pass(ar, s, [&](bool dry) {
+        Run r(e, s, dry, &ar, b0, Btot);
+        return unet_run(r, x, t, y, out, io_dtype, Bn, h, w, L);
+    });
 }
 
 int unet_forward(sdmi_engine* e, const void* x, const void* t, const void* ctx, const void* y, void* out, int io_dtype,
@@ -1649,25 +1656,19 @@ static int vae_encode_run(Run& r, const void* x, int io_dtype, float* out, int B
 int vae_decode(sdmi_engine* e, const void* z, int io_dtype, float* out, int B, int h, int w, hipStream_t s) {
     SDMI_REQUIRE(e->vae.ready, "vae not finalized");
     SDMI_CHECK_HIP(hipSetDevice(e->device));
-    Run dry{e, s, true};
-    e->arena.dry = true; e->arena.high = 0;
-    TRY(vae_decode_run(dry, z, io_dtype, out, B, h, w));
-    e->arena.dry = false;
-    TRY(ensure_arena(e, e->arena.high, s));
-    Run run{e, s, false};
-    return vae_decode_run(run, z, io_dtype, out, B, h, w);
+    return two_pass(e->arena, s, [&](bool dry) {
+        Run r(e, s, dry);
+        return vae_decode_run(r, z, io_dtype, out, B, h, w);
+    });
 }
 
 int vae_encode(sdmi_engine* e, const void* x, int io_dtype, float* out, int B, int H, int W, hipStream_t s) {
     SDMI_REQUIRE(e->vae.ready && e->vae.has_encoder, "vae encoder weights not loaded");
     SDMI_CHECK_HIP(hipSetDevice(e->device));
-    Run dry{e, s, true};
-    e->arena.dry = true; e->arena.high = 0;
-    TRY(vae_encode_run(dry, x, io_dtype, out, B, H, W));
-    e->arena.dry = false;
-    TRY(ensure_arena(e, e->arena.high, s));
-    Run run{e, s, false};
-    return vae_encode_run(run, x, io_dtype, out, B, H, W);
+    return two_pass(e->arena, s, [&](bool dry) {
+        Run r(e, s, dry);
+        return vae_encode_run(r, x, io_dtype, out, B, H, W);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1832,13 +1833,10 @@ int engine_clip_forward(sdmi_engine* e, int slot, const int* tokens, const float
     SDMI_REQUIRE(skip >= 1 && skip <= c.cfg.layers, "clip: 1 <= skip <= layers");
     SDMI_REQUIRE(tokens != nullptr && out != nullptr, "null argument");
     SDMI_CHECK_HIP(hipSetDevice(e->device));
-    Run dry{e, s, true};
-    e->arena.dry = true; e->arena.high = 0;
-    TRY(clip_run(dry, c, tokens, inputs_embeds, B, L, skip, apply_final_ln, out, pooled));
-    e->arena.dry = false;
-    TRY(ensure_arena(e, e->arena.high, s));
-    Run run{e, s, false};
-    return clip_run(run, c, tokens, inputs_embeds, B, L, skip, apply_final_ln, out, pooled);
+    return two_pass(e->arena, s, [&](bool dry) {
+        Run r(e, s, dry);
+        return clip_run(r, c, tokens, inputs_embeds, B, L, skip, apply_final_ln, out, pooled);
+    });
 }
 
 int engine_load_unet_tensor(sdmi_engine* e, const char* key, const void* data, int dtype, int ndim, const int64_t* shape,
@@ -2015,6 +2013,69 @@ int engine_set_context(sdmi_engine* e, const void* ctx, int dtype, int Bn, int L
     return unet_set_context(e, ctx, dtype, Bn, L, s, conditional);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Upscaler nets (sdmi_net): what their builds and their runs share
+// ------------------------------------------------------------------------------------------------------------
+// a fresh allocation that the net owns, filled from `host` (null: left for a pack launch to fill)
+static int net_upload(sdmi_net* net, const void* host, size_t bytes, void** dev) {
+    SDMI_CHECK_HIP(hipMalloc(dev, std::max<size_t>(bytes, 256)));
+    net->owned.push_back(*dev);
+    if (host) SDMI_CHECK_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// a norm of width C off the blob cursor: gamma, then beta
+static int net_norm(sdmi_net* net, const float*& src, int C, NormW* n) {
+    n->c = C;
+    TRY(net_upload(net, src, (size_t)C * sizeof(float), (void**)&n->g));
+    TRY(net_upload(net, src + C, (size_t)C * sizeof(float), (void**)&n->b));
+    src += 2 * C;
+    return 0;
+}
+
+// the host blob on the device, for the builds whose pack launches read it there; freed when the build returns
+struct StagedBlob {
+    float* p = nullptr;
+    ~StagedBlob() { (void)hipFree(p); }
+    int stage(const float* blob, int64_t blob_floats) {
+        SDMI_CHECK_HIP(hipMalloc((void**)&p, blob_floats * sizeof(float)));
+        SDMI_CHECK_HIP(hipMemcpy(p, blob, blob_floats * sizeof(float), hipMemcpyHostToDevice));
+        return 0;
+    }
+};
+
+// the relative-position table of an 8 x 8 window, entry (dy + 7) * 15 + (dx + 7) of head h at table[entry * entry_stride + h * head_stride],
+// as the attention kernels read it: bias[h][a][b] = table entry (ya - yb, xa - xb) of head h
+static int net_rel_bias(sdmi_net* net, const float* table, int heads, size_t entry_stride, size_t head_stride, float** dev) {
+    std::vector<float> bias((size_t)heads * 4096);
+    for (int h = 0; h < heads; ++h)
+        for (int a = 0; a < 64; ++a)
+            for (int b = 0; b < 64; ++b)
+                bias[((size_t)h * 64 + a) * 64 + b] =
+                    table[(size_t)(((a >> 3) - (b >> 3) + 7) * 15 + ((a & 7) - (b & 7) + 7)) * entry_stride + h * head_stride];
+    return net_upload(net, bias.data(), bias.size() * sizeof(float), (void**)dev);
+}
+
+// A net's forward is one pass over the arena, pass(Run&): what a dry walk takes from a private arena ...
+template <class Pass>
+static int64_t pass_scratch_bytes(sdmi_engine* e, Pass pass) {
+    Arena ar;
+    ar.dry = true;
+    Run dry(e, nullptr, true, &ar);
+    if (pass(dry) != 0) return 0;
+    return (int64_t)ar.high;
+}
+// ... and the run, out of the engine's arena
+template <class Pass>
+static int run_pass(sdmi_engine* e, hipStream_t s, Pass pass) {
+    const bool tiling = e->tiling;                            // p.tiling belongs to the diffusion model's convs, not to an upscaler's
+    e->tiling = false;
+    struct Restore { sdmi_engine* e; bool v; ~Restore() { e->tiling = v; } } restore{e, tiling};
+    return two_pass(e->arena, s, [&](bool dry) {
+        Run r(e, s, dry);
+        return pass(r);
+    });
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // RRDBNet upscalers (ESRGAN / Real-ESRGAN): BasicSR's RRDBNet.forward (basicsr/archs/rrdbnet_arch.py) as rrdb_conv launches
@@ -2038,22 +2099,18 @@ int esrgan_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int nu
     std::unique_ptr<sdmi_esrgan> net(new sdmi_esrgan);
     net->e = e; net->num_block = num_block; net->in_ch = in_ch; net->scale = scale; net->unshuffle = 4 / scale;
     net->cin0 = rup(in_ch, 32);
-    float* dblob = nullptr;
-    SDMI_CHECK_HIP(hipMalloc((void**)&dblob, blob_floats * sizeof(float)));
-    struct Free { float* p; ~Free() { (void)hipFree(p); } } guard{dblob};
-    SDMI_CHECK_HIP(hipMemcpy(dblob, blob, blob_floats * sizeof(float), hipMemcpyHostToDevice));
+    StagedBlob dblob;
+    TRY(dblob.stage(blob, blob_floats));
     int64_t off = 0;
     auto pack = [&](sdmi_esrgan::Conv* c, int O, int I) -> int {
         c->cin = rup(I, 32); c->nout = O <= 32 ? 32 : 64; c->n_real = O;
         const size_t wb = (size_t)c->nout * 9 * c->cin * sizeof(half_t), bb = (size_t)c->nout * sizeof(float);
-        SDMI_CHECK_HIP(hipMalloc((void**)&c->w, std::max<size_t>(wb, 256)));
-        net->owned.push_back(c->w);
-        SDMI_CHECK_HIP(hipMalloc((void**)&c->b, 256));
-        net->owned.push_back(c->b);
-        TRY(launch_pack_conv_weight(dblob + off, 1, c->w, O, I, 3, 3, c->nout, c->cin, 0, nullptr));
+        TRY(net_upload(net.get(), nullptr, wb, (void**)&c->w));
+        TRY(net_upload(net.get(), nullptr, bb, (void**)&c->b));
+        TRY(launch_pack_conv_weight(dblob.p + off, 1, c->w, O, I, 3, 3, c->nout, c->cin, 0, nullptr));
         off += (int64_t)O * I * 9;
         SDMI_CHECK_HIP(hipMemset(c->b, 0, bb));
-        SDMI_CHECK_HIP(hipMemcpy(c->b, dblob + off, (size_t)O * sizeof(float), hipMemcpyDeviceToDevice));
+        SDMI_CHECK_HIP(hipMemcpy(c->b, dblob.p + off, (size_t)O * sizeof(float), hipMemcpyDeviceToDevice));
         off += O;
         return 0;
     };
@@ -2071,29 +2128,60 @@ int esrgan_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int nu
     return 0;
 }
 
-namespace {
-struct EsrganBufs { half_t *in, *x[3], *feat, *trunk, *u1, *u2, *u3; };
-// the arena layout of one run (pure host arithmetic): M low-resolution pixels
-EsrganBufs esrgan_take(Arena& ar, const sdmi_esrgan& n, size_t M) {
-    EsrganBufs b;
-    ar.reset();
-    b.in = (half_t*)ar.take(M * n.cin0 * sizeof(half_t));
-    for (int i = 0; i < 3; ++i) b.x[i] = (half_t*)ar.take(M * 192 * sizeof(half_t));
-    b.feat = (half_t*)ar.take(M * 64 * sizeof(half_t));
-    b.trunk = (half_t*)ar.take(M * 64 * sizeof(half_t));
-    b.u1 = (half_t*)ar.take(4 * M * 64 * sizeof(half_t));
-    b.u2 = (half_t*)ar.take(16 * M * 64 * sizeof(half_t));
-    b.u3 = (half_t*)ar.take(16 * M * 64 * sizeof(half_t));
-    return b;
+// One pass over the network (dry: the arena layout alone).  M = B * h * w low-resolution pixels
+static int esrgan_pass(Run& r, const sdmi_esrgan& n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8) {
+    const int f = n.unshuffle, h = H / f, w = W / f;
+    const size_t M = (size_t)B * h * w;
+    r.ar->reset();
+    half_t* xin = r.H(M * n.cin0);
+    half_t* x[3];
+    for (half_t*& p : x) p = r.H(M * 192);
+    half_t* feat = r.H(M * 64);
+    half_t* trunk = r.H(M * 64);
+    half_t* u1 = r.H(4 * M * 64);
+    half_t* u2 = r.H(16 * M * 64);
+    half_t* u3 = r.H(16 * M * 64);
+    if (r.dry) return 0;
+
+    auto conv = [&](const sdmi_esrgan::Conv& c, const half_t* src, int lda, int hh, int ww, int up, void* dst, int ldo, int ep,
+                    float alpha = 1.f, const half_t* r1 = nullptr, int ldr1 = 0, float beta = 1.f, const half_t* r2 = nullptr, int ldr2 = 0,
+                    int store = RRDB_ST_F16) -> int {
+        RrdbP p{};
+        p.in = src; p.w = c.w; p.bias = c.b; p.r1 = r1; p.r2 = r2; p.out = dst;
+        p.B = B; p.H = hh; p.W = ww; p.cin = c.cin; p.lda = lda; p.up = up;
+        p.ldo = ldo; p.n_real = c.n_real; p.ldr1 = ldr1; p.ldr2 = ldr2; p.ep = ep; p.store = store; p.alpha = alpha; p.beta = beta;
+        return launch_rrdb_conv(p, c.nout, r.s);
+    };
+
+    TRY(launch_rrdb_input(in, in_u8, xin, B, 3, H, W, f, n.cin0, r.s));
+    // conv_first twice (K = 288: 0.4 % of the network's work): once into `feat`, the trunk's skip tensor that conv_body's epilogue adds,
+    // once into channels 0..63 of the first dense buffer.  conv_body cannot read that skip from x[0]: the third RDB of every RRDB writes
+    // its result over x[0], so by then x[0] holds the body's output, not conv_first's.
+    TRY(conv(n.first, xin, n.cin0, h, w, 0, feat, 64, RRDB_EP_NONE));
+    TRY(conv(n.first, xin, n.cin0, h, w, 0, x[0], 192, RRDB_EP_NONE));
+    // Dense blocks on three rotating 192-wide buffers: RDB j of an RRDB reads x[j] and writes channels 0..63 of x[(j + 1) % 3], so the
+    // third one lands on x[0] — the RRDB's own input, which its epilogue reads as r2 (same element, same lane, before the store).
+    for (int i = 0; i < n.num_block; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const sdmi_esrgan::Conv* c = &n.rdb[((size_t)i * 3 + j) * 5];
+            half_t* src = x[j];
+            half_t* dst = x[(j + 1) % 3];
+            for (int k = 0; k < 4; ++k) TRY(conv(c[k], src, 192, h, w, 0, src + 64 + 32 * k, 192, RRDB_EP_LRELU));
+            if (j < 2) TRY(conv(c[4], src, 192, h, w, 0, dst, 192, RRDB_EP_RES1, 0.2f, src, 192));
+            else TRY(conv(c[4], src, 192, h, w, 0, dst, 192, RRDB_EP_RES2, 0.2f, src, 192, 0.2f, dst, 192));
+        }
+    TRY(conv(n.body, x[0], 192, h, w, 0, trunk, 64, RRDB_EP_RES1, 1.f, feat, 64));
+    TRY(conv(n.up1, trunk, 64, 2 * h, 2 * w, 1, u1, 64, RRDB_EP_LRELU));
+    TRY(conv(n.up2, u1, 64, 4 * h, 4 * w, 1, u2, 64, RRDB_EP_LRELU));
+    TRY(conv(n.hr, u2, 64, 4 * h, 4 * w, 0, u3, 64, RRDB_EP_LRELU));
+    TRY(conv(n.last, u3, 64, 4 * h, 4 * w, 0, out, 0, RRDB_EP_NONE, 1.f, nullptr, 0, 1.f, nullptr, 0,
+             out_u8 ? RRDB_ST_U8_HWC : RRDB_ST_F32_NCHW));
+    return 0;
 }
-}  // namespace
 
 int64_t esrgan_scratch_bytes(const sdmi_esrgan* n, int B, int H, int W) {
     if (!n || B <= 0 || H <= 0 || W <= 0) return 0;
-    Arena ar;
-    ar.dry = true;
-    esrgan_take(ar, *n, (size_t)B * (H / n->unshuffle) * (W / n->unshuffle));
-    return (int64_t)ar.high;
+    return pass_scratch_bytes(n->e, [&](Run& r) { return esrgan_pass(r, *n, nullptr, 0, B, H, W, nullptr, 0); });
 }
 
 // in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
@@ -2106,47 +2194,7 @@ int esrgan_run(sdmi_esrgan* n, const void* in, int in_u8, int B, int H, int W, v
     const int h = H / f, w = W / f;
     SDMI_REQUIRE((long long)B * h * w * 16 < (1ll << 31) - 256, "image too large: B*H*W*16 output pixels must stay below 2^31");
     SDMI_CHECK_HIP(hipSetDevice(e->device));
-    const size_t M = (size_t)B * h * w;
-    e->arena.dry = true; e->arena.high = 0;
-    esrgan_take(e->arena, *n, M);
-    e->arena.dry = false;
-    TRY(ensure_arena(e, e->arena.high, s));
-    const EsrganBufs b = esrgan_take(e->arena, *n, M);
-
-    auto conv = [&](const sdmi_esrgan::Conv& c, const half_t* src, int lda, int hh, int ww, int up, void* dst, int ldo, int ep,
-                    float alpha = 1.f, const half_t* r1 = nullptr, int ldr1 = 0, float beta = 1.f, const half_t* r2 = nullptr, int ldr2 = 0,
-                    int store = RRDB_ST_F16) -> int {
-        RrdbP p{};
-        p.in = src; p.w = c.w; p.bias = c.b; p.r1 = r1; p.r2 = r2; p.out = dst;
-        p.B = B; p.H = hh; p.W = ww; p.cin = c.cin; p.lda = lda; p.up = up;
-        p.ldo = ldo; p.n_real = c.n_real; p.ldr1 = ldr1; p.ldr2 = ldr2; p.ep = ep; p.store = store; p.alpha = alpha; p.beta = beta;
-        return launch_rrdb_conv(p, c.nout, s);
-    };
-
-    TRY(launch_rrdb_input(in, in_u8, b.in, B, 3, H, W, f, n->cin0, s));
-    // conv_first twice (K = 288: 0.4 % of the network's work): once into `feat`, the trunk's skip tensor that conv_body's epilogue adds,
-    // once into channels 0..63 of the first dense buffer.  conv_body cannot read that skip from x[0]: the third RDB of every RRDB writes
-    // its result over x[0], so by then x[0] holds the body's output, not conv_first's.
-    TRY(conv(n->first, b.in, n->cin0, h, w, 0, b.feat, 64, RRDB_EP_NONE));
-    TRY(conv(n->first, b.in, n->cin0, h, w, 0, b.x[0], 192, RRDB_EP_NONE));
-    // Dense blocks on three rotating 192-wide buffers: RDB j of an RRDB reads x[j] and writes channels 0..63 of x[(j + 1) % 3], so the
-    // third one lands on x[0] — the RRDB's own input, which its epilogue reads as r2 (same element, same lane, before the store).
-    for (int i = 0; i < n->num_block; ++i)
-        for (int j = 0; j < 3; ++j) {
-            const sdmi_esrgan::Conv* c = &n->rdb[((size_t)i * 3 + j) * 5];
-            half_t* src = b.x[j];
-            half_t* dst = b.x[(j + 1) % 3];
-            for (int k = 0; k < 4; ++k) TRY(conv(c[k], src, 192, h, w, 0, src + 64 + 32 * k, 192, RRDB_EP_LRELU));
-            if (j < 2) TRY(conv(c[4], src, 192, h, w, 0, dst, 192, RRDB_EP_RES1, 0.2f, src, 192));
-            else TRY(conv(c[4], src, 192, h, w, 0, dst, 192, RRDB_EP_RES2, 0.2f, src, 192, 0.2f, dst, 192));
-        }
-    TRY(conv(n->body, b.x[0], 192, h, w, 0, b.trunk, 64, RRDB_EP_RES1, 1.f, b.feat, 64));
-    TRY(conv(n->up1, b.trunk, 64, 2 * h, 2 * w, 1, b.u1, 64, RRDB_EP_LRELU));
-    TRY(conv(n->up2, b.u1, 64, 4 * h, 4 * w, 1, b.u2, 64, RRDB_EP_LRELU));
-    TRY(conv(n->hr, b.u2, 64, 4 * h, 4 * w, 0, b.u3, 64, RRDB_EP_LRELU));
-    TRY(conv(n->last, b.u3, 64, 4 * h, 4 * w, 0, out, 0, RRDB_EP_NONE, 1.f, nullptr, 0, 1.f, nullptr, 0,
-             out_u8 ? RRDB_ST_U8_HWC : RRDB_ST_F32_NCHW));
-    return 0;
+    return run_pass(e, s, [&](Run& r) { return esrgan_pass(r, *n, in, in_u8, B, H, W, out, out_u8); });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2166,27 +2214,23 @@ int compact_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int n
     SDMI_CHECK_HIP(hipSetDevice(e->device));
     std::unique_ptr<sdmi_compact> net(new sdmi_compact);
     net->e = e; net->num_conv = num_conv; net->scale = scale;
-    float* dblob = nullptr;
-    SDMI_CHECK_HIP(hipMalloc((void**)&dblob, blob_floats * sizeof(float)));
-    struct Free { float* p; ~Free() { (void)hipFree(p); } } guard{dblob};
-    SDMI_CHECK_HIP(hipMemcpy(dblob, blob, blob_floats * sizeof(float), hipMemcpyHostToDevice));
+    StagedBlob dblob;
+    TRY(dblob.stage(blob, blob_floats));
     int64_t off = 0;
     net->convs.resize((size_t)num_conv + 2);
     for (int i = 0; i < num_conv + 2; ++i) {
         sdmi_compact::Conv* c = &net->convs[(size_t)i];
         const int O = i == num_conv + 1 ? 3 * scale * scale : 64, I = i == 0 ? 3 : 64, cin = i == 0 ? 32 : 64;
-        SDMI_CHECK_HIP(hipMalloc((void**)&c->w, (size_t)64 * 9 * cin * sizeof(half_t)));
-        net->owned.push_back(c->w);
-        SDMI_CHECK_HIP(hipMalloc((void**)&c->b, 2 * 64 * sizeof(float)));
-        net->owned.push_back(c->b);
+        TRY(net_upload(net.get(), nullptr, (size_t)64 * 9 * cin * sizeof(half_t), (void**)&c->w));
+        TRY(net_upload(net.get(), nullptr, 2 * 64 * sizeof(float), (void**)&c->b));
         c->slope = c->b + 64;
-        TRY(launch_pack_conv_weight(dblob + off, 1, c->w, O, I, 3, 3, 64, cin, 0, nullptr));
+        TRY(launch_pack_conv_weight(dblob.p + off, 1, c->w, O, I, 3, 3, 64, cin, 0, nullptr));
         off += (int64_t)O * I * 9;
         SDMI_CHECK_HIP(hipMemset(c->b, 0, 2 * 64 * sizeof(float)));
-        SDMI_CHECK_HIP(hipMemcpy(c->b, dblob + off, (size_t)O * sizeof(float), hipMemcpyDeviceToDevice));
+        SDMI_CHECK_HIP(hipMemcpy(c->b, dblob.p + off, (size_t)O * sizeof(float), hipMemcpyDeviceToDevice));
         off += O;
         if (i <= num_conv) {
-            SDMI_CHECK_HIP(hipMemcpy(c->slope, dblob + off, 64 * sizeof(float), hipMemcpyDeviceToDevice));
+            SDMI_CHECK_HIP(hipMemcpy(c->slope, dblob.p + off, 64 * sizeof(float), hipMemcpyDeviceToDevice));
             off += 64;
         }
     }
@@ -2195,23 +2239,38 @@ int compact_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int n
     return 0;
 }
 
-namespace {
-struct CompactBufs { half_t *in, *x[2]; };
-CompactBufs compact_take(Arena& ar, size_t M) {
-    CompactBufs b;
-    ar.reset();
-    b.in = (half_t*)ar.take(M * 32 * sizeof(half_t));
-    for (int i = 0; i < 2; ++i) b.x[i] = (half_t*)ar.take(M * 64 * sizeof(half_t));
-    return b;
+// One pass over the network (dry: the arena layout alone).  M = B * H * W pixels: every activation is at the input's resolution
+static int compact_pass(Run& r, const sdmi_compact& n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8) {
+    const size_t M = (size_t)B * H * W;
+    r.ar->reset();
+    half_t* xin = r.H(M * 32);
+    half_t* x[2];
+    for (half_t*& p : x) p = r.H(M * 64);
+    if (r.dry) return 0;
+
+    TRY(launch_rrdb_input(in, in_u8, xin, B, 3, H, W, 1, 32, r.s));
+    const half_t* src = xin;
+    for (int i = 0; i < n.num_conv + 2; ++i) {
+        const sdmi_compact::Conv& c = n.convs[(size_t)i];
+        const bool last = i == n.num_conv + 1;
+        CompactP p{};
+        p.in = src; p.w = c.w; p.bias = c.b; p.slope = c.slope;
+        p.B = B; p.H = H; p.W = W; p.cin = i == 0 ? 32 : 64; p.lda = p.cin;
+        if (last) {                                   // the activations never see a high-resolution tensor
+            p.ep = COMPACT_EP_TAIL; p.r = n.scale; p.n_real = 3 * n.scale * n.scale;
+            p.base = in; p.base_u8 = in_u8; p.out = out; p.out_u8 = out_u8;
+        } else {
+            p.ep = COMPACT_EP_PRELU; p.n_real = 64; p.out = x[i & 1]; p.ldo = 64;
+            src = x[i & 1];
+        }
+        TRY(launch_compact_conv(p, r.s));
+    }
+    return 0;
 }
-}  // namespace
 
 int64_t compact_scratch_bytes(const sdmi_compact* n, int B, int H, int W) {
     if (!n || B <= 0 || H <= 0 || W <= 0) return 0;
-    Arena ar;
-    ar.dry = true;
-    compact_take(ar, (size_t)B * H * W);
-    return (int64_t)ar.high;
+    return pass_scratch_bytes(n->e, [&](Run& r) { return compact_pass(r, *n, nullptr, 0, B, H, W, nullptr, 0); });
 }
 
 // in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
@@ -2222,31 +2281,7 @@ int compact_run(sdmi_compact* n, const void* in, int in_u8, int B, int H, int W,
     SDMI_REQUIRE(B > 0 && H > 0 && W > 0, "empty image");
     SDMI_REQUIRE((long long)B * H * W * n->scale * n->scale < (1ll << 31) - 256, "image too large: the output must stay below 2^31 pixels");
     SDMI_CHECK_HIP(hipSetDevice(e->device));
-    const size_t M = (size_t)B * H * W;
-    e->arena.dry = true; e->arena.high = 0;
-    compact_take(e->arena, M);
-    e->arena.dry = false;
-    TRY(ensure_arena(e, e->arena.high, s));
-    const CompactBufs b = compact_take(e->arena, M);
-
-    TRY(launch_rrdb_input(in, in_u8, b.in, B, 3, H, W, 1, 32, s));
-    const half_t* src = b.in;
-    for (int i = 0; i < n->num_conv + 2; ++i) {
-        const sdmi_compact::Conv& c = n->convs[(size_t)i];
-        const bool last = i == n->num_conv + 1;
-        CompactP p{};
-        p.in = src; p.w = c.w; p.bias = c.b; p.slope = c.slope;
-        p.B = B; p.H = H; p.W = W; p.cin = i == 0 ? 32 : 64; p.lda = p.cin;
-        if (last) {                                   // the activations never see a high-resolution tensor
-            p.ep = COMPACT_EP_TAIL; p.r = n->scale; p.n_real = 3 * n->scale * n->scale;
-            p.base = in; p.base_u8 = in_u8; p.out = out; p.out_u8 = out_u8;
-        } else {
-            p.ep = COMPACT_EP_PRELU; p.n_real = 64; p.out = b.x[i & 1]; p.ldo = 64;
-            src = b.x[i & 1];
-        }
-        TRY(launch_compact_conv(p, s));
-    }
-    return 0;
+    return run_pass(e, s, [&](Run& r) { return compact_pass(r, *n, in, in_u8, B, H, W, out, out_u8); });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2349,12 +2384,6 @@ static int swin_net_build(sdmi_swinir* net, const float* blob, int64_t blob_floa
     const int Cp = rup(C, 64), hid_pad = rup(Hd, 64), ldq = rup(96 * heads, 64), lda = rup(32 * heads, 64);
     net->C = C; net->Cp = Cp; net->D = D; net->ldq = ldq; net->lda = lda; net->hid_pad = hid_pad;
     const float* src = blob;
-    auto upload = [&](const void* host, size_t bytes, void** dev) -> int {
-        SDMI_CHECK_HIP(hipMalloc(dev, std::max<size_t>(bytes, 256)));
-        net->owned.push_back(*dev);
-        SDMI_CHECK_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
-        return 0;
-    };
     // one conv / linear: OIHW weight then bias off the blob -> [n_pad][taps][cin_pad] fp16 + [n_pad] fp32, output row o at row_of(o),
     // input channel i at col_of(i), everything else zero; bias_add: a constant per REAL output row (the output mean on conv_last)
     auto ident = [](int v) { return v; };
@@ -2370,16 +2399,10 @@ static int swin_net_build(sdmi_swinir* net, const float* blob, int64_t blob_floa
         for (int o = 0; o < O; ++o) b[(size_t)row_of(o)] = src[o] + (bias_add ? bias_add[o] : 0.f);
         src += O;
         c->cin = I; c->cin_pad = cin_pad; c->cout = O; c->n_pad = n_pad; c->taps = taps;
-        TRY(upload(w.data(), w.size() * sizeof(half_t), (void**)&c->w));
-        return upload(b.data(), b.size() * sizeof(float), (void**)&c->b);
+        TRY(net_upload(net, w.data(), w.size() * sizeof(half_t), (void**)&c->w));
+        return net_upload(net, b.data(), b.size() * sizeof(float), (void**)&c->b);
     };
-    auto norm = [&](NormW* n) -> int {
-        n->c = C;
-        TRY(upload(src, (size_t)C * sizeof(float), (void**)&n->g));
-        TRY(upload(src + C, (size_t)C * sizeof(float), (void**)&n->b));
-        src += 2 * C;
-        return 0;
-    };
+    auto norm = [&](NormW* n) { return net_norm(net, src, C, n); };
     // the conv that closes a layer / the trunk: 1conv, or 3conv with C / 4 padded to 64
     auto resi = [&](ConvW* c) -> int {
         if (!cfg->resi_3conv) return pack(&c[0], C, C, 9, Cp, Cp, ident, ident);
@@ -2393,18 +2416,14 @@ static int swin_net_build(sdmi_swinir* net, const float* blob, int64_t blob_floa
     if (v2) TRY(pack(&net->pe_proj, C, C, 1, Cp, Cp, ident, ident));
     TRY(norm(&net->pe_norm));
     net->layers.resize((size_t)cfg->num_layers);
-    std::vector<float> bias((size_t)heads * 4096);
     for (int i = 0; i < cfg->num_layers; ++i) {
         sdmi_swinir::Layer& L = net->layers[(size_t)i];
         L.blocks.resize((size_t)cfg->depths[i]);
         for (sdmi_swinir::Block& bk : L.blocks) {
-            auto table = [&]() -> int {                                // bias[h][a][b] = table[(ya - yb + 7) * 15 + (xa - xb + 7)][h]
-                for (int h = 0; h < heads; ++h)
-                    for (int a = 0; a < 64; ++a)
-                        for (int b = 0; b < 64; ++b)
-                            bias[((size_t)h * 64 + a) * 64 + b] = src[(size_t)(((a >> 3) - (b >> 3) + 7) * 15 + ((a & 7) - (b & 7) + 7)) * heads + h];
+            auto table = [&]() -> int {                                // [225][heads]
+                const float* t = src;
                 src += 225 * heads;
-                return upload(bias.data(), bias.size() * sizeof(float), (void**)&bk.bias);
+                return net_rel_bias(net, t, heads, (size_t)heads, 1, &bk.bias);
             };
             auto qkv = [&]() { return pack(&bk.qkv, 3 * C, C, 1, ldq, Cp, [&](int o) { return (o / C) * heads * 32 + slot(o % C); }, ident); };
             if (!v2) {
@@ -2416,7 +2435,7 @@ static int swin_net_build(sdmi_swinir* net, const float* blob, int64_t blob_floa
             } else {
                 TRY(qkv());
                 TRY(table());
-                TRY(upload(src, (size_t)heads * sizeof(float), (void**)&bk.head_scale));
+                TRY(net_upload(net, src, (size_t)heads * sizeof(float), (void**)&bk.head_scale));
                 src += heads;
                 TRY(pack(&bk.proj, C, C, 1, Cp, lda, ident, slot));
                 TRY(norm(&bk.n1));
@@ -2607,31 +2626,6 @@ static int swinir_pass(Run& r, const sdmi_swinir& n, const void* in, int in_u8, 
     return launch_swin_output(full, out, out_u8, B, H * sc, W * sc, Hp * sc, Wp * sc, r.s);
 }
 
-// The networks that are one pass over the arena (swinir_pass, scunet_pass), pass(Run&): what a dry walk takes from a private arena ...
-template <class Pass>
-static int64_t pass_scratch_bytes(sdmi_engine* e, Pass pass) {
-    Arena ar;
-    ar.dry = true;
-    Run dry(e, nullptr, true, &ar);
-    if (pass(dry) != 0) return 0;
-    return (int64_t)ar.high;
-}
-// ... and the run: a dry walk sizes the engine's arena, then the real one
-template <class Pass>
-static int run_pass(sdmi_engine* e, hipStream_t s, Pass pass) {
-    const bool tiling = e->tiling;                            // p.tiling belongs to the diffusion model's convs, not to an upscaler's
-    e->tiling = false;
-    struct Restore { sdmi_engine* e; bool v; ~Restore() { e->tiling = v; } } restore{e, tiling};
-    Run dry{e, s, true};
-    e->arena.dry = true; e->arena.high = 0;
-    const int rc = pass(dry);
-    e->arena.dry = false;
-    TRY(rc);
-    TRY(ensure_arena(e, e->arena.high, s));
-    Run run{e, s, false};
-    return pass(run);
-}
-
 static bool swinir_size_ok(const sdmi_swinir& n, int B, int H, int W) {
     if (B <= 0 || H < 8 || W < 8) return false;
     const long long M = (long long)B * rup(H, 8) * rup(W, 8);
@@ -2691,12 +2685,6 @@ int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const 
     std::unique_ptr<sdmi_scunet> net(new sdmi_scunet);
     net->e = e; net->cfg = *cfg;
     const float* src = blob;
-    auto upload = [&](const void* host, size_t bytes, void** dev) -> int {
-        SDMI_CHECK_HIP(hipMalloc(dev, std::max<size_t>(bytes, 256)));
-        net->owned.push_back(*dev);
-        SDMI_CHECK_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
-        return 0;
-    };
     // one conv / linear off the blob -> [O][taps][I] fp16 (+ [O] fp32 bias).  at(o, i, t): where the checkpoint keeps that weight
     auto pack = [&](ConvW* c, int O, int I, int taps, bool bias, const std::function<size_t(int, int, int)>& at) -> int {
         std::vector<half_t> w((size_t)O * taps * I);
@@ -2705,20 +2693,13 @@ int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const 
                 for (int i = 0; i < I; ++i) w[((size_t)o * taps + t) * I + i] = (half_t)src[at(o, i, t)];
         src += (size_t)O * I * taps;
         c->cin = c->cin_pad = I; c->cout = c->n_pad = O; c->taps = taps;
-        TRY(upload(w.data(), w.size() * sizeof(half_t), (void**)&c->w));
+        TRY(net_upload(net.get(), w.data(), w.size() * sizeof(half_t), (void**)&c->w));
         if (!bias) return 0;
-        TRY(upload(src, (size_t)O * sizeof(float), (void**)&c->b));
+        TRY(net_upload(net.get(), src, (size_t)O * sizeof(float), (void**)&c->b));
         src += O;
         return 0;
     };
     auto oihw = [](int I, int taps) { return [=](int o, int i, int t) { return ((size_t)o * I + i) * taps + t; }; };
-    auto norm = [&](NormW* n, int C) -> int {
-        n->c = C;
-        TRY(upload(src, (size_t)C * sizeof(float), (void**)&n->g));
-        TRY(upload(src + C, (size_t)C * sizeof(float), (void**)&n->b));
-        src += 2 * C;
-        return 0;
-    };
     // m_head / m_tail on rrdb_conv: 3 input channels in a 32-wide row, 3 output channels of a 32-wide tile
     {
         std::vector<half_t> w((size_t)64 * 9 * 32, (half_t)0.f);
@@ -2727,9 +2708,8 @@ int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const 
                 for (int t = 0; t < 9; ++t) w[((size_t)o * 9 + t) * 32 + i] = (half_t)src[((size_t)o * 3 + i) * 9 + t];
         src += 64 * 3 * 9;
         net->head.cin = 3; net->head.cin_pad = 32; net->head.cout = net->head.n_pad = 64; net->head.taps = 9;
-        TRY(upload(w.data(), w.size() * sizeof(half_t), (void**)&net->head.w));
+        TRY(net_upload(net.get(), w.data(), w.size() * sizeof(half_t), (void**)&net->head.w));
     }
-    std::vector<float> bias;
     for (int st = 0; st < 7; ++st) {
         const int t = scunet_stage_c(st), D = 2 * t, heads = t / 32;
         if (st > 3)     // ConvTranspose2d(2 D, D, 2, 2) [2 D][D][2][2]: GEMM row (dy * 2 + dx) * D + o, column i
@@ -2739,13 +2719,8 @@ int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const 
             bk.c = t;
             const float* ln1 = src;
             src += 2 * t;
-            bias.resize((size_t)heads * 4096);
-            for (int h = 0; h < heads; ++h)                 // bias[h][a][b] = params[h][ya - yb + 7][xa - xb + 7]
-                for (int a = 0; a < 64; ++a)
-                    for (int b = 0; b < 64; ++b)
-                        bias[((size_t)h * 64 + a) * 64 + b] = src[(size_t)h * 225 + ((a >> 3) - (b >> 3) + 7) * 15 + ((a & 7) - (b & 7) + 7)];
+            TRY(net_rel_bias(net.get(), src, heads, 1, 225, &bk.bias));      // relative_position_params [heads][15][15]
             src += 225 * heads;
-            TRY(upload(bias.data(), bias.size() * sizeof(float), (void**)&bk.bias));
             if (t <= 64) {
                 // the Block's tensors as the pack kernel wants them: fp16 matrices, fp32 vectors, all temporaries
                 std::vector<void*> tmp;
@@ -2776,9 +2751,8 @@ int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const 
                 rc = rc || up16(4 * t * t, &pp.w1) || up32(src, 4 * t, &pp.b1); src += 4 * t;
                 rc = rc || up16(4 * t * t, &pp.w2) || up32(src, t, &pp.b2); src += t;
                 if (!rc) {
-                    rc = hipMalloc(&bk.packs, scu_block_pack_bytes(t)) != hipSuccess;
+                    rc = net_upload(net.get(), nullptr, scu_block_pack_bytes(t), &bk.packs);
                     if (!rc) {
-                        net->owned.push_back(bk.packs);
                         pp.packs = bk.packs;
                         rc = launch_scu_block_pack(pp, t, nullptr) || hipDeviceSynchronize() != hipSuccess;
                     }
@@ -2786,12 +2760,10 @@ int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const 
                 for (void* d : tmp) (void)hipFree(d);
                 SDMI_REQUIRE(!rc, "packing a Block's weights failed");
             } else {
-                bk.n1.c = t;
-                TRY(upload(ln1, (size_t)t * sizeof(float), (void**)&bk.n1.g));
-                TRY(upload(ln1 + t, (size_t)t * sizeof(float), (void**)&bk.n1.b));
+                TRY(net_norm(net.get(), ln1, t, &bk.n1));
                 TRY(pack(&bk.qkv, 3 * t, t, 1, true, oihw(t, 1)));
                 TRY(pack(&bk.proj, t, t, 1, true, oihw(t, 1)));
-                TRY(norm(&bk.n2, t));
+                TRY(net_norm(net.get(), src, t, &bk.n2));
                 TRY(pack(&bk.fc1, 4 * t, t, 1, true, oihw(t, 1)));
                 TRY(pack(&bk.fc2, t, 4 * t, 1, true, oihw(4 * t, 1)));
             }
@@ -2810,7 +2782,7 @@ int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const 
                 for (int t = 0; t < 9; ++t) w[((size_t)o * 9 + t) * 64 + i] = (half_t)src[((size_t)o * 64 + i) * 9 + t];
         src += 3 * 64 * 9;
         net->tail.cin = net->tail.cin_pad = 64; net->tail.cout = 3; net->tail.n_pad = 32; net->tail.taps = 9;
-        TRY(upload(w.data(), w.size() * sizeof(half_t), (void**)&net->tail.w));
+        TRY(net_upload(net.get(), w.data(), w.size() * sizeof(half_t), (void**)&net->tail.w));
     }
     SDMI_REQUIRE(src - blob == blob_floats, "internal: blob walk does not end at its length");
     SDMI_CHECK_HIP(hipDeviceSynchronize());
@@ -2948,19 +2920,7 @@ int scunet_run(sdmi_scunet* n, const void* in, int in_u8, int B, int H, int W, v
 
 }  // namespace sdmi
 
-sdmi_scunet::~sdmi_scunet() {
-    for (void* p : owned) (void)hipFree(p);
-}
-
-sdmi_swinir::~sdmi_swinir() {
-    for (void* p : owned) (void)hipFree(p);
-}
-
-sdmi_compact::~sdmi_compact() {
-    for (void* p : owned) (void)hipFree(p);
-}
-
-sdmi_esrgan::~sdmi_esrgan() {
+sdmi_net::~sdmi_net() {
     for (void* p : owned) (void)hipFree(p);
 }
 

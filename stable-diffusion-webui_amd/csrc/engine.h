@@ -248,35 +248,37 @@ struct sdmi_engine {
     ~sdmi_engine();
 };
 
+// What every upscaler net is: the engine whose arena its runs take their activations from, and the device allocations (packed weights)
+// it owns.  A net is immutable after its sdmi_*_create.
+struct sdmi_net {
+    sdmi_engine* e = nullptr;
+    std::vector<void*> owned;
+    ~sdmi_net();
+};
+
 // RRDBNet upscaler (ESRGAN / Real-ESRGAN): packed weights of the rrdb_conv launches (rrdb.hip).  Activations come from the owning
 // engine's arena, like the VAE's; the net itself is immutable after sdmi_esrgan_create.
-struct sdmi_esrgan {
+struct sdmi_esrgan : sdmi_net {
     struct Conv { half_t* w = nullptr; float* b = nullptr; int cin = 0, nout = 0, n_real = 0; };
-    sdmi_engine* e = nullptr;
     int num_block = 0, in_ch = 0, scale = 0;
     int unshuffle = 1;                        // 4 / scale: pixel-unshuffle factor in front of conv_first (x2: 2, x1: 4)
     int cin0 = 0;                             // conv_first's input channels (3 / 12 / 48) padded to 32 / 32 / 64
     Conv first, body, up1, up2, hr, last;
     std::vector<Conv> rdb;                    // num_block x 3 x 5, in checkpoint order
-    std::vector<void*> owned;
-    ~sdmi_esrgan();
 };
 
 // Compact Real-ESRGAN upscaler (SRVGGNetCompact, 64 features, PReLU): packed weights of the compact_conv launches (compact.hip).
 // Activations come from the owning engine's arena; the net is immutable after sdmi_compact_create.
-struct sdmi_compact {
+struct sdmi_compact : sdmi_net {
     struct Conv { half_t* w = nullptr; float* b = nullptr; float* slope = nullptr; };
-    sdmi_engine* e = nullptr;
     int num_conv = 0, scale = 0;
     std::vector<Conv> convs;                  // num_conv + 2: first (3 -> 64), body, last (64 -> 3 scale^2; no PReLU after it)
-    std::vector<void*> owned;
-    ~sdmi_compact();
 };
 
 // SwinIR upscaler (nearest+conv upsampler): packed weights of the GEMM launches (linears and trunk convs, rows / columns padded to
 // multiples of 64, qkv / proj permuted into 32-wide head slots), the expanded relative-position bias of every block, and the 64-channel
 // tail as rrdb_conv weights.  Activations come from the owning engine's arena; the net is immutable after sdmi_swinir_create.
-struct sdmi_swinir {
+struct sdmi_swinir : sdmi_net {
     struct Block {
         sdmi::NormW n1, n2;
         sdmi::ConvW qkv, proj, fc1, fc2;
@@ -287,19 +289,16 @@ struct sdmi_swinir {
         std::vector<Block> blocks;
         sdmi::ConvW conv[3];                  // 1conv: conv[0]; 3conv: 3x3 (C -> C/4), 1x1, 3x3 (C/4 -> C)
     };
-    sdmi_engine* e = nullptr;
     sdmi_swinir_config cfg{};
     int C = 0, Cp = 0, D = 0, ldq = 0, lda = 0, hid_pad = 0;      // lda: row width of the attention output (32 heads rounded up to 64)
     sdmi::ConvW first, after[3], before, up1, up2, hr, last;
     sdmi::NormW pe_norm, norm;
     std::vector<Layer> layers;
-    std::vector<void*> owned;
     // Swin2SR (v2): Swin-V2 blocks — cosine attention, res-post-norm — in the same trunk; upsampler 0 nearest+conv (the tail above),
     // 1 pixelshuffle (before, ps[], last), 2 pixelshuffledirect (direct)
     int v2 = 0, upsampler = 0;
     sdmi::ConvW pe_proj;                      // patch_embed.proj: the 1x1 conv in front of patch_embed.norm
     sdmi::ConvW ps[2], direct;                // ps: 64 -> f*f*64, output channels in (i, j, c) order; direct: C -> 3 scale^2 (padded to 64)
-    ~sdmi_swinir();
 };
 
 // Swin2SR upscaler: SwinIR's trunk and buffers with v2 set (engine.cpp swinir_pass runs both)
@@ -311,7 +310,7 @@ struct sdmi_swin2sr : sdmi_swinir {
 // GEMM (128 / 256) weights, and the transformer Block either as one scu_block pack (trans_dim 32 / 64) or as the GEMM weights of the
 // swin_layernorm + conv_gemm + swin_window_attn route (128 / 256).  Activations come from the owning engine's arena; the net is immutable
 // after sdmi_scunet_create.
-struct sdmi_scunet {
+struct sdmi_scunet : sdmi_net {
     struct Block {
         int c = 0;                            // conv_dim = trans_dim
         sdmi::ConvW c11, c12, cb0, cb2;
@@ -320,10 +319,7 @@ struct sdmi_scunet {
         sdmi::NormW n1, n2;                   // c >= 128
         sdmi::ConvW qkv, proj, fc1, fc2;
     };
-    sdmi_engine* e = nullptr;
     sdmi_scunet_config cfg{};
     sdmi::ConvW head, tail, down[3], up[3];   // down[l]: level l -> l + 1 (K = 4 Cin); up[l]: level l + 1 -> l (N = 4 Cout)
     std::vector<Block> stage[7];              // m_down1, m_down2, m_down3, m_body, m_up3, m_up2, m_up1
-    std::vector<void*> owned;
-    ~sdmi_scunet();
 };

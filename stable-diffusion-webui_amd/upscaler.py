@@ -122,16 +122,24 @@ def _old_arch_to_new(sd):
     return out
 
 
+def _as_f32(t):
+    return np.asarray(t.detach().float().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32).ravel()
+
+
+def _unwrap_state_dict(sd):
+    for wrap in ("params_ema", "params"):
+        if wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+            break
+    return {k: v for k, v in sd.items() if hasattr(v, "shape")}
+
+
 def parse_esrgan_state_dict(sd):
     """Checkpoint state dict -> (blob, num_block, in_ch, scale): the engine's weight blob (fp32, every conv's OIHW weight then its bias,
     in checkpoint order — sdmi_esrgan_create), the number of RRDBs read from the keys (23, or 6 for the anime model) and the scale read
     from conv_first's input channels (3 -> x4, 12 -> x2, 48 -> x1: pixel-unshuffle in front).  Host only.  Raises ValueError on anything
     that is not a 64-feature / 32-growth RRDBNet."""
-    for wrap in ("params_ema", "params"):
-        if wrap in sd and isinstance(sd[wrap], dict):
-            sd = sd[wrap]
-            break
-    sd = {k: v for k, v in sd.items() if hasattr(v, "shape")}
+    sd = _unwrap_state_dict(sd)
     if "model.0.weight" in sd:
         sd = _old_arch_to_new(sd)
     if "conv_first.weight" not in sd:
@@ -161,21 +169,8 @@ def parse_esrgan_state_dict(sd):
         w, b = sd[n + ".weight"], sd[n + ".bias"]
         if tuple(w.shape) != (*want, 3, 3) or tuple(b.shape) != (want[0],):
             raise ValueError(f"RRDBNet {n}: weight {tuple(w.shape)}, expected {(*want, 3, 3)}")
-        parts += [np.asarray(w.detach().float().cpu().numpy() if hasattr(w, "detach") else w, dtype=np.float32).ravel(),
-                  np.asarray(b.detach().float().cpu().numpy() if hasattr(b, "detach") else b, dtype=np.float32).ravel()]
+        parts += [_as_f32(w), _as_f32(b)]
     return np.ascontiguousarray(np.concatenate(parts)), num_block, in_ch, scale
-
-
-def _as_f32(t):
-    return np.asarray(t.detach().float().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32).ravel()
-
-
-def _unwrap_state_dict(sd):
-    for wrap in ("params_ema", "params"):
-        if wrap in sd and isinstance(sd[wrap], dict):
-            sd = sd[wrap]
-            break
-    return {k: v for k, v in sd.items() if hasattr(v, "shape")}
 
 
 def parse_compact_state_dict(sd):
@@ -221,6 +216,59 @@ def parse_compact_state_dict(sd):
 SWINIR_MARK = "layers.0.residual_group.blocks.0.attn.qkv.weight"
 
 
+# What the SwinIR and the Swin2SR parser share (`family`: the name their messages open with)
+def _swin_tensor(sd, family, name, shape=None):
+    """sd[name] as flat fp32, of this shape where one is given — or say what is wrong."""
+    t = sd.get(name)
+    if t is None or (shape is not None and tuple(t.shape) != shape):
+        raise ValueError(f"{family} {name}: {None if t is None else tuple(t.shape)}, expected {shape}")
+    return _as_f32(t)
+
+
+def _swin_wb(sd, family, name, shape):
+    """[weight, bias] of the layer `name` as flat fp32, the weight of this shape — or say what is wrong."""
+    w, b = sd.get(name + ".weight"), sd.get(name + ".bias")
+    if w is None or b is None:
+        raise ValueError(f"{family} checkpoint lacks {name}.{'weight' if w is None else 'bias'}")
+    if tuple(w.shape) != shape or tuple(b.shape) != (shape[0],):
+        raise ValueError(f"{family} {name}: weight {tuple(w.shape)}, expected {shape}")
+    return [_as_f32(w), _as_f32(b)]
+
+
+def _swin_depths(sd, family):
+    """The blocks of every layer, counted from the keys."""
+    layers = sorted({int(m.group(1)) for k in sd for m in [re.match(r"layers\.(\d+)\.residual_group\.blocks\.0\.attn\.qkv\.weight$", k)] if m})
+    if not layers or layers != list(range(len(layers))) or len(layers) > 16:
+        raise ValueError(f"{family} layers are not 0..n-1 with 1 <= n <= 16: {layers}")
+    depths = []
+    for i in layers:
+        blocks = sorted({int(m.group(1)) for k in sd for m in [re.match(rf"layers\.{i}\.residual_group\.blocks\.(\d+)\.attn\.qkv\.weight$", k)] if m})
+        if blocks != list(range(len(blocks))):
+            raise ValueError(f"{family} layers.{i}: blocks are not 0..n-1: {blocks}")
+        depths.append(len(blocks))
+    return depths
+
+
+def _swin_trunk(sd, family, c, heads):
+    """-> (mlp_hidden, resi_3conv, resi): the trunk facts read off the first block and the first layer's closing conv, refused where the
+    engine's kernels are not built for them; resi(stem) lists the (name, weight shape) of a closing conv (1conv | 3conv)."""
+    if c % heads or c // heads > 32:
+        raise ValueError(f"{family} head_dim = {c}/{heads} = {c / heads:g}: the engine's attention kernel is built for head_dim <= 32")
+    b0 = "layers.0.residual_group.blocks.0."
+    if b0 + "mlp.fc1.weight" not in sd:
+        raise ValueError(f"{family} checkpoint lacks {b0}mlp.fc1.weight")
+    hidden = int(sd[b0 + "mlp.fc1.weight"].shape[0])
+    resi3 = "layers.0.conv.0.weight" in sd
+    if not resi3 and "layers.0.conv.weight" not in sd:
+        raise ValueError(f"{family} checkpoint lacks layers.0.conv (.weight for 1conv, .0 / .2 / .4 for 3conv)")
+    if resi3 and (c % 4 or c // 4 > 64):
+        raise ValueError(f"{family} 3conv with embed_dim {c}: the engine packs embed_dim / 4 <= 64 channels")
+    q = c // 4
+    resi = (lambda stem: [(stem + ".0", (q, c, 3, 3)), (stem + ".2", (q, q, 1, 1)), (stem + ".4", (c, q, 3, 3))]) if resi3 \
+        else (lambda stem: [(stem, (c, c, 3, 3))])
+    return hidden, resi3, resi
+
+
 def parse_swinir_state_dict(sd):
     """Checkpoint state dict of a SwinIR network with the nearest+conv upsampler (the real-world SR models: SwinIR-L x4 GAN, the M
     models x4 / x2) -> (blob, config): the engine's weight blob (fp32, every tensor flattened in the order include/sdmi.h documents at
@@ -241,15 +289,7 @@ def parse_swinir_state_dict(sd):
     c, in_ch = int(sd["conv_first.weight"].shape[0]), int(sd["conv_first.weight"].shape[1])
     if in_ch != 3 or tuple(sd["conv_first.weight"].shape[2:]) != (3, 3):
         raise ValueError(f"SwinIR conv_first takes {in_ch} input channels: expected 3")
-    layers = sorted({int(m.group(1)) for k in sd for m in [re.match(r"layers\.(\d+)\.residual_group\.blocks\.0\.attn\.qkv\.weight$", k)] if m})
-    if layers != list(range(len(layers))) or len(layers) > 16:
-        raise ValueError(f"SwinIR layers are not 0..n-1 with n <= 16: {layers}")
-    depths = []
-    for i in layers:
-        blocks = sorted({int(m.group(1)) for k in sd for m in [re.match(rf"layers\.{i}\.residual_group\.blocks\.(\d+)\.attn\.qkv\.weight$", k)] if m})
-        if blocks != list(range(len(blocks))):
-            raise ValueError(f"SwinIR layers.{i}: blocks are not 0..n-1: {blocks}")
-        depths.append(len(blocks))
+    depths = _swin_depths(sd, "SwinIR")
     b0 = "layers.0.residual_group.blocks.0."
     table = sd.get(b0 + "attn.relative_position_bias_table")
     if table is None or len(table.shape) != 2:
@@ -258,24 +298,12 @@ def parse_swinir_state_dict(sd):
     if int(table.shape[0]) != 225:
         w = (int(round(int(table.shape[0]) ** 0.5)) + 1) // 2
         raise ValueError(f"SwinIR window_size {w} (a {int(table.shape[0])}-row bias table): the engine's attention kernel is built for 8 (225 rows)")
-    if c % heads or c // heads > 32:
-        raise ValueError(f"SwinIR head_dim = {c}/{heads} = {c / heads:g}: the engine's attention kernel is built for head_dim <= 32")
-    if b0 + "mlp.fc1.weight" not in sd:
-        raise ValueError(f"SwinIR checkpoint lacks {b0}mlp.fc1.weight")
-    hidden = int(sd[b0 + "mlp.fc1.weight"].shape[0])
-    resi3 = "layers.0.conv.0.weight" in sd
-    if not resi3 and "layers.0.conv.weight" not in sd:
-        raise ValueError("SwinIR checkpoint lacks layers.0.conv (.weight for 1conv, .0 / .2 / .4 for 3conv)")
-    if resi3 and (c % 4 or c // 4 > 64):
-        raise ValueError(f"SwinIR 3conv with embed_dim {c}: the engine packs embed_dim / 4 <= 64 channels")
+    hidden, resi3, resi = _swin_trunk(sd, "SwinIR", c, heads)
     if int(sd["conv_before_upsample.0.weight"].shape[0]) != 64:
         raise ValueError(f"SwinIR num_feat = {int(sd['conv_before_upsample.0.weight'].shape[0])}: the engine's tail kernel is built for 64")
     if int(sd["conv_last.weight"].shape[0]) != 3:
         raise ValueError(f"SwinIR conv_last writes {int(sd['conv_last.weight'].shape[0])} channels: expected 3")
     scale = 4 if "conv_up2.weight" in sd else 2
-    q = c // 4
-    resi = (lambda stem: [(stem + ".0", (q, c, 3, 3)), (stem + ".2", (q, q, 1, 1)), (stem + ".4", (c, q, 3, 3))]) if resi3 \
-        else (lambda stem: [(stem, (c, c, 3, 3))])
     want = [("conv_first", (c, 3, 3, 3)), ("patch_embed.norm", (c,))]
     for i, depth in enumerate(depths):
         for j in range(depth):
@@ -288,17 +316,9 @@ def parse_swinir_state_dict(sd):
     parts = []
     for name, shape in want:
         if name.endswith("relative_position_bias_table"):
-            t = sd.get(name)
-            if t is None or tuple(t.shape) != shape:
-                raise ValueError(f"SwinIR {name}: {None if t is None else tuple(t.shape)}, expected {shape}")
-            parts.append(_as_f32(t))
-            continue
-        w, b = sd.get(name + ".weight"), sd.get(name + ".bias")
-        if w is None or b is None:
-            raise ValueError(f"SwinIR checkpoint lacks {name}.{'weight' if w is None else 'bias'}")
-        if tuple(w.shape) != shape or tuple(b.shape) != (shape[0],):
-            raise ValueError(f"SwinIR {name}: weight {tuple(w.shape)}, expected {shape}")
-        parts += [_as_f32(w), _as_f32(b)]
+            parts.append(_swin_tensor(sd, "SwinIR", name, shape))
+        else:
+            parts += _swin_wb(sd, "SwinIR", name, shape)
     config = dict(embed_dim=c, depths=tuple(depths), num_heads=heads, mlp_hidden=hidden, resi_3conv=int(resi3), scale=scale)
     return np.ascontiguousarray(np.concatenate(parts)), config
 
@@ -357,15 +377,7 @@ def parse_swin2sr_state_dict(sd):
     c, in_ch = int(sd["conv_first.weight"].shape[0]), int(sd["conv_first.weight"].shape[1])
     if in_ch != 3 or tuple(sd["conv_first.weight"].shape[2:]) != (3, 3):
         raise ValueError(f"Swin2SR conv_first takes {in_ch} input channels: expected 3")
-    layers = sorted({int(m.group(1)) for k in sd for m in [re.match(r"layers\.(\d+)\.residual_group\.blocks\.0\.attn\.qkv\.weight$", k)] if m})
-    if not layers or layers != list(range(len(layers))) or len(layers) > 16:
-        raise ValueError(f"Swin2SR layers are not 0..n-1 with 1 <= n <= 16: {layers}")
-    depths = []
-    for i in layers:
-        blocks = sorted({int(m.group(1)) for k in sd for m in [re.match(rf"layers\.{i}\.residual_group\.blocks\.(\d+)\.attn\.qkv\.weight$", k)] if m})
-        if blocks != list(range(len(blocks))):
-            raise ValueError(f"Swin2SR layers.{i}: blocks are not 0..n-1: {blocks}")
-        depths.append(len(blocks))
+    depths = _swin_depths(sd, "Swin2SR")
     heads = int(sd[SWIN2SR_MARK].shape[0])
     for k, v in sd.items():                                  # the cpb grid is computed, not stored: the window shows in the buffers
         side = None
@@ -377,17 +389,7 @@ def parse_swin2sr_state_dict(sd):
             side = (int(v.shape[1]) + 1) // 2
         if side is not None:
             raise ValueError(f"Swin2SR window_size {side} ({k} {tuple(v.shape)}): the engine's attention kernel is built for 8")
-    if c % heads or c // heads > 32:
-        raise ValueError(f"Swin2SR head_dim = {c}/{heads} = {c / heads:g}: the engine's attention kernel is built for head_dim <= 32")
-    b0 = "layers.0.residual_group.blocks.0."
-    if b0 + "mlp.fc1.weight" not in sd:
-        raise ValueError(f"Swin2SR checkpoint lacks {b0}mlp.fc1.weight")
-    hidden = int(sd[b0 + "mlp.fc1.weight"].shape[0])
-    resi3 = "layers.0.conv.0.weight" in sd
-    if not resi3 and "layers.0.conv.weight" not in sd:
-        raise ValueError("Swin2SR checkpoint lacks layers.0.conv (.weight for 1conv, .0 / .2 / .4 for 3conv)")
-    if resi3 and (c % 4 or c // 4 > 64):
-        raise ValueError(f"Swin2SR 3conv with embed_dim {c}: the engine packs embed_dim / 4 <= 64 channels")
+    hidden, resi3, resi = _swin_trunk(sd, "Swin2SR", c, heads)
     if upsampler != 2 and int(sd["conv_before_upsample.0.weight"].shape[0]) != 64:
         raise ValueError(f"Swin2SR num_feat = {int(sd['conv_before_upsample.0.weight'].shape[0])}: the engine's tail kernels are built for 64")
     if upsampler == 0:
@@ -411,24 +413,13 @@ def parse_swin2sr_state_dict(sd):
             raise ValueError(f"Swin2SR pixelshuffledirect with upsample.0 writing {n0} channels: the engine runs scales 2, 3 and 4 "
                              f"(12, 27, 48 channels)")
         tail = [("upsample.0", (n0, c, 3, 3))]
-    q = c // 4
-    resi = (lambda stem: [(stem + ".0", (q, c, 3, 3)), (stem + ".2", (q, q, 1, 1)), (stem + ".4", (c, q, 3, 3))]) if resi3 \
-        else (lambda stem: [(stem, (c, c, 3, 3))])
     parts = []
 
     def wb(name, shape):
-        w, b = sd.get(name + ".weight"), sd.get(name + ".bias")
-        if w is None or b is None:
-            raise ValueError(f"Swin2SR checkpoint lacks {name}.{'weight' if w is None else 'bias'}")
-        if tuple(w.shape) != shape or tuple(b.shape) != (shape[0],):
-            raise ValueError(f"Swin2SR {name}: weight {tuple(w.shape)}, expected {shape}")
-        parts.extend([_as_f32(w), _as_f32(b)])
+        parts.extend(_swin_wb(sd, "Swin2SR", name, shape))
 
     def tensor(name, shape=None):
-        t = sd.get(name)
-        if t is None or (shape is not None and tuple(t.shape) != shape):
-            raise ValueError(f"Swin2SR {name}: {None if t is None else tuple(t.shape)}, expected {shape}")
-        return _as_f32(t)
+        return _swin_tensor(sd, "Swin2SR", name, shape)
 
     def proj_of(stem):
         """PatchEmbed.proj of network_swin2sr.py, a 1x1 conv C -> C, as ([C, C], [C]) float64; the identity where a checkpoint has none."""
@@ -595,150 +586,39 @@ class EsrganInputTooLarge(ValueError):
     """An image whose intermediates the engine's arena cannot hold (EsrganNet.check_fits)."""
 
 
-class EsrganNet:
-    """One RRDBNet resident on an engine (sdmi_esrgan_*)."""
-
-    def __init__(self, state_dict, device=0, engine=None):
-        from . import _lib
-        from .engine import Engine
-        blob, self.num_block, self.in_ch, self.scale = parse_esrgan_state_dict(state_dict)
-        self.device = int(device)
-        self.engine = engine or Engine(self.device)
-        self.handle = _lib.lib.sdmi_esrgan_create(self.engine.handle, blob.ctypes.data, blob.size, self.num_block, self.in_ch, self.scale)
-        if not self.handle:
-            raise _lib.SdmiError("sdmi_esrgan_create failed: " + _lib.last_error())
-
-    def close(self):
-        if getattr(self, "handle", None):
-            from . import _lib
-            _lib.lib.sdmi_esrgan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def scratch_bytes(self, b, h, w):
-        """Arena bytes of one run, from the engine's own layout (sdmi_esrgan_scratch_bytes)."""
-        from . import _lib
-        return int(_lib.lib.sdmi_esrgan_scratch_bytes(self.handle, b, h, w))
-
-    def check_fits(self, b, h, w):
-        """Refuse an input whose intermediates (the 192-wide dense buffers, the (H s) x (W s) x 64 up-conv tensors) the arena cannot hold."""
-        unshuffle = 4 // self.scale
-        pixels = b * (h // unshuffle) * (w // unshuffle)
-        need = self.scratch_bytes(b, h, w)
-        # the arena the engine already holds is replaced, not added to, when it has to grow: it counts as available
-        limit = arena_limit_bytes(self.device) + self.engine.arena_bytes()
-        if pixels * 16 >= (1 << 31) - 256 or need > limit:
-            raise EsrganInputTooLarge(f"image {w}x{h} (batch {b}) is too large for the x{self.scale} upscaler: its intermediates need "
-                             f"{need / 2 ** 30:.1f} GiB of engine arena, {limit / 2 ** 30:.1f} GiB are available")
-
-    def run(self, x, out_u8=False):
-        """x: uint8 [B,H,W,3] (RGB; divided by 255 on the way in) or fp32 [B,3,H,W] in [0, 1], on the engine's device ->
-        fp32 [B,3,H s,W s], or with out_u8 uint8 [B,H s,W s,3] (clamp, x255, round half to even).  H, W: multiples of 4 / scale."""
-        import torch
-        from . import _lib
-        in_u8 = x.dtype == torch.uint8
-        x = x.contiguous() if in_u8 else x.float().contiguous()
-        b, h, w = (x.shape[0], x.shape[1], x.shape[2]) if in_u8 else (x.shape[0], x.shape[2], x.shape[3])
-        assert x.shape[3 if in_u8 else 1] == 3
-        self.check_fits(b, h, w)
-        s = self.scale
-        out = (torch.empty((b, h * s, w * s, 3), dtype=torch.uint8, device=x.device) if out_u8
-               else torch.empty((b, 3, h * s, w * s), dtype=torch.float32, device=x.device))
-        _lib.check(_lib.lib.sdmi_esrgan_run(self.handle, _lib.ptr(x), 1 if in_u8 else 0, b, h, w, _lib.ptr(out), 1 if out_u8 else 0,
-                                            _lib.stream_ptr()), "sdmi_esrgan_run")
-        return out
-
-
-class CompactNet:
-    """One compact Real-ESRGAN network (SRVGGNetCompact) resident on an engine (sdmi_compact_*): the twin of EsrganNet."""
-
-    def __init__(self, state_dict, device=0, engine=None):
-        from . import _lib
-        from .engine import Engine
-        blob, self.num_conv, self.scale = parse_compact_state_dict(state_dict)
-        self.device = int(device)
-        self.engine = engine or Engine(self.device)
-        self.handle = _lib.lib.sdmi_compact_create(self.engine.handle, blob.ctypes.data, blob.size, self.num_conv, self.scale)
-        if not self.handle:
-            raise _lib.SdmiError("sdmi_compact_create failed: " + _lib.last_error())
-
-    def close(self):
-        if getattr(self, "handle", None):
-            from . import _lib
-            _lib.lib.sdmi_compact_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def scratch_bytes(self, b, h, w):
-        """Arena bytes of one run, from the engine's own layout (sdmi_compact_scratch_bytes)."""
-        from . import _lib
-        return int(_lib.lib.sdmi_compact_scratch_bytes(self.handle, b, h, w))
-
-    def check_fits(self, b, h, w):
-        """Refuse an input whose intermediates (the padded input and two 64-wide buffers, all at the INPUT resolution) the arena cannot
-        hold, or whose output passes 2^31 pixels."""
-        need = self.scratch_bytes(b, h, w)
-        limit = arena_limit_bytes(self.device) + self.engine.arena_bytes()
-        if b * h * w * self.scale * self.scale >= (1 << 31) - 256 or need > limit:
-            raise EsrganInputTooLarge(f"image {w}x{h} (batch {b}) is too large for the x{self.scale} upscaler: its intermediates need "
-                                      f"{need / 2 ** 30:.1f} GiB of engine arena, {limit / 2 ** 30:.1f} GiB are available")
-
-    def run(self, x, out_u8=False):
-        """x: uint8 [B,H,W,3] (RGB; divided by 255 on the way in) or fp32 [B,3,H,W] in [0, 1], on the engine's device ->
-        fp32 [B,3,H s,W s], or with out_u8 uint8 [B,H s,W s,3] (clamp, x255, round half to even).  Any H, W."""
-        import torch
-        from . import _lib
-        in_u8 = x.dtype == torch.uint8
-        x = x.contiguous() if in_u8 else x.float().contiguous()
-        b, h, w = (x.shape[0], x.shape[1], x.shape[2]) if in_u8 else (x.shape[0], x.shape[2], x.shape[3])
-        assert x.shape[3 if in_u8 else 1] == 3
-        self.check_fits(b, h, w)
-        s = self.scale
-        out = (torch.empty((b, h * s, w * s, 3), dtype=torch.uint8, device=x.device) if out_u8
-               else torch.empty((b, 3, h * s, w * s), dtype=torch.float32, device=x.device))
-        _lib.check(_lib.lib.sdmi_compact_run(self.handle, _lib.ptr(x), 1 if in_u8 else 0, b, h, w, _lib.ptr(out), 1 if out_u8 else 0,
-                                             _lib.stream_ptr()), "sdmi_compact_run")
-        return out
-
-
-class SwinIRNet:
-    """One SwinIR network (nearest+conv upsampler) resident on an engine (sdmi_swinir_*): the twin of EsrganNet."""
-    _abi = "sdmi_swinir"                                     # the C entries of this class: <_abi>_destroy / _scratch_bytes / _run
+class _EngineNet:
+    """One upscaler network resident on an engine: the handle of the C entries <_abi>_create / _destroy / _scratch_bytes / _run and the
+    size checks in front of a run.  A family supplies its _abi, how a state dict becomes the arguments of its create entry (_parse),
+    and what differs in check_fits."""
+    _abi = None
+    _noun = None                                             # what check_fits calls the net; None: "the x{scale} upscaler"
+    _zero_need_is_a_refusal = False                          # scratch_bytes 0 = the engine refuses the size: a tensor passes 2^31 elements
+    unshuffle = 1                                            # H and W of an input must be multiples of this (the caller pads)
 
     def _fn(self, name):
         from . import _lib
         return getattr(_lib.lib, f"{self._abi}_{name}")
 
+    def _parse(self, state_dict):
+        """-> (blob, the arguments of the create entry behind the blob); sets scale and what else the family reads off the checkpoint."""
+        raise NotImplementedError
+
+    def _extra_elements(self, b, h, w):
+        """A tensor's element count that has to stay below 2^31 and that the arena bytes do not bound."""
+        return 0
+
     def __init__(self, state_dict, device=0, engine=None):
         from . import _lib
         from .engine import Engine
-        blob, self.config = parse_swinir_state_dict(state_dict)
-        self.scale = self.config["scale"]
+        blob, args = self._parse(state_dict)
         self.device = int(device)
         self.engine = engine or Engine(self.device)
-        cfg = _lib.SwinIRConfigC()
-        cfg.embed_dim, cfg.num_layers, cfg.num_heads = self.config["embed_dim"], len(self.config["depths"]), self.config["num_heads"]
-        cfg.mlp_hidden, cfg.resi_3conv, cfg.scale = self.config["mlp_hidden"], self.config["resi_3conv"], self.scale
-        for i, d in enumerate(self.config["depths"]):
-            cfg.depths[i] = d
-        import ctypes
-        self.handle = _lib.lib.sdmi_swinir_create(self.engine.handle, blob.ctypes.data, blob.size, ctypes.byref(cfg))
+        self.handle = self._fn("create")(self.engine.handle, blob.ctypes.data, blob.size, *args)
         if not self.handle:
-            raise _lib.SdmiError("sdmi_swinir_create failed: " + _lib.last_error())
+            raise _lib.SdmiError(f"{self._abi}_create failed: " + _lib.last_error())
 
     def close(self):
         if getattr(self, "handle", None):
-            from . import _lib
             self._fn("destroy")(self.handle)
             self.handle = None
 
@@ -749,27 +629,25 @@ class SwinIRNet:
             pass
 
     def scratch_bytes(self, b, h, w):
-        """Arena bytes of one run, from the engine's own layout (sdmi_swinir_scratch_bytes; 0 for a size the engine refuses)."""
-        from . import _lib
+        """Arena bytes of one run, from the engine's own layout (<_abi>_scratch_bytes; 0 for a size the engine refuses)."""
         return int(self._fn("scratch_bytes")(self.handle, b, h, w))
 
     def check_fits(self, b, h, w):
-        """Refuse an input whose intermediates (token tensors of the padded grid, the qkv and MLP rows, the (H s) x (W s) x 64 tail) the
-        arena cannot hold, or one of whose tensors passes 2^31 elements."""
-        if min(h, w) < 8:
-            raise ValueError(f"image {w}x{h}: SwinIR needs sides of at least 8 (one window)")
+        """Refuse an input whose intermediates the arena cannot hold, or one of whose tensors passes 2^31 elements."""
         need = self.scratch_bytes(b, h, w)
+        # the arena the engine already holds is replaced, not added to, when it has to grow: it counts as available
         limit = arena_limit_bytes(self.device) + self.engine.arena_bytes()
-        if need <= 0 or need > limit:
-            raise EsrganInputTooLarge(f"image {w}x{h} (batch {b}) is too large for the x{self.scale} upscaler: its intermediates need "
-                                      f"{need / 2 ** 30:.1f} GiB of engine arena, {limit / 2 ** 30:.1f} GiB are available"
-                                      if need > 0 else
-                                      f"image {w}x{h} (batch {b}) is too large for the x{self.scale} upscaler: a tensor passes 2^31 elements")
+        what = f"image {w}x{h} (batch {b}) is too large for {self._noun or f'the x{self.scale} upscaler'}"
+        if self._zero_need_is_a_refusal and need <= 0:
+            raise EsrganInputTooLarge(f"{what}: a tensor passes 2^31 elements")
+        if self._extra_elements(b, h, w) >= (1 << 31) - 256 or need > limit:
+            raise EsrganInputTooLarge(f"{what}: its intermediates need {need / 2 ** 30:.1f} GiB of engine arena, "
+                                      f"{limit / 2 ** 30:.1f} GiB are available")
 
     def run(self, x, out_u8=False):
         """x: uint8 [B,H,W,3] (RGB; divided by 255 on the way in) or fp32 [B,3,H,W] in [0, 1], on the engine's device ->
-        fp32 [B,3,H s,W s], or with out_u8 uint8 [B,H s,W s,3] (clamp, x255, round half to even).  Any H, W >= 8: the reflect padding to
-        multiples of the window and the crop happen on the device."""
+        fp32 [B,3,H s,W s], or with out_u8 uint8 [B,H s,W s,3] (clamp, x255, round half to even).  The sides a family takes are in its
+        docstring."""
         import torch
         from . import _lib
         in_u8 = x.dtype == torch.uint8
@@ -785,92 +663,92 @@ class SwinIRNet:
         return out
 
 
+class EsrganNet(_EngineNet):
+    """One RRDBNet resident on an engine (sdmi_esrgan_*).  H, W: multiples of 4 / scale (the x2 / x1 models pixel-unshuffle).  The arena
+    holds the 192-wide dense buffers and the (H s) x (W s) x 64 up-conv tensors."""
+    _abi = "sdmi_esrgan"
+    unshuffle = property(lambda self: 4 // self.scale)
+
+    def _parse(self, state_dict):
+        blob, self.num_block, self.in_ch, self.scale = parse_esrgan_state_dict(state_dict)
+        return blob, (self.num_block, self.in_ch, self.scale)
+
+    def _extra_elements(self, b, h, w):
+        return b * (h // self.unshuffle) * (w // self.unshuffle) * 16
+
+
+class CompactNet(_EngineNet):
+    """One compact Real-ESRGAN network (SRVGGNetCompact) resident on an engine (sdmi_compact_*).  Any H, W.  The arena holds the padded
+    input and two 64-wide buffers, all at the INPUT resolution; the output must stay below 2^31 pixels."""
+    _abi = "sdmi_compact"
+
+    def _parse(self, state_dict):
+        blob, self.num_conv, self.scale = parse_compact_state_dict(state_dict)
+        return blob, (self.num_conv, self.scale)
+
+    def _extra_elements(self, b, h, w):
+        return b * h * w * self.scale * self.scale
+
+
+def _swin_config_c(cfg, config):
+    """The fields sdmi_swinir_config and sdmi_swin2sr_config share, off a parser's config dict."""
+    import ctypes
+    cfg.embed_dim, cfg.num_layers, cfg.num_heads = config["embed_dim"], len(config["depths"]), config["num_heads"]
+    cfg.mlp_hidden, cfg.resi_3conv, cfg.scale = config["mlp_hidden"], config["resi_3conv"], config["scale"]
+    for i, d in enumerate(config["depths"]):
+        cfg.depths[i] = d
+    return ctypes.byref(cfg)
+
+
+class SwinIRNet(_EngineNet):
+    """One SwinIR network (nearest+conv upsampler) resident on an engine (sdmi_swinir_*).  Any H, W >= 8: the reflect padding to
+    multiples of the window and the crop happen on the device.  The arena holds the token tensors of the padded grid, the qkv and MLP
+    rows and the (H s) x (W s) x 64 tail."""
+    _abi = "sdmi_swinir"
+    _zero_need_is_a_refusal = True
+
+    def _parse(self, state_dict):
+        from . import _lib
+        blob, self.config = parse_swinir_state_dict(state_dict)
+        self.scale = self.config["scale"]
+        return blob, (_swin_config_c(_lib.SwinIRConfigC(), self.config),)
+
+    def check_fits(self, b, h, w):
+        if min(h, w) < 8:
+            raise ValueError(f"image {w}x{h}: SwinIR needs sides of at least 8 (one window)")
+        super().check_fits(b, h, w)
+
+
 class Swin2SRNet(SwinIRNet):
     """One Swin2SR network (nearest+conv, pixelshuffle or pixelshuffledirect upsampler) resident on an engine (sdmi_swin2sr_*): the
-    twin of SwinIRNet, whose size checks and run() it shares."""
+    twin of SwinIRNet, whose size checks it shares."""
     _abi = "sdmi_swin2sr"
 
-    def __init__(self, state_dict, device=0, engine=None):
+    def _parse(self, state_dict):
         from . import _lib
-        from .engine import Engine
         blob, self.config = parse_swin2sr_state_dict(state_dict)
         self.scale = self.config["scale"]
-        self.device = int(device)
-        self.engine = engine or Engine(self.device)
         cfg = _lib.Swin2SRConfigC()
-        cfg.embed_dim, cfg.num_layers, cfg.num_heads = self.config["embed_dim"], len(self.config["depths"]), self.config["num_heads"]
-        cfg.mlp_hidden, cfg.resi_3conv, cfg.scale = self.config["mlp_hidden"], self.config["resi_3conv"], self.scale
         cfg.upsampler = SWIN2SR_UPSAMPLERS.index(self.config["upsampler"])
-        for i, d in enumerate(self.config["depths"]):
-            cfg.depths[i] = d
+        return blob, (_swin_config_c(cfg, self.config),)
+
+
+class ScuNETNet(_EngineNet):
+    """One SCUNet (dim 64) resident on an engine (sdmi_scunet_*), scale 1.  Any H, W >= 1: the replicate padding to multiples of 64 and
+    the crop happen on the device.  The arena holds the skip tensors and the level-1 work buffers of the padded grid."""
+    _abi = "sdmi_scunet"
+    _noun = "ScuNET"
+    _zero_need_is_a_refusal = True
+
+    def _parse(self, state_dict):
         import ctypes
-        self.handle = _lib.lib.sdmi_swin2sr_create(self.engine.handle, blob.ctypes.data, blob.size, ctypes.byref(cfg))
-        if not self.handle:
-            raise _lib.SdmiError("sdmi_swin2sr_create failed: " + _lib.last_error())
-
-
-class ScuNETNet:
-    """One SCUNet (dim 64) resident on an engine (sdmi_scunet_*): the twin of EsrganNet, scale 1."""
-
-    def __init__(self, state_dict, device=0, engine=None):
         from . import _lib
-        from .engine import Engine
         blob, self.config = parse_scunet_state_dict(state_dict)
         self.scale = 1
-        self.device = int(device)
-        self.engine = engine or Engine(self.device)
         cfg = _lib.ScuNETConfigC()
         for i, d in enumerate(self.config["depths"]):
             cfg.depths[i] = d
-        import ctypes
-        self.handle = _lib.lib.sdmi_scunet_create(self.engine.handle, blob.ctypes.data, blob.size, ctypes.byref(cfg))
-        if not self.handle:
-            raise _lib.SdmiError("sdmi_scunet_create failed: " + _lib.last_error())
-
-    def close(self):
-        if getattr(self, "handle", None):
-            from . import _lib
-            _lib.lib.sdmi_scunet_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def scratch_bytes(self, b, h, w):
-        """Arena bytes of one run, from the engine's own layout (sdmi_scunet_scratch_bytes; 0 for a size the engine refuses)."""
-        from . import _lib
-        return int(_lib.lib.sdmi_scunet_scratch_bytes(self.handle, b, h, w))
-
-    def check_fits(self, b, h, w):
-        """Refuse an input whose intermediates (the skip tensors and the level-1 work buffers of the grid padded to multiples of 64) the
-        arena cannot hold, or one of whose tensors passes 2^31 elements."""
-        need = self.scratch_bytes(b, h, w)
-        limit = arena_limit_bytes(self.device) + self.engine.arena_bytes()
-        if need <= 0 or need > limit:
-            raise EsrganInputTooLarge(f"image {w}x{h} (batch {b}) is too large for ScuNET: its intermediates need "
-                                      f"{need / 2 ** 30:.1f} GiB of engine arena, {limit / 2 ** 30:.1f} GiB are available"
-                                      if need > 0 else
-                                      f"image {w}x{h} (batch {b}) is too large for ScuNET: a tensor passes 2^31 elements")
-
-    def run(self, x, out_u8=False):
-        """x: uint8 [B,H,W,3] (RGB; divided by 255 on the way in) or fp32 [B,3,H,W] in [0, 1], on the engine's device ->
-        fp32 [B,3,H,W], or with out_u8 uint8 [B,H,W,3] (clamp, x255, round half to even).  Any H, W >= 1: the replicate padding to
-        multiples of 64 and the crop happen on the device."""
-        import torch
-        from . import _lib
-        in_u8 = x.dtype == torch.uint8
-        x = x.contiguous() if in_u8 else x.float().contiguous()
-        b, h, w = (x.shape[0], x.shape[1], x.shape[2]) if in_u8 else (x.shape[0], x.shape[2], x.shape[3])
-        assert x.shape[3 if in_u8 else 1] == 3
-        self.check_fits(b, h, w)
-        out = (torch.empty((b, h, w, 3), dtype=torch.uint8, device=x.device) if out_u8
-               else torch.empty((b, 3, h, w), dtype=torch.float32, device=x.device))
-        _lib.check(_lib.lib.sdmi_scunet_run(self.handle, _lib.ptr(x), 1 if in_u8 else 0, b, h, w, _lib.ptr(out), 1 if out_u8 else 0,
-                                            _lib.stream_ptr()), "sdmi_scunet_run")
-        return out
+        return blob, (ctypes.byref(cfg),)
 
 
 def make_upscaler_net(state_dict, device=0, engine=None):
@@ -914,7 +792,7 @@ class UpscalerESRGAN(Upscaler):
         net = self.load_model(selected_model)
         rgb = np.array(img.convert("RGB"))
         h, w = rgb.shape[:2]
-        f = 4 // net.scale if isinstance(net, EsrganNet) else 1   # the x2 / x1 RRDBNets pixel-unshuffle: sides padded up to a multiple, cropped after
+        f = net.unshuffle                                    # the x2 / x1 RRDBNets pixel-unshuffle: sides padded up to a multiple, cropped after
         ph, pw = -h % f, -w % f
         if ph or pw:
             rgb = np.pad(rgb, ((0, ph), (0, pw), (0, 0)), mode="reflect" if min(h, w) > max(ph, pw) else "edge")

@@ -17,7 +17,7 @@ import compact_reference as R
 import rrdb_reference as RR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GPU_FILE_CASES = 2 + 1 + 3 + 3 + 2 + 4 + 1 + 6 + 1 + 1 + 1         # the cases of tests/test_gpu_compact.py
+GPU_FILE_CASES = 2 + 1 + 3 + 3 + 2 + 4 + 1 + 6 + 1 + 1 + 1 + 1         # the cases of tests/test_gpu_compact.py
 
 
 def sub(name):

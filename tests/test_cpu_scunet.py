@@ -21,7 +21,7 @@ import swinir_reference as SR
 from helpers import rel_l2, worst_slice_rel_l2
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GPU_FILE_CASES = 7 + 1 + 2 + 1 + 2 + 4 + 1 + 1 + 1 + 1                     # the cases of tests/test_gpu_scunet.py
+GPU_FILE_CASES = 7 + 1 + 2 + 1 + 2 + 4 + 1 + 1 + 1 + 1 + 1                     # the cases of tests/test_gpu_scunet.py
 
 
 def sub(name):

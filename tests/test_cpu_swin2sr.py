@@ -22,8 +22,8 @@ from helpers import rel_l2, worst_slice_rel_l2
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the cases of tests/test_gpu_swin2sr.py: attention 7 + zero rows + mask + wide rows + refusals | layernorm_add 6 + in place + refusals
-# | networks 9 + uint8 3 + handles | do_upscale + registry
-GPU_FILE_CASES = (7 + 1 + 1 + 1 + 1) + (6 + 1 + 1) + (9 + 3 + 1) + (1 + 1)
+# | networks 9 + arena size + uint8 3 + handles | do_upscale + registry
+GPU_FILE_CASES = (7 + 1 + 1 + 1 + 1) + (6 + 1 + 1) + (9 + 1 + 3 + 1) + (1 + 1)
 
 
 def sub(name):

@@ -19,7 +19,7 @@ import swinir_reference as R
 from helpers import rel_l2, worst_slice_rel_l2
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GPU_FILE_CASES = 8 + 1 + 1 + 6 + 1 + 2 + 1 + 5 + 1 + 1 + 1 + 1          # the cases of tests/test_gpu_swinir.py
+GPU_FILE_CASES = 8 + 1 + 1 + 6 + 1 + 2 + 1 + 5 + 1 + 1 + 1 + 1 + 1          # the cases of tests/test_gpu_swinir.py
 
 
 def sub(name):

@@ -237,6 +237,20 @@ def test_compact_network_vs_reference(dev, num_conv, scale, b, h, w):
         assert float((net.run(x8.to(dev)).cpu() - got.cpu()).abs().max()) < 1e-6
 
 
+def test_compact_run_takes_the_arena_its_scratch_bytes_sizes(dev):
+    """Sizing and running are one walk over the arena: on an engine that has run nothing, one run leaves the arena at what
+    sdmi_compact_scratch_bytes reports, grown by the engine's rule (csrc/engine.cpp ensure_arena: need + need / 16 + 1 MiB)."""
+    engine = sub("engine").Engine(0)
+    net = sub("upscaler").CompactNet(R.make_state_dict(4, 4), device=0, engine=engine)
+    b, h, w = 2, 12, 20
+    assert engine.arena_bytes() == 0
+    got = net.run(R.image(b, h, w, 14).to(dev))
+    n = net.scratch_bytes(b, h, w)
+    assert got.shape == (b, 3, 4 * h, 4 * w) and b * h * w * (32 + 2 * 64) * 2 <= n
+    assert engine.arena_bytes() == n + (n >> 4) + (1 << 20)
+    net.close()
+
+
 def test_compact_network_under_the_training_wrapper(dev):
     up = sub("upscaler")
     sd, net = net_for(4, 4)

@@ -202,6 +202,22 @@ def test_esrgan_network_vs_reference(dev, scale, b, h, w):
     assert_parity(got, ref, R.fp16_twin(sd, x), 1, (0, 2), f"x{scale} network")
 
 
+def test_esrgan_run_takes_the_arena_its_scratch_bytes_sizes(dev):
+    """Sizing and running are one walk over the arena: on an engine that has run nothing, one run leaves the arena at what
+    sdmi_esrgan_scratch_bytes reports, grown by the engine's rule (csrc/engine.cpp ensure_arena: need + need / 16 + 1 MiB).  The x2 model:
+    the pixel-unshuffle factor is part of the layout."""
+    engine = sub("engine").Engine(0)
+    net = sub("upscaler").EsrganNet(R.make_state_dict(2, 2), device=0, engine=engine)
+    b, h, w = 1, 12, 20
+    assert engine.arena_bytes() == 0
+    got = net.run(image(b, h, w, 12).to(dev))
+    n = net.scratch_bytes(b, h, w)
+    m = b * (h // 2) * (w // 2)
+    assert got.shape == (b, 3, 2 * h, 2 * w) and 2 * 2 * 16 * m * 64 < n
+    assert engine.arena_bytes() == n + (n >> 4) + (1 << 20)
+    net.close()
+
+
 def test_esrgan_old_arch_keys_give_the_same_network(dev):
     sd, new = net_for(4)
     _, old = net_for(4, old_arch=True)

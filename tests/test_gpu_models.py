@@ -1393,6 +1393,39 @@ def test_hypernetworks_in_engine_vs_oracle(dev, tiny):
     assert torch.equal(fwd(), base)
 
 
+def test_a_forward_refused_in_its_sizing_walk_leaves_the_engine_usable(dev, tiny):
+    """A forward is one walk twice (csrc/engine.cpp two_pass): dry to size the arena, then the launches.  A hypernetwork module whose last
+    linear does not return to its width — only the C ABI lets one in, hypernetwork.py refuses such a file — is refused by the self-attention
+    of that width inside the dry walk: the call fails before anything is launched.  With the hypernetworks cleared the same call gives the
+    bits it gave before."""
+    import ctypes
+    import json
+    lib, hn_mod = sub("_lib"), sub("hypernetwork")
+    model = tiny["model"]
+    eng = model.engine
+    x, t, ctx = seeded((2, 4, 16, 16), 61).to(dev), torch.tensor([650.0, 40.0], device=dev), seeded((2, 77, 64), 62).to(dev)
+
+    def fwd():
+        eng.set_context(ctx)
+        return eng.unet_forward(x, t, None, None).float().cpu()
+    base = fwd()
+    w, b = torch.zeros((64, 128)), torch.zeros(64)               # 128 -> 64 as the whole K module of width 128 (the text context is 64 wide)
+    try:
+        lib.check(lib.lib.sdmi_unet_hypernet_begin(eng.handle, 1.0), "hypernet_begin")
+        lib.check(lib.lib.sdmi_unet_hypernet_linear(eng.handle, 128, 0, w.data_ptr(), b.data_ptr(), lib.F32, 64, 128, 0), "hypernet_linear")
+        eng.set_context(ctx)
+        lib.check(lib.lib.sdmi_profile_begin(), "profile_begin")
+        with pytest.raises(lib.SdmiError, match="hypernetwork output width must equal its input width"):
+            eng.unet_forward(x, t, None, None)
+        torch.cuda.synchronize()
+        buf = ctypes.create_string_buffer(1 << 16)
+        lib.check(lib.lib.sdmi_profile_end(buf, len(buf)), "profile_end")
+        assert json.loads(buf.value.decode())["kernels"] == []   # refused in the dry walk: nothing was launched
+    finally:
+        hn_mod.load_hypernetworks(model, [], [])
+    assert torch.equal(fwd(), base)
+
+
 def test_arena_reuse_gives_the_same_bits(dev, tiny):
     """Engine option "arena_reuse": the temporaries of every ResBlock / transformer block are released when the block returns and the next
     block's launches write over them (same stream: ordered behind every reader).  Only addresses change — UNet forward (tiny, and an

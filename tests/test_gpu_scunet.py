@@ -244,6 +244,22 @@ def test_scunet_network_vs_reference(dev, name):
     assert_parity(got, ref, twin, 1, (0, 2), f"network {name} {b}x{h}x{w}")
 
 
+def test_scunet_run_takes_the_arena_its_scratch_bytes_sizes(dev):
+    """Sizing and running are one walk over the arena: on an engine that has run nothing, one run leaves the arena at what
+    sdmi_scunet_scratch_bytes reports, grown by the engine's rule (csrc/engine.cpp ensure_arena: need + need / 16 + 1 MiB).  24 x 40 pads
+    to one 64 x 64 grid."""
+    name = "d1-small"
+    depths, (b, h, w) = NET_CASES[name]
+    engine = sub("engine").Engine(0)
+    net = sub("upscaler").ScuNETNet(R.make_state_dict(depths), device=0, engine=engine)
+    assert engine.arena_bytes() == 0
+    got = net.run(R.image(b, h, w, 11).to(dev))
+    n = net.scratch_bytes(b, h, w)
+    assert got.shape == (b, 3, h, w) and 0 < n
+    assert engine.arena_bytes() == n + (n >> 4) + (1 << 20)
+    net.close()
+
+
 SMALL = "d1-small"
 
 

@@ -356,6 +356,21 @@ def test_swin2sr_network_vs_reference(dev, name):
     assert_parity(got, ref, twin, 1, (0, 2), f"network {name} {b}x{h}x{w}")
 
 
+def test_swin2sr_run_takes_the_arena_its_scratch_bytes_sizes(dev):
+    """Sizing and running are one walk over the arena: on an engine that has run nothing, one run leaves the arena at what
+    sdmi_swin2sr_scratch_bytes reports, grown by the engine's rule (csrc/engine.cpp ensure_arena: need + need / 16 + 1 MiB)."""
+    name = "direct-x2"
+    args, kw, (b, h, w) = NET_CASES[name]
+    engine = sub("engine").Engine(0)
+    net = sub("upscaler").Swin2SRNet(state_dict_for(name), device=0, engine=engine)
+    assert engine.arena_bytes() == 0
+    got = net.run(R.image(b, h, w, 20 + args[4]).to(dev))
+    n = net.scratch_bytes(b, h, w)
+    assert got.shape == (b, 3, h * args[4], w * args[4]) and 0 < n
+    assert engine.arena_bytes() == n + (n >> 4) + (1 << 20)
+    net.close()
+
+
 def twin_flip_share(name):
     """The share of output bytes on which the fp16-storage twin and the fp32 reference round to different uint8 values: what fp16
     storage alone moves across a rounding boundary."""

@@ -297,6 +297,21 @@ def test_swinir_network_vs_reference(dev, name):
     assert_parity(got, ref, twin, 1, (0, 2), f"network {name} {b}x{h}x{w}")
 
 
+def test_swinir_run_takes_the_arena_its_scratch_bytes_sizes(dev):
+    """Sizing and running are one walk over the arena: on an engine that has run nothing, one run leaves the arena at what
+    sdmi_swinir_scratch_bytes reports, grown by the engine's rule (csrc/engine.cpp ensure_arena: need + need / 16 + 1 MiB)."""
+    name = "c60-1conv-x2-one-window"
+    args, (b, h, w) = NET_CASES[name]
+    engine = sub("engine").Engine(0)
+    net = sub("upscaler").SwinIRNet(R.make_state_dict(*args), device=0, engine=engine)
+    assert engine.arena_bytes() == 0
+    got = net.run(R.image(b, h, w, 10 + args[4]).to(dev))
+    n = net.scratch_bytes(b, h, w)
+    assert got.shape == (b, 3, h * args[4], w * args[4]) and 0 < n
+    assert engine.arena_bytes() == n + (n >> 4) + (1 << 20)
+    net.close()
+
+
 def test_swinir_uint8_in_and_out(dev):
     """uint8 in is the same image: the same output; uint8 out is model_output_to_u8 of the same run's fp32 output, byte for byte."""
     up = sub("upscaler")
