@@ -770,6 +770,131 @@ int64_t sdmi_scunet_scratch_bytes(sdmi_scunet* h, int B, int H, int W);
  * empty image, tensors of 2^31 elements (B * roundup(H, 64) * roundup(W, 64) * 64). */
 int sdmi_scunet_run(sdmi_scunet* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
 
+/* ---- DAT upscalers ------------------------------------------------------------------------------------------------------------------- */
+
+/* All DAT token tensors below are fp16 rows with a head's D <= 32 channels in a 32-wide slot (dims D .. 31 zero): channel h * D + d of
+ * the network sits at column h * 32 + d.  Every entry refuses (non-zero return, message in sdmi_last_error, nothing written) what its
+ * comment lists. */
+
+/* The spatial window attention of one adaptive spatial attention block (csrc/dat.hip), both branches in one launch: heads
+ * [0, heads / 2) attend in windows of s0 rows x s1 columns, heads [heads / 2, heads) in windows of s1 rows x s0 columns.  Replaces, between
+ * the qkv and proj linears, the zero padding of the q / k / v grids right and bottom to multiples of max(s0, s1) (padded tokens are
+ * q = k = v = 0 and take part as keys with score 0 + bias), torch.roll by minus half the window on the padded grid (shift_h, shift_w =
+ * s0 / 2, s1 / 2; branch 1 by s1 / 2, s0 / 2), the window partition, `(q * scale) k^T + bias[h][rel]` (+ the region mask of the padded
+ * grid, -100 between tokens of different regions, when shifted), softmax, `@ v`, the inverses, and the crop to H x W: all index
+ * arithmetic, no rolled copy, mask or score tensor in memory.  Scores, bias, mask and softmax in fp32; the probabilities are rounded to
+ * fp16 for the second product.
+ * Refused: null descriptor / pointers; B, H or W < 1; heads odd or < 2; D outside 1..32; a split other than (8, 16) and (8, 32); a shift
+ * other than (0, 0) and (s0 / 2, s1 / 2); ldq < 96 heads; ldo < 32 heads; qkv / out not 16-byte aligned, a bias table not 4-byte aligned,
+ * ldq or ldo not a multiple of 8; 2^31 padded tokens. */
+typedef struct sdmi_dat_attn_desc {
+    const void* qkv;       /* fp16 token rows [B*H*W][ldq]: head h has q, k, v at columns h*32, (heads + h)*32, (2 heads + h)*32 */
+    const void* bias0;     /* fp32 [(2 s0 - 1)(2 s1 - 1)][heads / 2]: branch 0's dynamic position bias at the offsets (dy, dx), dy in
+                              [1 - s0, s0 - 1], dx in [1 - s1, s1 - 1], row-major; read at (ya - yb + s0 - 1)(2 s1 - 1) + (xa - xb + s1 - 1) */
+    const void* bias1;     /* fp32 [(2 s1 - 1)(2 s0 - 1)][heads / 2]: branch 1's, with s1 and s0 in each other's places */
+    void* out;             /* fp16 token rows [B*H*W][ldo]: head h at columns h*32, dims D .. 31 stored as zero; columns >= 32 heads untouched */
+    int32_t B, H, W;       /* the token grid (row-major rows), any size */
+    int32_t heads, D;
+    int32_t ldq, ldo;
+    int32_t s0, s1;        /* (8, 16) | (8, 32) */
+    int32_t shift_h, shift_w;  /* (0, 0) | (s0 / 2, s1 / 2) */
+    float scale;           /* D^-1/2 */
+} sdmi_dat_attn_desc;
+int sdmi_dat_window_attention(const sdmi_dat_attn_desc* d, void* stream);
+
+/* Channel attention of one adaptive channel attention block, first launch: per (image, head) and per block of 512 tokens the fp32 sums
+ * over the block's tokens n of q[n][i] k[n][j] (i, j < 32), q[n][i]^2 and k[n][j]^2.  qkv as above ([B*N][ldq]; only q and k are read);
+ * partials fp32 [B][heads][ceil(N / 512)][1088]: the 32 x 32 products at i * 32 + j, then the 32 + 32 squares.  Every sum is taken in token
+ * order by one thread.  Refused: null pointers; B or N < 1; heads outside 1..1024; ldq < 64 heads; qkv / partials not 16-byte aligned, ldq
+ * not a multiple of 8; 2^31 tokens. */
+int sdmi_dat_channel_gram(const void* qkv, void* partials, int B, int N, int heads, int ldq, void* stream);
+/* ... second launch: the partials added in block order (no atomics: two runs give the same bits), then
+ *   A[i][j] = softmax_j(temperature[h] * G[i][j] / (max(|q_i|, 1e-12) max(|k_j|, 1e-12))),  i, j < D,
+ * in fp32, written as fp16 into the head's diagonal block of A [B][32 heads][32 heads] (rows h*32 + i, columns h*32 + j), zeros
+ * everywhere else: att = v A^T is then one batched 1x1 sdmi_conv_gemm with A as per-image weights.  temperature fp32 [heads].
+ * Refused: null pointers; B or N < 1; D outside 1..32; partials / A not 16-byte aligned, temperature not 4-byte aligned. */
+int sdmi_dat_channel_softmax(const void* partials, const void* temperature, void* A, int B, int N, int heads, int D, void* stream);
+
+/* Depthwise 3x3 conv with zero padding on fp16 token rows x [B*H*W][ldx] (C channels read, C % 8 == 0): w fp32 [9][C] (tap (dy + 1) * 3 +
+ * dx + 1 first, then the channel), bias fp32 [C], fp32 sums.  ep 0: out = GELU(conv) (exact erf form; the adaptive interaction module's
+ * conv, its BatchNorm folded into w and bias).  ep 1: out = conv * mul (the feed-forward gate x1 * dwconv(norm(x2)); mul [B*H*W][ldm]).
+ * out [B*H*W][ldo] must not alias x or mul.  Refused: null pointers (mul with ep 1); ep outside 0..1; an empty tensor; C % 8 != 0; a row
+ * stride below C or not a multiple of 8; x / mul / out not 16-byte aligned; out aliasing an input. */
+int sdmi_dat_dwconv3x3(const void* x, const void* w, const void* bias, const void* mul, void* out, int B, int H, int W, int C, int ldx, int ldm,
+                       int ldo, int ep, void* stream);
+
+/* The channel gate of the adaptive interaction module: gate fp32 [B][C] = sigmoid(w2 GELU(w1 mean_n(x[b][n]) + b1) + b2) of the fp16
+ * token rows x [B*N][ld]: global average pool, Conv1x1 C -> C8 with its BatchNorm folded in (w1 fp32 [C8][C], b1 [C8]), GELU, Conv1x1
+ * C8 -> C (w2 fp32 [C][C8], b2 [C]).  Two launches: per block of 256 tokens the sums of every channel into ws (fp32
+ * [B][ceil(N / 256)][C]; strided token groups added in order, then the groups in order), then one workgroup per image adds the blocks
+ * in order: every sum has one fixed order, two runs give the same bits.  Refused: null pointers; B or N < 1; C not a multiple of 8 in
+ * 8..1024; C8 outside 1..128; ld < C or not a multiple of 8; x not 16-byte aligned, an fp32 argument not 4-byte aligned; 2^31 tokens. */
+int sdmi_dat_pool_gate(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, void* ws, void* gate, int B, int N, int C,
+                       int C8, int ld, void* stream);
+
+/* The spatial gate and the sum that attn.proj reads, one pass per token row:
+ *   sg = sigmoid(w2 . GELU(w1 s + b1) + b2)   (Conv1x1 C -> C16 with its BatchNorm folded in, GELU, Conv1x1 C16 -> 1)
+ *   out = s * gate[image] + t * sg
+ * with (s, t) = (att, conv) in a spatial block — out = att sigmoid(cmap(conv)) + sigmoid(smap(att)) conv — and (conv, att) in a channel
+ * block — out = att sigmoid(smap(conv)) + conv sigmoid(cmap(att)); `gate` is sdmi_dat_pool_gate of t.  Refused: null pointers; rows not a
+ * positive multiple of rows_per_image; C not a multiple of 64 in 64..512; C16 < 1 or C16 * C > 8192; a row stride below C; an fp32
+ * argument not 4-byte aligned. */
+typedef struct sdmi_dat_aim_desc {
+    const void* s;         /* fp16 rows [rows][lds] */
+    const void* t;         /* fp16 rows [rows][ldt] */
+    const void* gate;      /* fp32 [rows / rows_per_image][C] */
+    const void* w1;        /* fp32 [C16][C] */
+    const void* b1;        /* fp32 [C16] */
+    const void* w2;        /* fp32 [C16] */
+    float b2;
+    void* out;             /* fp16 rows [rows][ldo]; columns >= C untouched */
+    int64_t rows;
+    int32_t rows_per_image, C, C16;
+    int32_t lds, ldt, ldo;
+} sdmi_dat_aim_desc;
+int sdmi_dat_aim_combine(const sdmi_dat_aim_desc* d, void* stream);
+
+/* A whole DAT network (DAT.forward of basicsr's dat_arch.py with upsampler `pixelshuffle` and resi_connection `1conv`; the webui's
+ * "DAT x2" / "DAT x3" / "DAT x4" of modules/dat_model.py) held by an engine (scratch from the engine's arena, a fixed set of buffers
+ * whatever the depths).  Replaces the model call inside UpscalerDAT.do_upscale, run on the image whole instead of in DAT_tile tiles.
+ * Fixed: head dim <= 32, an even head count, split (8, 16) or (8, 32), 3 channels in / out, num_feat 64, img_range 1, scale 2, 3 or 4.
+ * Block j of a group is a spatial block for even j, a channel block for odd j; it is shifted when (group i even, j > 0, (j - 2) % 4 == 0)
+ * or (i odd, j % 4 == 0).  C8 = embed_dim / 8, C16 = embed_dim / 16 (integer division), half = ffn_hidden / 2.
+ * blob: host fp32, every tensor flattened in the checkpoint's channel order, in this order (weight then bias for convs, linears, norms):
+ *   conv_first; before_RG.1;
+ *   per group i, per block j:
+ *     norm1; attn.qkv;
+ *     spatial blocks: the dynamic position bias of attns.0 evaluated at its offsets [(2 s0 - 1)(2 s1 - 1)][heads / 2], then attns.1's
+ *       [(2 s1 - 1)(2 s0 - 1)][heads / 2];  channel blocks: attn.temperature [heads];
+ *     attn.dwconv with its BatchNorm folded in: [C][9], [C];
+ *     attn.channel_interaction: .1 with .2 (BatchNorm) folded in [C8][C], [C8]; .4 [C][C8], [C];
+ *     attn.spatial_interaction: .0 with .1 folded in [C16][C], [C16]; .3 [C16], [1];
+ *     attn.proj; norm2; ffn.fc1 [ffn_hidden][C]; ffn.sg.norm [half]; ffn.sg.conv [half][9], [half]; ffn.fc2 [C][half];
+ *     then the group's conv [C][C][3][3];
+ *   norm; conv_after_body; conv_before_upsample.0; upsample.0; upsample.2 (scale 4 only); conv_last.
+ * sdmi_dat_blob_floats gives its length (0 for a config the engine refuses).  NULL on error: a null argument, a blob of another length,
+ * embed_dim not a multiple of num_heads, num_heads odd, num_heads * 32 < embed_dim, num_heads * 32 > 512, embed_dim < 16, a split other
+ * than (8, 16) and (8, 32), ffn_hidden odd or < 2, a scale other than 2, 3, 4, more than 16 groups, a depth outside 1..64. */
+typedef struct sdmi_dat_config {
+    int32_t embed_dim;
+    int32_t num_layers;
+    int32_t depths[16];    /* blocks per residual group */
+    int32_t num_heads;
+    int32_t split0, split1;
+    int32_t ffn_hidden;    /* expansion_factor * embed_dim */
+    int32_t scale;         /* 2 | 3 | 4 */
+} sdmi_dat_config;
+typedef struct sdmi_dat sdmi_dat;
+int64_t sdmi_dat_blob_floats(const sdmi_dat_config* cfg);
+sdmi_dat* sdmi_dat_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_dat_config* cfg);
+void sdmi_dat_destroy(sdmi_dat* h);
+/* arena bytes a run on B images of H x W needs (0 for a refused size) */
+int64_t sdmi_dat_scratch_bytes(sdmi_dat* h, int B, int H, int W);
+/* in / out as sdmi_esrgan_run: uint8 HWC or fp32 NCHW in, fp32 NCHW or uint8 HWC [B][H s][W s][3] out (device memory).  Any H, W >= 1:
+ * the network's own convs run on the H x W grid, only the attention windows see a padded grid.  Refused: null pointers, an empty image,
+ * tensors of 2^31 elements. */
+int sdmi_dat_run(sdmi_dat* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

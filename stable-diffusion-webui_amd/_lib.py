@@ -94,6 +94,28 @@ class ScuNETConfigC(C.Structure):
     _fields_ = [("depths", C.c_int32 * 7)]
 
 
+class DatAttnDesc(C.Structure):
+    _fields_ = [
+        ("qkv", C.c_void_p), ("bias0", C.c_void_p), ("bias1", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("heads", C.c_int32), ("D", C.c_int32),
+        ("ldq", C.c_int32), ("ldo", C.c_int32), ("s0", C.c_int32), ("s1", C.c_int32),
+        ("shift_h", C.c_int32), ("shift_w", C.c_int32), ("scale", C.c_float),
+    ]
+
+
+class DatAimDesc(C.Structure):
+    _fields_ = [
+        ("s", C.c_void_p), ("t", C.c_void_p), ("gate", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p),
+        ("b2", C.c_float), ("out", C.c_void_p), ("rows", C.c_int64),
+        ("rows_per_image", C.c_int32), ("C", C.c_int32), ("C16", C.c_int32), ("lds", C.c_int32), ("ldt", C.c_int32), ("ldo", C.c_int32),
+    ]
+
+
+class DATConfigC(C.Structure):
+    _fields_ = [("embed_dim", C.c_int32), ("num_layers", C.c_int32), ("depths", C.c_int32 * 16), ("num_heads", C.c_int32),
+                ("split0", C.c_int32), ("split1", C.c_int32), ("ffn_hidden", C.c_int32), ("scale", C.c_int32)]
+
+
 class UNetConfigC(C.Structure):
     _fields_ = [
         ("in_channels", C.c_int32), ("out_channels", C.c_int32), ("model_channels", C.c_int32),
@@ -227,8 +249,16 @@ _SIGS = {
     "sdmi_scu_block_pack": (_i, [_vp] * 13 + [_i, _vp]),
     "sdmi_scunet_blob_floats": (_i64, [C.POINTER(ScuNETConfigC)]),
     "sdmi_scunet_create": (_vp, [_vp, _vp, _i64, C.POINTER(ScuNETConfigC)]),
+    "sdmi_dat_window_attention": (_i, [C.POINTER(DatAttnDesc), _vp]),
+    "sdmi_dat_channel_gram": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "sdmi_dat_channel_softmax": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "sdmi_dat_dwconv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "sdmi_dat_pool_gate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sdmi_dat_aim_combine": (_i, [C.POINTER(DatAimDesc), _vp]),
+    "sdmi_dat_blob_floats": (_i64, [C.POINTER(DATConfigC)]),
+    "sdmi_dat_create": (_vp, [_vp, _vp, _i64, C.POINTER(DATConfigC)]),
 }
-for _net in ("esrgan", "compact", "swinir", "swin2sr", "scunet"):       # the upscaler nets: create / blob_floats differ (above), the rest is one shape
+for _net in ("esrgan", "compact", "swinir", "swin2sr", "scunet", "dat"):       # the upscaler nets: create / blob_floats differ (above), the rest is one shape
     _SIGS[f"sdmi_{_net}_destroy"] = (None, [_vp])
     _SIGS[f"sdmi_{_net}_scratch_bytes"] = (_i64, [_vp, _i, _i, _i])
     _SIGS[f"sdmi_{_net}_run"] = (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp])

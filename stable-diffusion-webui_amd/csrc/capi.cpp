@@ -44,6 +44,10 @@ int64_t scunet_blob_floats(const sdmi_scunet_config* cfg);
 int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_scunet_config* cfg, sdmi_scunet** out);
 int64_t scunet_scratch_bytes(const sdmi_scunet* n, int B, int H, int W);
 int scunet_run(sdmi_scunet* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
+int64_t dat_blob_floats(const sdmi_dat_config* cfg);
+int dat_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_dat_config* cfg, sdmi_dat** out);
+int64_t dat_scratch_bytes(const sdmi_dat* n, int B, int H, int W);
+int dat_run(sdmi_dat* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
 }  // namespace sdmi
 
 using namespace sdmi;
@@ -815,6 +819,74 @@ int64_t sdmi_scunet_scratch_bytes(sdmi_scunet* h, int B, int H, int W) { return 
 int sdmi_scunet_run(sdmi_scunet* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
     API_GUARD_BEGIN
     return scunet_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_dat_window_attention(const sdmi_dat_attn_desc* d, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(d, "null descriptor");
+    SDMI_REQUIRE(d->s0 == 8 && (d->s1 == 16 || d->s1 == 32), "split must be (8, 16) or (8, 32)");
+    SDMI_REQUIRE((d->shift_h == 0 && d->shift_w == 0) || (d->shift_h == d->s0 / 2 && d->shift_w == d->s1 / 2), "shift must be (0, 0) or half the split");
+    DatAttnP p{};
+    p.qkv = (const half_t*)d->qkv; p.bias0 = (const float*)d->bias0; p.bias1 = (const float*)d->bias1; p.out = (half_t*)d->out;
+    p.B = d->B; p.H = d->H; p.W = d->W; p.heads = d->heads; p.D = d->D; p.ldq = d->ldq; p.ldo = d->ldo; p.s0 = d->s0; p.s1 = d->s1;
+    p.shifted = d->shift_h != 0 ? 1 : 0; p.scale = d->scale;
+    return launch_dat_window_attention(p, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_dat_channel_gram(const void* qkv, void* partials, int B, int N, int heads, int ldq, void* stream) {
+    API_GUARD_BEGIN
+    return launch_dat_channel_gram((const half_t*)qkv, (float*)partials, B, N, heads, ldq, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_dat_channel_softmax(const void* partials, const void* temperature, void* A, int B, int N, int heads, int D, void* stream) {
+    API_GUARD_BEGIN
+    return launch_dat_channel_softmax((const float*)partials, (const float*)temperature, (half_t*)A, B, N, heads, D, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_dat_dwconv3x3(const void* x, const void* w, const void* bias, const void* mul, void* out, int B, int H, int W, int C, int ldx, int ldm,
+                       int ldo, int ep, void* stream) {
+    API_GUARD_BEGIN
+    return launch_dat_dwconv3x3((const half_t*)x, (const float*)w, (const float*)bias, (const half_t*)mul, (half_t*)out, B, H, W, C, ldx, ldm, ldo, ep,
+                                (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_dat_pool_gate(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, void* ws, void* gate, int B, int N, int C,
+                       int C8, int ld, void* stream) {
+    API_GUARD_BEGIN
+    return launch_dat_pool_gate((const half_t*)x, (const float*)w1, (const float*)b1, (const float*)w2, (const float*)b2, (float*)ws, (float*)gate, B,
+                                N, C, C8, ld, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_dat_aim_combine(const sdmi_dat_aim_desc* d, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(d, "null descriptor");
+    DatAimP p{};
+    p.s = (const half_t*)d->s; p.t = (const half_t*)d->t; p.cg = (const float*)d->gate; p.w1 = (const float*)d->w1; p.b1 = (const float*)d->b1;
+    p.w2 = (const float*)d->w2; p.b2 = d->b2; p.out = (half_t*)d->out; p.rows = d->rows; p.rows_per_image = d->rows_per_image;
+    p.C = d->C; p.C16 = d->C16; p.lds = d->lds; p.ldt = d->ldt; p.ldo = d->ldo;
+    return launch_dat_aim_combine(p, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int64_t sdmi_dat_blob_floats(const sdmi_dat_config* cfg) { return dat_blob_floats(cfg); }
+
+sdmi_dat* sdmi_dat_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_dat_config* cfg) {
+    return created<sdmi_dat>([&](sdmi_dat** n) { return dat_create(e, (const float*)blob_f32, blob_floats, cfg, n); });
+}
+
+void sdmi_dat_destroy(sdmi_dat* h) { delete h; }
+
+int64_t sdmi_dat_scratch_bytes(sdmi_dat* h, int B, int H, int W) { return dat_scratch_bytes(h, B, H, W); }
+
+int sdmi_dat_run(sdmi_dat* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
+    API_GUARD_BEGIN
+    return dat_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
     API_GUARD_END
 }
 

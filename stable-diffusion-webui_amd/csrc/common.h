@@ -356,6 +356,47 @@ int launch_scu_input(const void* in, int u8, half_t* out, int B, int H, int W, i
 int launch_scu_patch2(const half_t* src, half_t* dst, int B, int h, int w, int C, int to_lo, hipStream_t s);
 int launch_scu_add(half_t* x, const half_t* y, int64_t n, hipStream_t s);            // x += y (a skip connection)
 
+// ---- DAT: rectangular-window attention on both halves of the heads, channel attention, depthwise 3x3 conv on token rows, the gates
+// ---- of the adaptive interaction module (dat.hip) ---------------------------------------------------------------------------------
+struct DatAttnP {
+    const half_t* qkv;     // token rows [B*H*W][ldq]: head h has q / k / v in 32-wide slots at columns h*32, (heads + h)*32, (2 heads + h)*32
+    const float* bias0;    // branch 0 (heads [0, heads/2), windows s0 x s1): [(2 s0 - 1)(2 s1 - 1)][heads / 2]
+    const float* bias1;    // branch 1 (heads [heads/2, heads), windows s1 x s0): [(2 s1 - 1)(2 s0 - 1)][heads / 2]
+    half_t* out;           // token rows [B*H*W][ldo]: head h at columns h*32, dims D .. 31 stored as zero
+    int B, H, W;           // token grid, any size: padded right / bottom to multiples of max(s0, s1) with zero tokens
+    int heads, D, ldq, ldo;
+    int s0, s1;            // split: (8, 16) | (8, 32)
+    int shifted;           // 1: both branches are rolled by half their window on the padded grid, the region mask is applied
+    float scale;           // D^-1/2
+    int Hpad, Wpad;        // set by the launcher
+};
+int launch_dat_window_attention(const DatAttnP& p, hipStream_t s);
+constexpr int DAT_GRAM_TOKENS = 512;    // tokens per partial of dat_channel_gram
+constexpr int DAT_POOL_TOKENS = 256;    // tokens per partial of dat_pool_gate
+// part fp32 [B][heads][ceil(N / DAT_GRAM_TOKENS)][1088]: sum q_i k_j (32 x 32), sum q_i^2 (32), sum k_j^2 (32) over a block of tokens
+int launch_dat_channel_gram(const half_t* qkv, float* part, int B, int N, int heads, int ldq, hipStream_t s);
+// the partials added in block order -> A fp16 [B][32 heads][32 heads], block-diagonal: softmax_j(temperature[h] q^_i . k^_j) for i, j < D
+int launch_dat_channel_softmax(const float* part, const float* temperature, half_t* A, int B, int N, int heads, int D, hipStream_t s);
+// depthwise 3x3, zero padding, on token rows: w fp32 [9][C] (tap-major), bias fp32 [C]; ep 0: GELU, ep 1: times mul's row
+int launch_dat_dwconv3x3(const half_t* x, const float* w, const float* bias, const half_t* mul, half_t* out, int B, int H, int W, int C, int ldx,
+                         int ldm, int ldo, int ep, hipStream_t s);
+// gate fp32 [B][C] = sigmoid(w2 GELU(w1 mean_tokens(x) + b1) + b2); w1 [C8][C], w2 [C][C8]; ws fp32 [B][ceil(N / DAT_POOL_TOKENS)][C]
+int launch_dat_pool_gate(const half_t* x, const float* w1, const float* b1, const float* w2, const float* b2, float* ws, float* gate, int B, int N,
+                         int C, int C8, int ld, hipStream_t s);
+struct DatAimP {
+    const half_t* s;       // the operand the spatial MLP reads, rows of stride lds
+    const half_t* t;       // the other operand (the one the channel gate was pooled from), rows of stride ldt
+    const float* cg;       // [images][C]: the channel gate
+    const float* w1;       // [C16][C]
+    const float* b1;       // [C16]
+    const float* w2;       // [C16]
+    float b2;
+    half_t* out;           // out = s cg + t sigmoid(w2 . GELU(w1 s + b1) + b2), rows of stride ldo
+    long long rows;
+    int rows_per_image, C, C16, lds, ldt, ldo;
+};
+int launch_dat_aim_combine(const DatAimP& p, hipStream_t s);
+
 // ---- norms ------------------------------------------------------------------------------------------------
 // pre_nchunk > 0: `ws` already holds (mean, M2) [B][pre_nchunk][groups][2] of HW / pre_nchunk rows each (written by the producing GEMM): skip the statistics pass
 // x0_lo / x1_lo (engine option "residual_fp32"): the lo parts when the inputs are (hi, lo) fp16 pairs of the carried stream

@@ -2918,6 +2918,292 @@ int scunet_run(sdmi_scunet* n, const void* in, int in_u8, int B, int H, int W, v
     return run_pass(e, s, [&](Run& r) { return scunet_pass(r, *n, in, in_u8, B, H, W, out, out_u8); });
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// DAT upscalers (pixelshuffle, 1conv): DAT.forward as GEMM launches (gemm.hip), swin_layernorm and Swin2SR's tail passes (swinir.hip),
+// the window / channel attention, depthwise convs and AIM gates of dat.hip, conv_last on rrdb_conv (rrdb.hip)
+// ------------------------------------------------------------------------------------------------------------
+// blob: fp32, in the order include/sdmi.h documents at sdmi_dat_config.
+static bool dat_config_ok(const sdmi_dat_config& c, std::string* why) {
+    auto fail = [&](const char* m) { if (why) *why = m; return false; };
+    if (c.embed_dim < 16 || c.num_heads < 2 || c.embed_dim % c.num_heads) return fail("embed_dim must be at least 16 and a multiple of num_heads");
+    if (c.num_heads % 2) return fail("num_heads must be even (half of the heads per window branch)");
+    if (c.num_heads * 32 < c.embed_dim) return fail("head dim = embed_dim / num_heads must be <= 32 (num_heads * 32 >= embed_dim)");
+    if (c.num_heads * 32 > 512 || (c.embed_dim / 16) * c.num_heads * 32 > 8192) return fail("num_heads * 32 must be <= 512 (the AIM pass holds a row per wave)");
+    if (c.split0 != 8 || (c.split1 != 16 && c.split1 != 32)) return fail("split must be (8, 16) or (8, 32)");
+    if (c.num_layers < 1 || c.num_layers > 16) return fail("num_layers in 1..16");
+    for (int i = 0; i < c.num_layers; ++i)
+        if (c.depths[i] < 1 || c.depths[i] > 64) return fail("depths[i] in 1..64");
+    if (c.ffn_hidden < 2 || c.ffn_hidden % 2) return fail("ffn_hidden must be even (the feed-forward gate splits it in two)");
+    if (c.scale != 2 && c.scale != 3 && c.scale != 4) return fail("scale 2 | 3 | 4");
+    return true;
+}
+
+int64_t dat_blob_floats(const sdmi_dat_config* c) {
+    if (!c || !dat_config_ok(*c, nullptr)) return 0;
+    const int64_t C = c->embed_dim, E = c->ffn_hidden, hf = E / 2, C8 = C / 8, C16 = C / 16, hh = c->num_heads / 2;
+    const int64_t tab = (2 * c->split0 - 1) * (2 * c->split1 - 1) * hh, s2 = c->scale == 3 ? 9 : 4;
+    auto lin = [](int64_t o, int64_t i, int64_t taps = 1) { return o * i * taps + o; };
+    const int64_t common = 2 * C + lin(3 * C, C) + 10 * C + (C8 * C + C8 + C * C8 + C) + (C16 * C + 2 * C16 + 1) + lin(C, C) + 2 * C + lin(E, C) +
+                           2 * hf + 10 * hf + lin(C, hf);
+    int64_t n = lin(C, 3, 9) + 2 * C;
+    for (int i = 0; i < c->num_layers; ++i) {
+        const int64_t d = c->depths[i], spatial = (d + 1) / 2;
+        n += d * common + spatial * 2 * tab + (d - spatial) * c->num_heads + lin(C, C, 9);
+    }
+    return n + 2 * C + lin(C, C, 9) + lin(64, C, 9) + (c->scale == 4 ? 2 : 1) * lin(s2 * 64, 64, 9) + lin(3, 64, 9);
+}
+
+int dat_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_dat_config* cfg, sdmi_dat** out) {
+    SDMI_REQUIRE(e && blob && cfg && out, "null argument");
+    std::string why;
+    SDMI_REQUIRE(dat_config_ok(*cfg, &why), "DAT config: " + why);
+    SDMI_REQUIRE(blob_floats == dat_blob_floats(cfg), "weight blob size does not match the config");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    std::unique_ptr<sdmi_dat> holder(new sdmi_dat);
+    sdmi_dat* net = holder.get();
+    net->e = e; net->cfg = *cfg;
+    const int C = cfg->embed_dim, heads = cfg->num_heads, D = C / heads, E = cfg->ffn_hidden, hf = E / 2, C8 = C / 8, C16 = C / 16;
+    const int Cp = rup(C, 64), Sp = 32 * heads, Hh = rup(hf, 64);
+    net->C = C; net->Cp = Cp; net->D = D; net->Sp = Sp; net->half = hf; net->Hh = Hh; net->C8 = C8; net->C16 = C16;
+    const float* src = blob;
+    auto ident = [](int v) { return v; };
+    auto slot = [&](int v) { return (v / D) * 32 + v % D; };            // channel h * D + d -> column h * 32 + d
+    // one conv / linear off the blob, as swin_net_build packs it: output row o at row_of(o), input channel i at col_of(i), the rest zero
+    auto pack = [&](ConvW* c, int O, int I, int taps, int n_pad, int cin_pad, const std::function<int(int)>& row_of,
+                    const std::function<int(int)>& col_of, const float* bias_add = nullptr) -> int {
+        std::vector<half_t> w((size_t)n_pad * taps * cin_pad, (half_t)0.f);
+        std::vector<float> b((size_t)n_pad, 0.f);
+        for (int o = 0; o < O; ++o)
+            for (int i = 0; i < I; ++i)
+                for (int t = 0; t < taps; ++t)
+                    w[((size_t)row_of(o) * taps + t) * cin_pad + col_of(i)] = (half_t)src[((size_t)o * I + i) * taps + t];
+        src += (size_t)O * I * taps;
+        for (int o = 0; o < O; ++o) b[(size_t)row_of(o)] = src[o] + (bias_add ? bias_add[o] : 0.f);
+        src += O;
+        c->cin = I; c->cin_pad = cin_pad; c->cout = O; c->n_pad = n_pad; c->taps = taps;
+        TRY(net_upload(net, w.data(), w.size() * sizeof(half_t), (void**)&c->w));
+        return net_upload(net, b.data(), b.size() * sizeof(float), (void**)&c->b);
+    };
+    // an fp32 matrix [rows][cols] off the blob -> [rows_pad][cols_pad] with row r at row_of(r), column c at col_of(c); transposed: the
+    // blob holds [cols][rows] (a depthwise weight [C][9] -> [9][C])
+    auto mat = [&](float** dev, int rows, int cols, int rows_pad, int cols_pad, const std::function<int(int)>& row_of,
+                   const std::function<int(int)>& col_of, bool transposed = false) -> int {
+        std::vector<float> m((size_t)rows_pad * cols_pad, 0.f);
+        for (int rr = 0; rr < rows; ++rr)
+            for (int cc = 0; cc < cols; ++cc)
+                m[(size_t)row_of(rr) * cols_pad + col_of(cc)] = transposed ? src[(size_t)cc * rows + rr] : src[(size_t)rr * cols + cc];
+        src += (size_t)rows * cols;
+        return net_upload(net, m.data(), m.size() * sizeof(float), (void**)dev);
+    };
+    auto raw = [&](float** dev, size_t count) -> int {
+        TRY(net_upload(net, src, count * sizeof(float), (void**)dev));
+        src += count;
+        return 0;
+    };
+    const size_t tab = (size_t)(2 * cfg->split0 - 1) * (2 * cfg->split1 - 1) * (heads / 2);
+
+    TRY(pack(&net->first, C, 3, 9, Cp, 64, ident, ident));
+    TRY(net_norm(net, src, C, &net->rg_norm));
+    net->layers.resize((size_t)cfg->num_layers);
+    for (int i = 0; i < cfg->num_layers; ++i) {
+        sdmi_dat::Layer& L = net->layers[(size_t)i];
+        L.blocks.resize((size_t)cfg->depths[i]);
+        for (int j = 0; j < cfg->depths[i]; ++j) {
+            sdmi_dat::Block& bk = L.blocks[(size_t)j];
+            bk.spatial = j % 2 == 0;
+            bk.shifted = bk.spatial && ((i % 2 == 0 && j > 0 && (j - 2) % 4 == 0) || (i % 2 == 1 && j % 4 == 0));
+            TRY(net_norm(net, src, C, &bk.n1));
+            TRY(pack(&bk.qkv, 3 * C, C, 1, 3 * Sp, Cp, [&](int o) { return (o / C) * Sp + slot(o % C); }, ident));
+            if (bk.spatial) {
+                TRY(raw(&bk.tab0, tab));
+                TRY(raw(&bk.tab1, tab));
+            } else {
+                TRY(raw(&bk.temperature, (size_t)heads));
+            }
+            TRY(mat(&bk.dw_w, 9, C, 9, Sp, ident, slot, true));
+            TRY(mat(&bk.dw_b, 1, C, 1, Sp, ident, slot));
+            TRY(mat(&bk.ci_w1, C8, C, C8, Sp, ident, slot));
+            TRY(raw(&bk.ci_b1, (size_t)C8));
+            TRY(mat(&bk.ci_w2, C, C8, Sp, C8, slot, ident));
+            TRY(mat(&bk.ci_b2, 1, C, 1, Sp, ident, slot));
+            TRY(mat(&bk.si_w1, C16, C, C16, Sp, ident, slot));
+            TRY(raw(&bk.si_b1, (size_t)C16));
+            TRY(raw(&bk.si_w2, (size_t)C16));
+            bk.si_b2 = *src++;
+            TRY(pack(&bk.proj, C, C, 1, Cp, Sp, ident, slot));
+            TRY(net_norm(net, src, C, &bk.n2));
+            TRY(pack(&bk.fc1, E, C, 1, 2 * Hh, Cp, [&](int o) { return o < hf ? o : Hh + o - hf; }, ident));     // x1 | x2 in two 64-multiple halves
+            TRY(net_norm(net, src, hf, &bk.sgn));
+            TRY(mat(&bk.sg_w, 9, hf, 9, Hh, ident, ident, true));
+            TRY(mat(&bk.sg_b, 1, hf, 1, Hh, ident, ident));
+            TRY(pack(&bk.fc2, C, hf, 1, Cp, Hh, ident, ident));
+        }
+        TRY(pack(&L.conv, C, C, 9, Cp, Cp, ident, ident));
+    }
+    TRY(net_norm(net, src, C, &net->norm));
+    TRY(pack(&net->after, C, C, 9, Cp, Cp, ident, ident));
+    const float mean[3] = {0.4488f, 0.4371f, 0.4040f};                 // y / img_range + mean folds into conv_last's bias
+    const int f2 = cfg->scale == 3 ? 9 : 4;                             // torch's channel c f^2 + (i f + j) -> row (i f + j) * 64 + c
+    TRY(pack(&net->before, 64, C, 9, 64, Cp, ident, ident));
+    for (int k = 0; k < (cfg->scale == 4 ? 2 : 1); ++k)
+        TRY(pack(&net->ps[k], f2 * 64, 64, 9, f2 * 64, 64, [&](int o) { return (o % f2) * 64 + o / f2; }, ident));
+    TRY(pack(&net->last, 3, 64, 9, 32, 64, ident, ident, mean));
+    SDMI_REQUIRE(src - blob == blob_floats, "internal: blob walk does not end at its length");
+    SDMI_CHECK_HIP(hipDeviceSynchronize());
+    *out = holder.release();
+    return 0;
+}
+
+// One pass over the network (dry: the arena layout alone).  M = B * H * W tokens, no padding of the grid (the window attention pads by
+// index).  Stream tensors are Cp wide with zeros in columns C .. Cp - 1; q | k | v, att, the AIM conv and proj's input are Sp = 32 heads wide
+// in head slots; fc1 writes x1 | x2 as two Hh-wide halves of one row.
+static int dat_pass(Run& r, const sdmi_dat& n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8) {
+    const int sc = n.cfg.scale, Cp = n.Cp, Sp = n.Sp, Hh = n.Hh, heads = n.cfg.num_heads, N = H * W;
+    const size_t M = (size_t)B * N;
+    r.ar->reset();
+    half_t* x0 = r.H(M * 64);                                 // the mean-subtracted input
+    half_t* feat = r.H(M * Cp);                               // conv_first's output: the trunk's skip tensor
+    half_t* pool[4];                                          // token tensors: a group's input and the blocks' ping-pong
+    for (half_t*& p : pool) p = r.H(M * Cp);
+    half_t* ln = r.H(M * Cp);
+    half_t* qkv = r.H(M * 3 * Sp);
+    half_t* att = r.H(M * Sp);
+    half_t* cv = r.H(M * Sp);                                 // GELU(BN(dwconv(v)))
+    half_t* mix = r.H(M * Sp);                                // what proj reads
+    half_t* hid = r.H(M * 2 * Hh);
+    half_t* gated = r.H(M * Hh);                              // x1 * dwconv(norm(x2))
+    float* gram = r.F((size_t)B * heads * cdiv(N, DAT_GRAM_TOKENS) * 1088);
+    half_t* amat = r.H((size_t)B * Sp * Sp);
+    float* pool_ws = r.F((size_t)B * cdiv(N, DAT_POOL_TOKENS) * Sp);
+    float* cgate = r.F((size_t)B * Sp);
+    half_t* c1 = r.H(M * 64);
+    half_t* up[2] = {r.H(M * sc * sc * 64), r.H(M * sc * sc * 64)};      // the step convs' outputs and their shuffles, ping-pong
+    float* full = r.F(M * sc * sc * 3);
+
+    auto conv = [&](const ConvW& w, const half_t* a, const half_t* resid, half_t* o, int flags = 0, int f = 1) -> int {      // 3x3 pad 1 / linear, on the grid x f
+        ConvArgs c;
+        c.a0 = a; c.c0 = w.cin_pad; c.B = B; c.Hi = c.Ho = H * f; c.Wi = c.Wo = W * f; c.pad = w.taps == 9 ? 1 : 0;
+        c.resid = resid; c.ldr = w.n_pad; c.out = o; c.ldo = w.n_pad; c.flags = flags;
+        const size_t mark = r.ar->mark();                     // a split-K workspace lives for its launch only
+        const int rc = run_conv(r, w, c);
+        r.ar->rewind(mark);
+        return rc;
+    };
+    auto lnorm = [&](const NormW& w, const half_t* a, half_t* o) -> int {
+        return r.dry ? 0 : launch_swin_layernorm(a, w.g, w.b, o, (int64_t)M, n.C, Cp, 1e-5f, r.s);
+    };
+    // everything between qkv and proj
+    auto attention = [&](const sdmi_dat::Block& bk) -> int {
+        if (r.dry) return 0;
+        const half_t* v = qkv + 2 * Sp;
+        if (bk.spatial) {
+            DatAttnP a{};
+            a.qkv = qkv; a.bias0 = bk.tab0; a.bias1 = bk.tab1; a.out = att; a.B = B; a.H = H; a.W = W; a.heads = heads; a.D = n.D;
+            a.ldq = 3 * Sp; a.ldo = Sp; a.s0 = n.cfg.split0; a.s1 = n.cfg.split1; a.shifted = bk.shifted ? 1 : 0; a.scale = 1.0f / sqrtf((float)n.D);
+            TRY(launch_dat_window_attention(a, r.s));
+        } else {
+            TRY(launch_dat_channel_gram(qkv, gram, B, N, heads, 3 * Sp, r.s));
+            TRY(launch_dat_channel_softmax(gram, bk.temperature, amat, B, N, heads, n.D, r.s));
+            GemmP g{};                                        // att[b] = v[b] A[b]^T: a batched 1x1 GEMM with per-image weights
+            g.a0 = v; g.c0 = Sp; g.cin = Sp; g.lda0 = 3 * Sp;
+            g.w = amat; g.ldw = Sp;
+            g.out = att;
+            g.Hi = N; g.Wi = 1; g.Ho = N; g.Wo = 1; g.taps = 1; g.stride = 1;
+            g.M = N; g.N = Sp; g.K = Sp; g.ldo = Sp; g.rows_per_batch = N; g.n_real = Sp;
+            g.alpha = 1.f;
+            g.a_bs = (long)N * 3 * Sp; g.w_bs = (long)Sp * Sp; g.o_bs = (long)N * Sp;
+            TRY(launch_gemm(g, B, r.e->force_generic, r.e->use_glds, r.s));
+        }
+        TRY(launch_dat_dwconv3x3(v, bk.dw_w, bk.dw_b, nullptr, cv, B, H, W, Sp, 3 * Sp, 0, Sp, 0, r.s));
+        const half_t* sop = bk.spatial ? att : cv;            // the spatial MLP's operand; the channel gate is pooled from the other
+        const half_t* top = bk.spatial ? cv : att;
+        TRY(launch_dat_pool_gate(top, bk.ci_w1, bk.ci_b1, bk.ci_w2, bk.ci_b2, pool_ws, cgate, B, N, Sp, n.C8, Sp, r.s));
+        DatAimP m{};
+        m.s = sop; m.t = top; m.cg = cgate; m.w1 = bk.si_w1; m.b1 = bk.si_b1; m.w2 = bk.si_w2; m.b2 = bk.si_b2; m.out = mix;
+        m.rows = (long long)M; m.rows_per_image = N; m.C = Sp; m.C16 = n.C16; m.lds = Sp; m.ldt = Sp; m.ldo = Sp;
+        return launch_dat_aim_combine(m, r.s);
+    };
+    // x2 <- LayerNorm(x2) in place (a lane reads what it then writes), then x1 * dwconv(x2)
+    auto gate = [&](const sdmi_dat::Block& bk) -> int {
+        if (r.dry) return 0;
+        TRY(launch_swin_layernorm(hid + Hh, bk.sgn.g, bk.sgn.b, hid + Hh, (int64_t)M, n.half, 2 * Hh, 1e-5f, r.s));
+        return launch_dat_dwconv3x3(hid + Hh, bk.sg_w, bk.sg_b, hid, gated, B, H, W, Hh, 2 * Hh, 2 * Hh, Hh, 1, r.s);
+    };
+
+    if (!r.dry) TRY(launch_swin_input(in, in_u8, x0, B, H, W, H, W, 64, r.s));
+    TRY(conv(n.first, x0, nullptr, feat));
+    half_t* x = pool[0];
+    std::vector<half_t*> free_ = {pool[1], pool[2], pool[3]};
+    TRY(lnorm(n.rg_norm, feat, x));
+    for (const sdmi_dat::Layer& L : n.layers) {
+        half_t* cur = x;
+        for (const sdmi_dat::Block& bk : L.blocks) {
+            half_t* mid = free_.back(); free_.pop_back();
+            half_t* nxt = free_.back(); free_.pop_back();
+            TRY(lnorm(bk.n1, cur, ln));
+            TRY(conv(bk.qkv, ln, nullptr, qkv));
+            TRY(attention(bk));
+            TRY(conv(bk.proj, mix, cur, mid));
+            TRY(lnorm(bk.n2, mid, ln));
+            TRY(conv(bk.fc1, ln, nullptr, hid, EP_GELU));
+            TRY(gate(bk));
+            TRY(conv(bk.fc2, gated, mid, nxt));
+            free_.push_back(mid);
+            if (cur != x) free_.push_back(cur);
+            cur = nxt;
+        }
+        half_t* y = free_.back(); free_.pop_back();
+        TRY(conv(L.conv, cur, x, y));
+        free_.push_back(x);
+        if (cur != x) free_.push_back(cur);
+        x = y;
+    }
+    TRY(lnorm(n.norm, x, ln));
+    half_t* trunk = free_.back();
+    TRY(conv(n.after, ln, feat, trunk));
+    TRY(conv(n.before, trunk, nullptr, c1));
+    if (!r.dry) TRY(launch_swin_lrelu(c1, (int64_t)(M * 64), 0.01f, r.s));
+    const int f = sc == 3 ? 3 : 2;
+    const half_t* t = c1;
+    int g = 1;                                                // the grid so far: (H g) x (W g)
+    for (int k = 0; k < (sc == 4 ? 2 : 1); ++k) {
+        TRY(conv(n.ps[k], t, nullptr, up[0], 0, g));
+        if (!r.dry) TRY(launch_swin2_pixel_shuffle(up[0], up[1], B, H * g, W * g, f, r.s));
+        t = up[1];
+        g *= f;
+    }
+    if (r.dry) return 0;
+    RrdbP p{};
+    p.in = up[1]; p.w = n.last.w; p.bias = n.last.b; p.out = full;
+    p.B = B; p.H = sc * H; p.W = sc * W; p.cin = 64; p.lda = 64; p.n_real = n.last.cout; p.ep = RRDB_EP_NONE; p.store = RRDB_ST_F32_NCHW;
+    p.alpha = 1.f; p.beta = 1.f;
+    TRY(launch_rrdb_conv(p, n.last.n_pad, r.s));
+    return launch_swin_output(full, out, out_u8, B, H * sc, W * sc, H * sc, W * sc, r.s);
+}
+
+static bool dat_size_ok(const sdmi_dat& n, int B, int H, int W) {
+    if (B <= 0 || H < 1 || W < 1) return false;
+    const long long Mp = (long long)B * rup(H, n.cfg.split1) * rup(W, n.cfg.split1);      // the attention's padded grid
+    const long long widest = std::max<long long>({3ll * n.Sp, 2ll * n.Hh, (long long)n.Cp, 64ll * n.cfg.scale * n.cfg.scale});
+    return Mp * widest < (1ll << 31) - 256;
+}
+
+int64_t dat_scratch_bytes(const sdmi_dat* n, int B, int H, int W) {
+    if (!n || !dat_size_ok(*n, B, H, W)) return 0;
+    return pass_scratch_bytes(n->e, [&](Run& r) { return dat_pass(r, *n, nullptr, 0, B, H, W, nullptr, 0); });
+}
+
+// in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
+// out: [B][3][H s][W s] fp32 NCHW, or (out_u8) uint8 HWC [B][H s][W s][3] = round_half_even(clamp(y, 0, 1) * 255).
+int dat_run(sdmi_dat* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s) {
+    SDMI_REQUIRE(n && in && out, "null argument");
+    sdmi_engine* e = n->e;
+    SDMI_REQUIRE(B > 0 && H >= 1 && W >= 1, "empty image");
+    SDMI_REQUIRE(dat_size_ok(*n, B, H, W), "image too large: every intermediate tensor must stay below 2^31 elements");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    return run_pass(e, s, [&](Run& r) { return dat_pass(r, *n, in, in_u8, B, H, W, out, out_u8); });
+}
+
 }  // namespace sdmi
 
 sdmi_net::~sdmi_net() {
@@ -2945,11 +3231,12 @@ sdmi_engine::~sdmi_engine() {
 
 // The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units; there the upscalers'
 // and the cross-attention chain's kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip, swinir.hip,
-// scunet.hip and xattn_chain.hip on their own (build.sh).
+// scunet.hip, dat.hip and xattn_chain.hip on their own (build.sh).
 #ifndef __HIP__
 #include "rrdb.hip"
 #include "compact.hip"
 #include "swinir.hip"
 #include "scunet.hip"
+#include "dat.hip"
 #include "xattn_chain.hip"
 #endif

@@ -306,6 +306,35 @@ struct sdmi_swin2sr : sdmi_swinir {
     sdmi_swin2sr_config cfg2{};
 };
 
+// DAT upscaler (pixelshuffle tail, 1conv groups): the linears and trunk convs as GEMM weights (token rows C rounded up to 64 wide; qkv's
+// output, proj's input and everything between in 32-wide head slots, Sp = 32 heads columns; fc1's two halves each rounded up to 64), the
+// fp32 operands of the dat.hip launches in the same layouts, the 64-channel tail as Swin2SR's.  Activations come from the owning engine's
+// arena; the net is immutable after sdmi_dat_create.
+struct sdmi_dat : sdmi_net {
+    struct Block {
+        bool spatial = true, shifted = false;
+        sdmi::NormW n1, n2, sgn;              // sgn: ffn.sg.norm over ffn_hidden / 2
+        sdmi::ConvW qkv, proj, fc1, fc2;
+        float* tab0 = nullptr;                // spatial: the two bias tables
+        float* tab1 = nullptr;
+        float* temperature = nullptr;         // channel: [heads]
+        float *dw_w = nullptr, *dw_b = nullptr;                           // [9][Sp], [Sp]
+        float *ci_w1 = nullptr, *ci_b1 = nullptr, *ci_w2 = nullptr, *ci_b2 = nullptr;   // [C8][Sp], [C8], [Sp][C8], [Sp]
+        float *si_w1 = nullptr, *si_b1 = nullptr, *si_w2 = nullptr;       // [C16][Sp], [C16], [C16]
+        float si_b2 = 0.f;
+        float *sg_w = nullptr, *sg_b = nullptr;                           // [9][Hh], [Hh]
+    };
+    struct Layer {
+        std::vector<Block> blocks;
+        sdmi::ConvW conv;
+    };
+    sdmi_dat_config cfg{};
+    int C = 0, Cp = 0, D = 0, Sp = 0, half = 0, Hh = 0, C8 = 0, C16 = 0;      // half = ffn_hidden / 2, Hh = half rounded up to 64
+    sdmi::ConvW first, after, before, ps[2], last;
+    sdmi::NormW rg_norm, norm;
+    std::vector<Layer> layers;
+};
+
 // ScuNET (Swin-Conv-UNet, dim 64): per ConvTransBlock the two 1x1 convs as GEMM weights, the 3x3 pair as rrdb_conv (widths 32 / 64) or
 // GEMM (128 / 256) weights, and the transformer Block either as one scu_block pack (trans_dim 32 / 64) or as the GEMM weights of the
 // swin_layernorm + conv_gemm + swin_window_attn route (128 / 256).  Activations come from the owning engine's arena; the net is immutable

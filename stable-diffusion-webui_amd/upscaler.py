@@ -6,7 +6,7 @@ up in (modules/images.py:276, modules/modelloader.py:136), the ``Upscaler.upscal
 the three built-in PIL scalers (None / Lanczos / Nearest, modules/upscaler.py:107-154).  The RRDBNet family (ESRGAN, Real-ESRGAN) and the
 compact Real-ESRGAN models (SRVGGNetCompact: General 4xV3, General WDN 4xV3, AnimeVideo) run on the engine (``UpscalerESRGAN`` /
 ``register_esrgan`` below, csrc/rrdb.hip and csrc/compact.hip), and so do the SwinIR models with the nearest+conv upsampler
-(``SwinIRNet``) and the Swin2SR models (``Swin2SRNet``; both csrc/swinir.hip) and the ScuNET models (``ScuNETNet``, csrc/scunet.hip); other model upscalers register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)``
+(``SwinIRNet``) and the Swin2SR models (``Swin2SRNet``; both csrc/swinir.hip) and the ScuNET models (``ScuNETNet``, csrc/scunet.hip) and the DAT models (``DATNet``, csrc/dat.hip); other model upscalers register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)``
 is called as in the reference.
 """
 from __future__ import annotations
@@ -532,13 +532,174 @@ def parse_scunet_state_dict(sd):
     return np.ascontiguousarray(np.concatenate(parts)), dict(depths=tuple(depths), dim=dim, scale=1)
 
 
+DAT_MARKS = ("before_RG.1.weight", "layers.0.blocks.0.attn.attns.0.pos.pos_proj.weight")
+DAT_SPLITS = {15 * 31: (8, 16), 15 * 63: (8, 32)}           # rows of attns.0.rpe_biases = (2 s0 - 1)(2 s1 - 1)
+_BN_EPS = np.float32(1e-5)
+
+
+def _ln_f32(x, g, b):
+    mu = x.mean(axis=-1, keepdims=True, dtype=np.float32)
+    var = ((x - mu) ** 2).mean(axis=-1, keepdims=True, dtype=np.float32)
+    return ((x - mu) / np.sqrt(var + np.float32(1e-5)) * g + b).astype(np.float32)
+
+
+def dat_position_bias(pos, hsp, wsp):
+    """The dynamic position bias of one attention branch (DynamicPosBias, residual = False) evaluated in fp32 at the (2 hsp - 1)(2 wsp - 1)
+    integer offsets (dy, dx), dy in [1 - hsp, hsp - 1] outer, dx in [1 - wsp, wsp - 1] inner -> [offsets, heads / 2].  pos: name ->
+    fp32 array for pos_proj, pos1.0, pos1.2, pos2.0, pos2.2, pos3.0, pos3.2 (.weight / .bias): pos3(pos2(pos1(pos_proj(r)))), every posK
+    a LayerNorm, ReLU, Linear."""
+    dy, dx = np.meshgrid(np.arange(1 - hsp, hsp, dtype=np.float32), np.arange(1 - wsp, wsp, dtype=np.float32), indexing="ij")
+    x = np.stack([dy.ravel(), dx.ravel()], axis=1).astype(np.float32)
+    x = (x @ pos["pos_proj.weight"].T + pos["pos_proj.bias"]).astype(np.float32)
+    for k in ("pos1", "pos2", "pos3"):
+        x = np.maximum(_ln_f32(x, pos[k + ".0.weight"], pos[k + ".0.bias"]), np.float32(0))
+        x = (x @ pos[k + ".2.weight"].T + pos[k + ".2.bias"]).astype(np.float32)
+    return np.ascontiguousarray(x)
+
+
+def dat_bn_fold(w, b, gamma, beta, mean, var):
+    """Conv (weight [O, ...], bias [O]) followed by an eval-mode BatchNorm2d (eps 1e-5) as one conv, in fp32 -> (weight, bias)."""
+    w, b, gamma, beta, mean, var = (np.asarray(t, dtype=np.float32) for t in (w, b, gamma, beta, mean, var))
+    s = (gamma / np.sqrt(var + _BN_EPS)).astype(np.float32)
+    return (w * s.reshape((-1,) + (1,) * (w.ndim - 1))).astype(np.float32), ((b - mean) * s + beta).astype(np.float32)
+
+
+def parse_dat_state_dict(sd):
+    """Checkpoint state dict of a DAT network (basicsr's dat_arch.py with upsampler 'pixelshuffle' and resi_connection '1conv': the
+    webui's "DAT x2" / "DAT x3" / "DAT x4", DAT-S, DAT-2) -> (blob, config): the engine's weight blob (fp32, in the order include/sdmi.h
+    documents at sdmi_dat_config, every tensor in the checkpoint's channel order; the dynamic position bias of each branch evaluated to
+    its table, every BatchNorm folded into the conv in front of it, both in fp32) and config = dict(embed_dim, depths, num_heads, split,
+    ffn_hidden, scale), all read off the shapes: the split from attns.0.rpe_biases (or relative_position_index), the scale from the
+    upsample.* convs.  The buffers rpe_biases / relative_position_index / attn_mask_* hold nothing the engine reads.  Host only.  Raises
+    ValueError, naming the reason, on what the engine's kernels are not built for."""
+    sd = _unwrap_state_dict(sd)
+    if any(k not in sd for k in DAT_MARKS) or "conv_first.weight" not in sd:
+        raise ValueError(f"not a DAT checkpoint: no {' / '.join(k for k in DAT_MARKS + ('conv_first.weight',) if k not in sd)}")
+    if "layers.0.conv.0.weight" in sd or "conv_after_body.0.weight" in sd:
+        raise ValueError("DAT resi_connection '3conv' (layers.0.conv.0): the engine runs the 1conv models")
+    if "upsample.0.weight" not in sd:
+        raise ValueError("DAT checkpoint lacks upsample.0.weight")
+    if "conv_before_upsample.0.weight" not in sd:
+        raise ValueError("DAT upsampler 'pixelshuffledirect' (DAT-light: no conv_before_upsample): the engine runs the pixelshuffle models")
+    c, in_ch = int(sd["conv_first.weight"].shape[0]), int(sd["conv_first.weight"].shape[1])
+    if in_ch != 3 or tuple(sd["conv_first.weight"].shape[2:]) != (3, 3):
+        raise ValueError(f"DAT conv_first takes {in_ch} input channels: expected 3")
+    layers = sorted({int(m.group(1)) for k in sd for m in [re.match(r"layers\.(\d+)\.blocks\.0\.attn\.qkv\.weight$", k)] if m})
+    if not layers or layers != list(range(len(layers))) or len(layers) > 16:
+        raise ValueError(f"DAT layers are not 0..n-1 with 1 <= n <= 16: {layers}")
+    depths = []
+    for i in layers:
+        blocks = sorted({int(m.group(1)) for k in sd for m in [re.match(rf"layers\.{i}\.blocks\.(\d+)\.attn\.qkv\.weight$", k)] if m})
+        if blocks != list(range(len(blocks))):
+            raise ValueError(f"DAT layers.{i}: blocks are not 0..n-1: {blocks}")
+        depths.append(len(blocks))
+    b0 = "layers.0.blocks.0."
+    temps = [v for k, v in sd.items() if k.endswith("attn.temperature")]
+    if temps:
+        heads = int(temps[0].shape[0])
+    elif b0 + "attn.attns.0.pos.pos3.2.weight" in sd:
+        heads = 2 * int(sd[b0 + "attn.attns.0.pos.pos3.2.weight"].shape[0])
+    else:
+        raise ValueError(f"DAT checkpoint lacks {b0}attn.attns.0.pos.pos3.2.weight")
+    if heads % 2:
+        raise ValueError(f"DAT num_heads = {heads} is odd: half of the heads go to each window branch")
+    if heads < 2 or c % heads or c // heads > 32:
+        raise ValueError(f"DAT head_dim = {c}/{heads} = {c / max(heads, 1):g}: the engine's attention kernels are built for head_dim <= 32")
+    if 32 * heads > 512 or c < 16:
+        raise ValueError(f"DAT embed_dim {c} with {heads} heads: the engine runs 16 <= embed_dim and at most 16 heads")
+    rpe, rpi = sd.get(b0 + "attn.attns.0.rpe_biases"), sd.get(b0 + "attn.attns.0.relative_position_index")
+    if rpe is not None:
+        split = DAT_SPLITS.get(int(rpe.shape[0]))
+        found = f"{int(rpe.shape[0])} rows of rpe_biases"
+    elif rpi is not None:
+        split = {128: (8, 16), 256: (8, 32)}.get(int(rpi.shape[0]))
+        found = f"{int(rpi.shape[0])} tokens per window"
+    else:
+        raise ValueError(f"DAT checkpoint lacks {b0}attn.attns.0.rpe_biases")
+    if split is None:
+        raise ValueError(f"DAT split_size with {found}: the engine's window kernel is built for (8, 16) and (8, 32)")
+    if b0 + "ffn.fc1.weight" not in sd:
+        raise ValueError(f"DAT checkpoint lacks {b0}ffn.fc1.weight")
+    hidden = int(sd[b0 + "ffn.fc1.weight"].shape[0])
+    if hidden % 2:
+        raise ValueError(f"DAT ffn hidden width {hidden} is odd: the feed-forward gate splits it in two")
+    if int(sd["conv_before_upsample.0.weight"].shape[0]) != 64:
+        raise ValueError(f"DAT num_feat = {int(sd['conv_before_upsample.0.weight'].shape[0])}: the engine's tail kernels are built for 64")
+    n0 = int(sd["upsample.0.weight"].shape[0])
+    scale = {(256, False): 2, (576, False): 3, (256, True): 4}.get((n0, "upsample.2.weight" in sd))
+    if scale is None or any(f"upsample.{k}.weight" in sd for k in (4, 6)):
+        raise ValueError(f"DAT pixelshuffle with upsample.0 writing {n0} channels"
+                         f"{' and further steps' if 'upsample.2.weight' in sd else ''}: the engine runs scales 2, 3 and 4")
+    half, c8, c16, hh = hidden // 2, c // 8, c // 16, heads // 2
+    pos_dim = (c // 2 // 4) // 4
+    parts = []
+
+    def wb(name, shape):
+        parts.extend(_swin_wb(sd, "DAT", name, shape))
+
+    def tensor(name, shape=None):
+        if name not in sd:
+            raise ValueError(f"DAT checkpoint lacks {name}")
+        return _swin_tensor(sd, "DAT", name, shape).reshape(shape if shape is not None else tuple(sd[name].shape))
+
+    def folded(conv, bn, shape):
+        """conv (weight of this shape, bias) with the BatchNorm `bn` folded in."""
+        o = shape[0]
+        w, b = dat_bn_fold(tensor(conv + ".weight", shape), tensor(conv + ".bias", (o,)), tensor(bn + ".weight", (o,)),
+                           tensor(bn + ".bias", (o,)), tensor(bn + ".running_mean", (o,)), tensor(bn + ".running_var", (o,)))
+        parts.extend([w.ravel(), b])
+
+    def bias_table(stem, hsp, wsp):
+        shapes = {"pos_proj.weight": (pos_dim, 2), "pos_proj.bias": (pos_dim,)}
+        for k, out in (("pos1", pos_dim), ("pos2", pos_dim), ("pos3", hh)):
+            shapes.update({k + ".0.weight": (pos_dim,), k + ".0.bias": (pos_dim,), k + ".2.weight": (out, pos_dim), k + ".2.bias": (out,)})
+        parts.append(dat_position_bias({k: tensor(stem + k, s) for k, s in shapes.items()}, hsp, wsp).ravel())
+
+    wb("conv_first", (c, 3, 3, 3))
+    wb("before_RG.1", (c,))
+    for i, depth in enumerate(depths):
+        for j in range(depth):
+            b = f"layers.{i}.blocks.{j}."
+            wb(b + "norm1", (c,))
+            wb(b + "attn.qkv", (3 * c, c))
+            if j % 2 == 0:
+                bias_table(b + "attn.attns.0.pos.", split[0], split[1])
+                bias_table(b + "attn.attns.1.pos.", split[1], split[0])
+            else:
+                parts.append(tensor(b + "attn.temperature", (heads, 1, 1)).ravel())
+            folded(b + "attn.dwconv.0", b + "attn.dwconv.1", (c, 1, 3, 3))
+            folded(b + "attn.channel_interaction.1", b + "attn.channel_interaction.2", (c8, c, 1, 1))
+            wb(b + "attn.channel_interaction.4", (c, c8, 1, 1))
+            folded(b + "attn.spatial_interaction.0", b + "attn.spatial_interaction.1", (c16, c, 1, 1))
+            wb(b + "attn.spatial_interaction.3", (1, c16, 1, 1))
+            wb(b + "attn.proj", (c, c))
+            wb(b + "norm2", (c,))
+            wb(b + "ffn.fc1", (hidden, c))
+            wb(b + "ffn.sg.norm", (half,))
+            wb(b + "ffn.sg.conv", (half, 1, 3, 3))
+            wb(b + "ffn.fc2", (c, half))
+        wb(f"layers.{i}.conv", (c, c, 3, 3))
+    wb("norm", (c,))
+    wb("conv_after_body", (c, c, 3, 3))
+    wb("conv_before_upsample.0", (64, c, 3, 3))
+    wb("upsample.0", (n0, 64, 3, 3))
+    if scale == 4:
+        wb("upsample.2", (256, 64, 3, 3))
+    wb("conv_last", (3, 64, 3, 3))
+    config = dict(embed_dim=c, depths=tuple(depths), num_heads=heads, split=split, ffn_hidden=hidden, scale=scale)
+    return np.ascontiguousarray(np.concatenate(parts)), config
+
+
 def upscaler_family(sd):
-    """"scunet" | "swin2sr" | "swinir" | "rrdb" | "compact" by the key layout: m_head.0.weight together with the first block's
+    """"dat" | "scunet" | "swin2sr" | "swinir" | "rrdb" | "compact" by the key layout: before_RG.1.weight together with the first block's
+    attns.0.pos.pos_proj.weight marks a DAT network (no other family has either key); m_head.0.weight together with the first block's
     relative_position_params marks a ScuNET; the first block's attn.logit_scale marks a Swin2SR network (it has an attn.qkv.weight
     too, so this test comes before the next); the first block's attn.qkv.weight marks a SwinIR network (it has a conv_first.weight
     too, so this test comes before the next); conv_first.weight / model.0.weight mark an RRDBNet, a 4-d body.0.weight without them a
     compact network.  Anything else counts as "rrdb" and gets that loader's refusal."""
     keys = _unwrap_state_dict(sd)
+    if all(k in keys for k in DAT_MARKS):
+        return "dat"
     if all(k in keys for k in SCUNET_MARKS):
         return "scunet"
     if SWIN2SR_MARK in keys:
@@ -552,11 +713,12 @@ def upscaler_family(sd):
 
 def parse_upscaler_state_dict(sd):
     """The dispatcher over the checkpoints the engine runs -> ("rrdb", parse_esrgan_state_dict(sd)), ("compact",
-    parse_compact_state_dict(sd)), ("swinir", (blob, config, scale)), ("swin2sr", (blob, config, scale)) or ("scunet", (blob, config, 1));
-    the scale is the last member of each tuple."""
+    parse_compact_state_dict(sd)), ("swinir", (blob, config, scale)), ("swin2sr", (blob, config, scale)), ("scunet", (blob, config, 1)) or
+    ("dat", (blob, config, scale)); the scale is the last member of each tuple."""
     family = upscaler_family(sd)
-    if family in ("swinir", "swin2sr", "scunet"):
-        blob, config = {"swinir": parse_swinir_state_dict, "swin2sr": parse_swin2sr_state_dict, "scunet": parse_scunet_state_dict}[family](sd)
+    if family in ("swinir", "swin2sr", "scunet", "dat"):
+        blob, config = {"swinir": parse_swinir_state_dict, "swin2sr": parse_swin2sr_state_dict, "scunet": parse_scunet_state_dict,
+                        "dat": parse_dat_state_dict}[family](sd)
         return family, (blob, config, config["scale"])
     return family, (parse_compact_state_dict if family == "compact" else parse_esrgan_state_dict)(sd)
 
@@ -751,9 +913,31 @@ class ScuNETNet(_EngineNet):
         return blob, (ctypes.byref(cfg),)
 
 
+class DATNet(_EngineNet):
+    """One DAT network (pixelshuffle upsampler, 1conv groups) resident on an engine (sdmi_dat_*).  Any H, W >= 1: the network has no
+    padding of its own, the attention windows pad by index on the device.  The arena holds the token tensors, the slot-layout q | k | v,
+    attention, conv and mix rows, the feed-forward rows and the (H s) x (W s) x 64 tail."""
+    _abi = "sdmi_dat"
+    _noun = "DAT"
+    _zero_need_is_a_refusal = True
+
+    def _parse(self, state_dict):
+        import ctypes
+        from . import _lib
+        blob, self.config = parse_dat_state_dict(state_dict)
+        self.scale = self.config["scale"]
+        cfg = _lib.DATConfigC()
+        cfg.embed_dim, cfg.num_layers, cfg.num_heads = self.config["embed_dim"], len(self.config["depths"]), self.config["num_heads"]
+        cfg.split0, cfg.split1 = self.config["split"]
+        cfg.ffn_hidden, cfg.scale = self.config["ffn_hidden"], self.scale
+        for i, d in enumerate(self.config["depths"]):
+            cfg.depths[i] = d
+        return blob, (ctypes.byref(cfg),)
+
+
 def make_upscaler_net(state_dict, device=0, engine=None):
-    """EsrganNet, CompactNet, SwinIRNet, Swin2SRNet or ScuNETNet, by the checkpoint's key layout (upscaler_family)."""
-    cls = {"compact": CompactNet, "swinir": SwinIRNet, "swin2sr": Swin2SRNet, "scunet": ScuNETNet}.get(upscaler_family(state_dict), EsrganNet)
+    """EsrganNet, CompactNet, SwinIRNet, Swin2SRNet, ScuNETNet or DATNet, by the checkpoint's key layout (upscaler_family)."""
+    cls = {"compact": CompactNet, "swinir": SwinIRNet, "swin2sr": Swin2SRNet, "scunet": ScuNETNet, "dat": DATNet}.get(upscaler_family(state_dict), EsrganNet)
     return cls(state_dict, device=device, engine=engine)
 
 
@@ -766,7 +950,8 @@ class UpscalerESRGAN(Upscaler):
     for the same VRAM reason as ESRGAN_tile), the padding to the window size done on the device; Swin2SR checkpoints (what the extension
     builds from swinir_model_arch_v2.py) run as Swin2SRNet the same way.  ScuNET checkpoints run as ScuNETNet:
     extensions-builtin/ScuNET's UpscalerScuNET.do_upscale with the image in one tile; the result has the input's size and the driver
-    loop of Upscaler.upscale fits it with Lanczos."""
+    loop of Upscaler.upscale fits it with Lanczos.  DAT checkpoints (pixelshuffle, 1conv) run as DATNet: modules/dat_model.py's
+    UpscalerDAT.do_upscale with the image in one tile (DAT_tile exists for the same VRAM reason)."""
     name = "ESRGAN"
 
     def __init__(self, device=0, engine=None):
@@ -805,7 +990,7 @@ def register_esrgan(paths, device=0, engine=None):
     """Append one ``UpscalerData(name, path, scaler, scale)`` per checkpoint to shared.sd_upscalers (after the built-ins, which are
     installed first if the list is empty): `paths` is a {name: path} mapping or a list of paths (name = the file's stem), so
     hr_upscaler="R-ESRGAN 4x+" and opts.upscaler_for_img2img resolve through _resize_to.  RRDBNet, compact (SRVGGNetCompact), SwinIR,
-    Swin2SR and ScuNET checkpoints may be mixed; the scale is read from the checkpoint.
+    Swin2SR, ScuNET and DAT checkpoints may be mixed; the scale is read from the checkpoint.
     engine: see UpscalerESRGAN (all entries of one call share one scaler object and so one engine)."""
     if not shared.sd_upscalers:
         shared.sd_upscalers = builtin_upscalers()

@@ -742,6 +742,16 @@ def install_scunet_hook(webui_shared, device_index: int = 0):
     return _install_whole_image_hook(webui_shared, device_index, "UpscalerScuNET")
 
 
+def install_dat_hook(webui_shared, device_index: int = 0):
+    """Point the webui's DAT scaler objects (modules/dat_model.py: "DAT x2", "DAT x3", "DAT x4") at the engine: install_swinir_hook for
+    the entries of ``webui_shared.sd_upscalers`` whose scaler class is UpscalerDAT.  ``do_upscale(img, path)`` runs the checkpoint as
+    sdmi_dat_run on the image whole instead of as a torch module in DAT_tile tiles.  The same fall-back rules: a URL that is not on disk
+    yet, a checkpoint the loader refuses (pixelshuffledirect, 3conv, head dim > 32, an odd head count, another split, num_feat other
+    than 64) or that fails to load or pack, and an image too large for the arena stay on the stock path.  Idempotent.  Returns the names
+    of the hooked entries."""
+    return _install_whole_image_hook(webui_shared, device_index, "UpscalerDAT")
+
+
 def _install_whole_image_hook(webui_shared, device_index, scaler_class):
     from . import upscaler as amd_upscaler
     engine_scaler = amd_upscaler.UpscalerESRGAN(device_index)
