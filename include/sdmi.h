@@ -148,6 +148,37 @@ enum {
 int sdmi_conv_gemm(const sdmi_conv_desc* d, void* stream);
 int64_t sdmi_conv_splitk_workspace_bytes(int M, int N, int K, int batch);
 
+/* TEST ENTRY (tests and timing tools; the engine fills these fields itself): sdmi_conv_gemm plus the epilogue forms the public
+ * descriptor does not carry.  x == NULL is exactly sdmi_conv_gemm(d, stream).  Nothing here touches a process-wide knob.
+ *   stats_out / stats_cpg  GroupNorm statistics of the stored tensor: per (image b, chunk of BM rows, group of stats_cpg channels) the
+ *                          mean and the centred sum of squares of the fp16-rounded outputs (of hi + lo with out_lo), fp32, at
+ *                          stats_out[((b * stats_nchunk + chunk) * (N / stats_cpg) + g) * 2 + {0, 1}].  stats_nchunk is written back:
+ *                          rows per image / BM of the tile that ran, or 0 when the launch could not produce them (nothing is written then).
+ *   lnp_out                LayerNorm row partials: per row m and column tile t the sum and the sum of squares of the fp16-rounded
+ *                          outputs, at lnp_out[(m * lnp_np + t) * 2 + {0, 1}].  lnp_np is written back (N / BN, or 0: nothing written).
+ *   ln_stats, ln_s, ...    with flag SDMI_EP_LNFOLD in d->flags: A is the un-normalised input of a LayerNorm folded into the weights
+ *                          (sdmi_ln_fold_weights), out[m][n] = rstd[m] * (acc[m][n] - mean[m] * ln_s[n]) + bias[n].  ln_np == 0: ln_stats
+ *                          holds (mean, rstd) per row (sdmi_ln_rowstats); ln_np > 0: [M][ln_np][2] row partials as lnp_out leaves them,
+ *                          finished with ln_inv_c = 1 / C and ln_eps.
+ *   out_lo / resid_lo      (hi, lo) stream tensors: out_lo receives fp16(x - fp16(x)) of every stored x in the layout of out; resid_lo
+ *                          is added with resid, in its layout.
+ *   bias_scale             the bias is added as bias * bias_scale (0 = 1).   gate: a device int; the launch is a no-op when it holds 0.
+ * Refused before anything is launched, next to what sdmi_conv_gemm refuses: stats_out with stats_cpg <= 0 or N % stats_cpg != 0, or
+ * stats_bytes < B * 64 * (N / stats_cpg) * 8; lnp_out with lnp_bytes < M * (N / 64) * 8; SDMI_EP_LNFOLD without ln_stats / ln_s, with
+ * ln_stats_bytes < M * max(1, ln_np) * 8 or ln_s_bytes < N * 4; out_lo / resid_lo with out_lo_bytes / resid_lo_bytes smaller than
+ * ((M - 1) * ldo + N) * 2 / ((M - 1) * ldr + N) * 2; resid_lo without resid; either pair or SDMI_EP_LNFOLD with batch > 1. */
+enum { SDMI_EP_LNFOLD = 0x4000 };
+typedef struct sdmi_gemm_extras {
+    float* stats_out; int32_t stats_cpg; int32_t stats_nchunk;
+    const float* ln_stats; const float* ln_s; int32_t ln_np; float ln_inv_c, ln_eps;
+    float* lnp_out; int32_t lnp_np;
+    float bias_scale;
+    void* out_lo; const void* resid_lo;
+    const int32_t* gate;
+    int64_t stats_bytes, lnp_bytes, ln_stats_bytes, ln_s_bytes, out_lo_bytes, resid_lo_bytes;
+} sdmi_gemm_extras;
+int sdmi_conv_gemm_ex(const sdmi_conv_desc* d, sdmi_gemm_extras* x, void* stream);
+
 /* Repack helpers (device side, run once at load): OIHW fp16/fp32 conv weight -> [O][ky*3+kx][I(+pad)] fp16. */
 int sdmi_pack_conv_weight(const void* w_oihw, int dtype, void* out_f16, int O, int I, int kh, int kw,
                           int O_pad, int I_pad, int geglu, void* stream);
@@ -163,6 +194,24 @@ int64_t sdmi_groupnorm_workspace_bytes(int B, int HW, int groups);
 /* LayerNorm over the last dim of [rows, C] fp16 (fp32 statistics, eps 1e-5). */
 int sdmi_layernorm(const void* x, const void* gamma_f32, const void* beta_f32, void* out_f16,
                    int64_t rows, int C, float eps, void* stream);
+
+/* TEST ENTRIES (tests and timing tools) for the norm forms only the engine launches.
+ * sdmi_groupnorm_ex: sdmi_groupnorm with pre_nchunk > 0 — the workspace already holds (mean, centred sum of squares) fp32
+ * [B][pre_nchunk][groups][2] of HW / pre_nchunk rows each, as sdmi_conv_gemm_ex's stats_out leaves them, and only the apply pass runs
+ * (pre_nchunk > 64, negative, or not dividing HW is refused; pre_nchunk == 0 runs the ordinary statistics pass, as sdmi_groupnorm does)
+ * — and with x0_lo / x1_lo, the lo halves of (hi, lo) input pairs, or NULL.
+ * sdmi_ln_rowstats: (mean, rstd) fp32 [rows][2] of x fp16 [rows][C] (C % 8 == 0, C <= 2048).
+ * sdmi_ln_fold_weights: wf[n][k] = fp16(w[n][k] * gamma[k]) for k < C and 0 up to K, s_out[n] = sum_k wf[n][k] (fp32),
+ * c_out[n] = sum_k beta[k] * w[n][k] + (bias ? bias[n] : 0); w and wf fp16 [n_rows][K], K >= C.  The product w * gamma (exact in 35 bits)
+ * reaches fp16 in ONE rounding on gfx950, where the multiply and the conversion compile to one mixed-precision instruction; a build that
+ * rounds to fp32 first (the host emulation) stores another fp16 neighbour for about one element in 2^13.  s_out is the sum of the wf
+ * actually stored, so either way the folded epilogue subtracts exactly what the matrix core accumulated. */
+int sdmi_groupnorm_ex(const void* x0, const void* x1, int c0, int c1, const void* gamma_f32, const void* beta_f32,
+                      void* out_f16, int B, int HW, int groups, float eps, int silu,
+                      void* workspace_f32, int64_t workspace_bytes, int pre_nchunk, const void* x0_lo, const void* x1_lo, void* stream);
+int sdmi_ln_rowstats(const void* x, void* stats_f32, int64_t rows, int C, float eps, void* stream);
+int sdmi_ln_fold_weights(const void* w, const void* gamma_f32, const void* beta_f32, const void* bias_or_null, void* wf, void* s_out,
+                         void* c_out, int n_rows, int K, int C, void* stream);
 
 /* The feed-forward chain of a BasicTransformerBlock as one launch (csrc/rowchain.hip; row width C = 320, rows % 128 == 0).  It
  * replaces, for the ff third of ldm's BasicTransformerBlock._forward as the webui runs it (modules/sd_hijack_unet.py:83-102), the launch

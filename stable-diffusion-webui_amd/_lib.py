@@ -15,6 +15,7 @@ F16, F32 = 0, 1
 EP_OUT_F32, EP_GEGLU, EP_NCHW, EP_BIAS_ROW = 1, 2, 4, 8
 EP_TRANSPOSE = 64
 EP_WRAP = 128
+EP_LNFOLD = 0x4000       # sdmi_conv_gemm_ex only
 RRDB_EP_NONE, RRDB_EP_LRELU, RRDB_EP_RES1, RRDB_EP_RES2, RRDB_EP_RELU = 0, 1, 2, 3, 4
 RRDB_ST_F16, RRDB_ST_F32_NCHW, RRDB_ST_U8_HWC = 0, 1, 2
 COMPACT_EP_NONE, COMPACT_EP_PRELU, COMPACT_EP_TAIL = 0, 1, 2
@@ -36,6 +37,18 @@ class ConvDesc(C.Structure):
         ("a_bs", C.c_int64), ("w_bs", C.c_int64), ("o_bs", C.c_int64), ("r_bs", C.c_int64),
         ("force_generic", C.c_int32), ("reserved", C.c_int32),
         ("splitk_workspace", C.c_void_p), ("splitk_workspace_bytes", C.c_int64),
+    ]
+
+
+class GemmExtras(C.Structure):
+    """include/sdmi.h sdmi_gemm_extras (test entry sdmi_conv_gemm_ex); its leading fields are tests/hostemu/emu.cpp emu_gemm_extras."""
+    _fields_ = [
+        ("stats_out", C.c_void_p), ("stats_cpg", C.c_int32), ("stats_nchunk", C.c_int32),
+        ("ln_stats", C.c_void_p), ("ln_s", C.c_void_p), ("ln_np", C.c_int32), ("ln_inv_c", C.c_float), ("ln_eps", C.c_float),
+        ("lnp_out", C.c_void_p), ("lnp_np", C.c_int32), ("bias_scale", C.c_float),
+        ("out_lo", C.c_void_p), ("resid_lo", C.c_void_p), ("gate", C.c_void_p),
+        ("stats_bytes", C.c_int64), ("lnp_bytes", C.c_int64), ("ln_stats_bytes", C.c_int64), ("ln_s_bytes", C.c_int64),
+        ("out_lo_bytes", C.c_int64), ("resid_lo_bytes", C.c_int64),
     ]
 
 
@@ -165,12 +178,16 @@ _SIGS = {
     "sdmi_attention_vt": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "sdmi_attention_vt_ex": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp]),
     "sdmi_conv_gemm": (_i, [C.POINTER(ConvDesc), _vp]),
+    "sdmi_conv_gemm_ex": (_i, [C.POINTER(ConvDesc), C.POINTER(GemmExtras), _vp]),
     "sdmi_conv_splitk_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "sdmi_bench_conv_gemm": (_i, [C.POINTER(ConvDesc), _i, C.POINTER(C.c_float), _vp]),
     "sdmi_pack_conv_weight": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "sdmi_groupnorm": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _i64, _vp]),
     "sdmi_groupnorm_workspace_bytes": (_i64, [_i, _i, _i]),
     "sdmi_layernorm": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _f, _vp]),
+    "sdmi_groupnorm_ex": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _i64, _i, _vp, _vp, _vp]),
+    "sdmi_ln_rowstats": (_i, [_vp, _vp, _i64, _i, _f, _vp]),
+    "sdmi_ln_fold_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sdmi_rowchain_ff_pack_bytes": (_i64, [_i, _i]),
     "sdmi_rowchain_ff_pack": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "sdmi_rowchain_ff": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _vp]),

@@ -241,6 +241,54 @@ int sdmi_conv_gemm(const sdmi_conv_desc* d, void* stream) {
     API_GUARD_END
 }
 
+// Test entry: sdmi_conv_gemm plus the GemmP fields only the engine fills (include/sdmi.h sdmi_gemm_extras).  Every buffer the extra
+// epilogues write or read is checked against its worst case over the tile families before anything is launched, so a caller's wrong
+// guess about the tile that runs cannot become an out-of-bounds access.
+int sdmi_conv_gemm_ex(const sdmi_conv_desc* d, sdmi_gemm_extras* x, void* stream) {
+    if (!x) return sdmi_conv_gemm(d, stream);
+    API_GUARD_BEGIN
+    GemmP p;
+    if (desc_to_p(d, &p)) return 1;
+    const int batch = d->batch > 0 ? d->batch : 1;
+    const bool hilo = x->out_lo || x->resid_lo;
+    if (x->stats_out) {
+        SDMI_REQUIRE(x->stats_cpg > 0 && p.N % x->stats_cpg == 0, "sdmi_conv_gemm_ex: stats_out needs stats_cpg > 0 and N % stats_cpg == 0");
+        SDMI_REQUIRE(x->stats_bytes >= (int64_t)d->B * 64 * (p.N / x->stats_cpg) * 2 * (int64_t)sizeof(float),
+                     "sdmi_conv_gemm_ex: stats_bytes smaller than B * 64 * (N / stats_cpg) * 8");
+    }
+    SDMI_REQUIRE(!x->lnp_out || x->lnp_bytes >= (int64_t)p.M * ((p.N + 63) / 64) * 2 * (int64_t)sizeof(float),
+                 "sdmi_conv_gemm_ex: lnp_bytes smaller than M * (N / 64) * 8");
+    if (p.flags & EP_LNFOLD) {
+        SDMI_REQUIRE(x->ln_stats && x->ln_s && !hilo, "sdmi_conv_gemm_ex: SDMI_EP_LNFOLD needs ln_stats and ln_s (and no (hi, lo) pair)");
+        SDMI_REQUIRE(x->ln_np >= 0 && x->ln_stats_bytes >= (int64_t)p.M * (x->ln_np > 0 ? x->ln_np : 1) * 2 * (int64_t)sizeof(float),
+                     "sdmi_conv_gemm_ex: ln_stats_bytes smaller than M * max(1, ln_np) * 8");
+        SDMI_REQUIRE(x->ln_s_bytes >= (int64_t)p.N * (int64_t)sizeof(float), "sdmi_conv_gemm_ex: ln_s_bytes smaller than N * 4");
+    }
+    SDMI_REQUIRE(!(p.flags & EP_HILO), "sdmi_conv_gemm_ex: (hi, lo) tensors are given as out_lo / resid_lo, not as a flag");
+    SDMI_REQUIRE(!x->out_lo || x->out_lo_bytes >= ((int64_t)(p.M - 1) * p.ldo + p.N) * (int64_t)sizeof(half_t),
+                 "sdmi_conv_gemm_ex: out_lo_bytes smaller than the footprint of out");
+    SDMI_REQUIRE(!x->resid_lo || p.resid, "sdmi_conv_gemm_ex: resid_lo without resid");
+    SDMI_REQUIRE(!x->resid_lo || x->resid_lo_bytes >= ((int64_t)(p.M - 1) * p.ldr + p.N) * (int64_t)sizeof(half_t),
+                 "sdmi_conv_gemm_ex: resid_lo_bytes smaller than the footprint of resid");
+    SDMI_REQUIRE(batch == 1 || !(hilo || (p.flags & EP_LNFOLD)), "sdmi_conv_gemm_ex: (hi, lo) tensors and SDMI_EP_LNFOLD need batch == 1");
+    p.stats_out = x->stats_out; p.stats_cpg = x->stats_cpg;
+    p.lnp_out = x->lnp_out;
+    if (p.flags & EP_LNFOLD) { p.ln_stats = x->ln_stats; p.ln_s = x->ln_s; p.ln_np = x->ln_np; p.ln_inv_c = x->ln_inv_c; p.ln_eps = x->ln_eps; }
+    if (x->bias_scale != 0.f) p.bias_scale = x->bias_scale;
+    p.gate = x->gate;
+    if (hilo) {                                               // as engine.cpp run_conv hands them over
+        p.flags |= EP_HILO;
+        p.ln_stats = reinterpret_cast<const float*>(x->out_lo);
+        p.ln_s = reinterpret_cast<const float*>(x->resid_lo);
+    }
+    int nchunk = 0, np = 0;
+    const char* env = getenv("SDMI_NO_GLDS");
+    if (launch_gemm(p, batch, d->force_generic == 1, !(env && env[0] == '1') && d->force_generic != 2, (hipStream_t)stream, &nchunk, &np)) return 1;
+    x->stats_nchunk = nchunk; x->lnp_np = np;
+    return 0;
+    API_GUARD_END
+}
+
 int sdmi_bench_conv_gemm(const sdmi_conv_desc* d, int iters, float* ms_out, void* stream) {
     API_GUARD_BEGIN
     GemmP p;
@@ -287,6 +335,38 @@ int sdmi_groupnorm(const void* x0, const void* x1, int c0, int c1, const void* g
 int sdmi_layernorm(const void* x, const void* gamma, const void* beta, void* out, int64_t rows, int C, float eps, void* stream) {
     API_GUARD_BEGIN
     return launch_layernorm((const half_t*)x, (const float*)gamma, (const float*)beta, (half_t*)out, rows, C, eps, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+// Test entries for the norm forms only the engine launches (include/sdmi.h)
+int sdmi_groupnorm_ex(const void* x0, const void* x1, int c0, int c1, const void* gamma, const void* beta, void* out, int B, int HW,
+                      int groups, float eps, int silu, void* ws, int64_t ws_bytes, int pre_nchunk, const void* x0_lo, const void* x1_lo,
+                      void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(x0 && gamma && beta && out && B > 0 && HW > 0 && groups > 0, "sdmi_groupnorm_ex: null pointer or empty problem");
+    SDMI_REQUIRE(ws && ws_bytes >= groupnorm_ws_bytes(B, HW, groups), "groupnorm workspace too small");
+    SDMI_REQUIRE(pre_nchunk >= 0 && pre_nchunk <= 64 && (pre_nchunk == 0 || HW % pre_nchunk == 0),
+                 "sdmi_groupnorm_ex: pre_nchunk must lie in 0 .. 64 and divide HW");
+    SDMI_REQUIRE(ws_bytes >= (int64_t)B * pre_nchunk * groups * 2 * (int64_t)sizeof(float), "sdmi_groupnorm_ex: workspace smaller than the statistics it holds");
+    return launch_groupnorm((const half_t*)x0, (const half_t*)x1, c0, x1 ? c1 : 0, (const float*)gamma, (const float*)beta,
+                            (half_t*)out, B, HW, groups, eps, silu != 0, (float*)ws, (hipStream_t)stream, pre_nchunk,
+                            (const half_t*)x0_lo, x1 ? (const half_t*)x1_lo : nullptr);
+    API_GUARD_END
+}
+
+int sdmi_ln_rowstats(const void* x, void* stats, int64_t rows, int C, float eps, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(x && stats && rows > 0 && C > 0, "sdmi_ln_rowstats: null pointer or empty problem");
+    return launch_ln_rowstats((const half_t*)x, (float*)stats, rows, C, eps, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_ln_fold_weights(const void* w, const void* gamma, const void* beta, const void* bias, void* wf, void* s_out, void* c_out,
+                         int n_rows, int K, int C, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(w && gamma && beta && wf && s_out && c_out, "sdmi_ln_fold_weights: null pointer");
+    return launch_ln_fold_weights((const half_t*)w, (const float*)gamma, (const float*)beta, (const float*)bias, (half_t*)wf,
+                                  (float*)s_out, (float*)c_out, n_rows, K, C, (hipStream_t)stream);
     API_GUARD_END
 }
 
