@@ -213,6 +213,52 @@ int sdmi_ln_rowstats(const void* x, void* stats_f32, int64_t rows, int C, float 
 int sdmi_ln_fold_weights(const void* w, const void* gamma_f32, const void* beta_f32, const void* bias_or_null, void* wf, void* s_out,
                          void* c_out, int n_rows, int K, int C, void* stream);
 
+/* TEST ENTRIES for the elementwise helpers only the engine launches (csrc/elementwise.hip), one launch each.  Every entry refuses, before
+ * anything is launched, null pointers (other than the ones marked "or NULL"), sizes <= 0, dtype codes other than SDMI_F16 / SDMI_F32 and
+ * what is listed with it.
+ * sdmi_small_linear: out[b][n] = act_out(sum_k act_in(a[b][k]) * w[n][k] + bias[n]) + add[b][n]; a fp32 [B][lda], w fp16 [N][K] dense,
+ *   bias fp32 [N] or NULL, add fp32 [B][ldo] or NULL (may be out itself), out fp32 [B][ldo]; act = SiLU where silu_in / silu_out != 0.
+ *   Columns [N, ldo) of out and [K, lda) of a are not touched.  Refused: K % 8, lda % 4, lda < K, ldo < N, a or w off a 16-byte boundary.
+ *   The kernel form follows B, K and N (B <= 16, 16 rows x K fp32 within 96 KB of LDS and N >= 256: activations staged in LDS) and the
+ *   debug knob small_linear_lds (0: always one wave per column); both forms give the same bits.
+ * sdmi_silu_f32: y[i] = x[i] / (1 + expf(-x[i])), fp32, the expression of small_linear's silu_in.
+ * sdmi_timestep_embedding: out fp32 [B][dim] = [cos(t[b] f_j) | sin(t[b] f_j)], f_j = expf(-ln(10000) j / (dim / 2)), j < dim / 2, and a
+ *   last column of 0 where dim is odd; t [B] in t_dtype.  Refused: dim < 2.
+ * sdmi_nchw_to_nhwc: out fp16 [B][HW][cpad] from x [B][C][HW] (x_dtype): channel c = fp16(fp32(x) * scale), or, with mix_w fp32 [C][C]
+ *   (and mix_b fp32 [C] or NULL), fp16(mix_b[o] + sum_c mix_w[o][c] * (x[c] * scale)) accumulated with fmaf in c order; with lo_ch != 0
+ *   channels [C, 2C) = fp16(v - fp32(fp16(v))), v = fp32(x) * scale; the remaining channels up to cpad are 0.
+ *   Refused: C > 16, cpad < C, lo_ch without 2C <= cpad or together with mix_w, mix_b without mix_w.
+ * sdmi_add_nchw_residual: f = (fp32(src) + fp32(src_lo)) + fp32(ctrl); dst = fp16(f), dst_lo = fp16(f - fp32(dst)); src / dst (and the
+ *   lo halves, both or neither) fp16 NHWC [B][HW][C], dst may be src; ctrl NCHW [B][C][HW] in ctrl_dtype.  Refused: C % 8, one-sided lo.
+ * sdmi_ctx_compare: *gate (int32, zeroed by the caller) = 1 if the bits of fp16(src[b][l][c]) differ anywhere from cached[b][l][c];
+ *   src [B][L][C] in src_dtype, cached fp16 [B][Lpad][C].  sdmi_ctx_update_gated: if *gate != 0, cached[b][l][c] = fp16(src[b][l][c]) for
+ *   l < L; rows [L, Lpad) are never written.  Refused: Lpad < L.
+ * sdmi_hn_act: x fp16 [n] in place, x = fp16(act(fp32(x))); kind 0 identity, 1 relu, 2 leakyrelu, 3 elu, 4 hardswish, 5 tanh, 6 sigmoid,
+ *   7 silu, 8 gelu (erf), 9 mish, 10 relu6, 11 selu, 12 softplus, 13 softsign, 14 hardtanh, 15 hardsigmoid.  Refused: any other kind.
+ * sdmi_axpy_f16: y = fp16(fp32(x) + a * fp32(h)), the product and the sum each rounded to fp32; fp16 [n].
+ * sdmi_clip_embed: out fp16 [B][L][C] = fp16(v + pos_emb[l][c]), v = inputs_embeds[b][l][c] (fp32) when given, else
+ *   fp32(tok_emb[clamp(tokens[b][l], 0, vocab - 1)][c]); tokens int32 [B][L] (not read with inputs_embeds, may then be NULL),
+ *   tok_emb [vocab][C] in tok_dtype, pos_emb fp32 [L][C].  Refused: vocab <= 0.
+ * sdmi_clip_pool: pooled fp32 [B][C] = fp32(hidden[b][argmax_l tokens[b][l]][:]), the first maximum; hidden fp16 [B][L][C].
+ * sdmi_convert: dst[i] = (dst_dtype)src[i], n elements (F32 -> F16 through the engine's copy-out launch). */
+int sdmi_small_linear(const void* a_f32, const void* w_f16, const void* bias_f32, const void* add_f32, void* out_f32, int B, int N, int K,
+                      int lda, int ldo, int silu_in, int silu_out, void* stream);
+int sdmi_silu_f32(const void* x_f32, void* y_f32, int64_t n, void* stream);
+int sdmi_timestep_embedding(const void* t, int t_dtype, void* out_f32, int B, int dim, void* stream);
+int sdmi_nchw_to_nhwc(const void* x, int x_dtype, void* out_f16, int B, int C, int HW, int cpad, float scale, const void* mix_w_f32,
+                      const void* mix_b_f32, int lo_ch, void* stream);
+int sdmi_add_nchw_residual(const void* src_f16, const void* src_lo_f16, const void* ctrl, int ctrl_dtype, void* dst_f16, void* dst_lo_f16,
+                           int B, int C, int HW, void* stream);
+int sdmi_ctx_compare(const void* src, int src_dtype, const void* cached_f16, int B, int L, int Lpad, int C, void* gate_i32, void* stream);
+int sdmi_ctx_update_gated(const void* src, int src_dtype, void* cached_f16, int B, int L, int Lpad, int C, const void* gate_i32,
+                          void* stream);
+int sdmi_hn_act(void* x_f16, int64_t n, int kind, void* stream);
+int sdmi_axpy_f16(void* y_f16, const void* x_f16, const void* h_f16, float a, int64_t n, void* stream);
+int sdmi_clip_embed(const void* tokens_i32, const void* tok_emb, int tok_dtype, const void* pos_emb_f32, const void* inputs_embeds_f32,
+                    void* out_f16, int B, int L, int C, int vocab, void* stream);
+int sdmi_clip_pool(const void* tokens_i32, const void* hidden_f16, void* pooled_f32, int B, int L, int C, void* stream);
+int sdmi_convert(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream);
+
 /* The feed-forward chain of a BasicTransformerBlock as one launch (csrc/rowchain.hip; row width C = 320, rows % 128 == 0).  It
  * replaces, for the ff third of ldm's BasicTransformerBlock._forward as the webui runs it (modules/sd_hijack_unet.py:83-102), the launch
  * sequence LayerNorm -> GEGLU proj -> Linear -> + x.  (Round 5's cross-attention chain, sdmi_rowchain_xattn* — lane-owns-row, projections

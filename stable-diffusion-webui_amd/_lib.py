@@ -188,6 +188,18 @@ _SIGS = {
     "sdmi_groupnorm_ex": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _i64, _i, _vp, _vp, _vp]),
     "sdmi_ln_rowstats": (_i, [_vp, _vp, _i64, _i, _f, _vp]),
     "sdmi_ln_fold_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sdmi_small_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "sdmi_silu_f32": (_i, [_vp, _vp, _i64, _vp]),
+    "sdmi_timestep_embedding": (_i, [_vp, _i, _vp, _i, _i, _vp]),
+    "sdmi_nchw_to_nhwc": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    "sdmi_add_nchw_residual": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "sdmi_ctx_compare": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sdmi_ctx_update_gated": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sdmi_hn_act": (_i, [_vp, _i64, _i, _vp]),
+    "sdmi_axpy_f16": (_i, [_vp, _vp, _vp, _f, _i64, _vp]),
+    "sdmi_clip_embed": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "sdmi_clip_pool": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sdmi_convert": (_i, [_vp, _i, _vp, _i, _i64, _vp]),
     "sdmi_rowchain_ff_pack_bytes": (_i64, [_i, _i]),
     "sdmi_rowchain_ff_pack": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "sdmi_rowchain_ff": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _vp]),

@@ -370,6 +370,124 @@ int sdmi_ln_fold_weights(const void* w, const void* gamma, const void* beta, con
     API_GUARD_END
 }
 
+// Test entries for the elementwise helpers only the engine launches (include/sdmi.h).  Each refuses on the host whatever would make its
+// kernel read or write outside the buffers the header describes; the launchers' own requirements stay behind them.
+static inline bool dtype_ok(int d) { return d == SDMI_F16 || d == SDMI_F32; }
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int sdmi_small_linear(const void* a, const void* w, const void* bias, const void* add, void* out, int B, int N, int K, int lda, int ldo,
+                      int silu_in, int silu_out, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(a && w && out && B > 0 && N > 0 && K > 0, "sdmi_small_linear: null pointer or empty problem");
+    SDMI_REQUIRE(K % 8 == 0 && lda % 4 == 0 && lda >= K && ldo >= N, "sdmi_small_linear: K % 8 == 0, lda % 4 == 0, lda >= K, ldo >= N");
+    SDMI_REQUIRE(aligned16(a) && aligned16(w), "sdmi_small_linear: a and w are read in 16-byte vectors");
+    return launch_small_linear((const float*)a, (const half_t*)w, (const float*)bias, (const float*)add, (float*)out, B, N, K, lda, ldo,
+                               silu_in != 0, silu_out != 0, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_silu_f32(const void* x, void* y, int64_t n, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(x && y && n > 0, "sdmi_silu_f32: null pointer or empty problem");
+    return launch_silu_f32((const float*)x, (float*)y, n, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_timestep_embedding(const void* t, int t_dtype, void* out, int B, int dim, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(t && out && B > 0 && dim >= 2, "sdmi_timestep_embedding: null pointer, B <= 0 or dim < 2");
+    SDMI_REQUIRE((int64_t)B * dim < (1LL << 31), "sdmi_timestep_embedding: B * dim is indexed in 32 bits");
+    SDMI_REQUIRE(dtype_ok(t_dtype), "sdmi_timestep_embedding: t_dtype must be SDMI_F16 or SDMI_F32");
+    return launch_timestep_embedding(t, t_dtype, (float*)out, B, dim, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_nchw_to_nhwc(const void* x, int x_dtype, void* out, int B, int C, int HW, int cpad, float scale, const void* mix_w,
+                      const void* mix_b, int lo_ch, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(x && out && B > 0 && C > 0 && HW > 0, "sdmi_nchw_to_nhwc: null pointer or empty problem");
+    SDMI_REQUIRE(C <= 16 && cpad >= C, "sdmi_nchw_to_nhwc: C <= 16 and cpad >= C");
+    SDMI_REQUIRE(!lo_ch || (2 * C <= cpad && !mix_w), "sdmi_nchw_to_nhwc: lo_ch needs 2 * C <= cpad and no mix_w");
+    SDMI_REQUIRE(mix_w || !mix_b, "sdmi_nchw_to_nhwc: mix_b without mix_w");
+    SDMI_REQUIRE(dtype_ok(x_dtype), "sdmi_nchw_to_nhwc: x_dtype must be SDMI_F16 or SDMI_F32");
+    return launch_nchw_to_nhwc(x, x_dtype, (half_t*)out, B, C, HW, cpad, scale, (const float*)mix_w, (const float*)mix_b, (hipStream_t)stream,
+                               lo_ch != 0);
+    API_GUARD_END
+}
+
+int sdmi_add_nchw_residual(const void* src, const void* src_lo, const void* ctrl, int ctrl_dtype, void* dst, void* dst_lo, int B, int C,
+                           int HW, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(src && ctrl && dst && B > 0 && C > 0 && HW > 0, "sdmi_add_nchw_residual: null pointer or empty problem");
+    SDMI_REQUIRE(C % 8 == 0 && (src_lo == nullptr) == (dst_lo == nullptr), "sdmi_add_nchw_residual: C % 8 == 0; (hi, lo) in means (hi, lo) out");
+    SDMI_REQUIRE(aligned16(src) && aligned16(src_lo) && aligned16(dst) && aligned16(dst_lo), "sdmi_add_nchw_residual: the NHWC tensors move in 16-byte vectors");
+    SDMI_REQUIRE(dtype_ok(ctrl_dtype), "sdmi_add_nchw_residual: ctrl_dtype must be SDMI_F16 or SDMI_F32");
+    return launch_add_nchw_residual((const half_t*)src, (const half_t*)src_lo, ctrl, ctrl_dtype, (half_t*)dst, (half_t*)dst_lo, B, C, HW,
+                                    (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_ctx_compare(const void* src, int src_dtype, const void* cached, int B, int L, int Lpad, int C, void* gate, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(src && cached && gate && B > 0 && L > 0 && C > 0, "sdmi_ctx_compare: null pointer or empty problem");
+    SDMI_REQUIRE(Lpad >= L, "sdmi_ctx_compare: Lpad >= L");
+    SDMI_REQUIRE(dtype_ok(src_dtype), "sdmi_ctx_compare: src_dtype must be SDMI_F16 or SDMI_F32");
+    return launch_ctx_compare(src, src_dtype, (const half_t*)cached, B, L, Lpad, C, (int*)gate, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_ctx_update_gated(const void* src, int src_dtype, void* cached, int B, int L, int Lpad, int C, const void* gate, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(src && cached && gate && B > 0 && L > 0 && C > 0, "sdmi_ctx_update_gated: null pointer or empty problem");
+    SDMI_REQUIRE(Lpad >= L, "sdmi_ctx_update_gated: Lpad >= L");
+    SDMI_REQUIRE(dtype_ok(src_dtype), "sdmi_ctx_update_gated: src_dtype must be SDMI_F16 or SDMI_F32");
+    return launch_ctx_update_gated(src, src_dtype, (half_t*)cached, B, L, Lpad, C, (const int*)gate, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_hn_act(void* x, int64_t n, int kind, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(x && n > 0, "sdmi_hn_act: null pointer or empty problem");
+    SDMI_REQUIRE(kind >= 0 && kind <= 15, "sdmi_hn_act: kind must lie in 0 .. 15");
+    return launch_act_f16((half_t*)x, n, kind, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_axpy_f16(void* y, const void* x, const void* h, float a, int64_t n, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(y && x && h && n > 0, "sdmi_axpy_f16: null pointer or empty problem");
+    return launch_axpy_f16((half_t*)y, (const half_t*)x, (const half_t*)h, a, n, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_clip_embed(const void* tokens, const void* tok_emb, int tok_dtype, const void* pos_emb, const void* inputs_embeds, void* out, int B,
+                    int L, int C, int vocab, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(pos_emb && out && (inputs_embeds || (tokens && tok_emb)) && B > 0 && L > 0 && C > 0, "sdmi_clip_embed: null pointer or empty problem");
+    SDMI_REQUIRE(vocab > 0, "sdmi_clip_embed: vocab > 0");
+    SDMI_REQUIRE(dtype_ok(tok_dtype), "sdmi_clip_embed: tok_dtype must be SDMI_F16 or SDMI_F32");
+    return launch_clip_embed((const int*)tokens, tok_emb, tok_dtype, (const float*)pos_emb, (const float*)inputs_embeds, (half_t*)out, B, L, C,
+                             vocab, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_clip_pool(const void* tokens, const void* hidden, void* pooled, int B, int L, int C, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(tokens && hidden && pooled && B > 0 && L > 0 && C > 0, "sdmi_clip_pool: null pointer or empty problem");
+    return launch_clip_pool((const int*)tokens, (const half_t*)hidden, (float*)pooled, B, L, C, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_convert(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(src && dst && n > 0, "sdmi_convert: null pointer or empty problem");
+    SDMI_REQUIRE(dtype_ok(src_dtype) && dtype_ok(dst_dtype), "sdmi_convert: the dtypes must be SDMI_F16 or SDMI_F32");
+    if (dst_dtype == SDMI_F32) return launch_convert_to_f32(src, src_dtype, (float*)dst, n, (hipStream_t)stream);
+    if (src_dtype == SDMI_F32) return launch_copy_out((const float*)src, dst, SDMI_F16, n, (hipStream_t)stream);
+    return launch_convert_to_f16(src, SDMI_F16, (half_t*)dst, n, (hipStream_t)stream);
+    API_GUARD_END
+}
+
 int64_t sdmi_rowchain_ff_pack_bytes(int C, int hidden) { return (int64_t)rowchain_ff_pack_bytes(C, hidden); }
 int sdmi_rowchain_ff_pack(const void* w1, const void* b1, const void* w2, void* packs, int C, int hidden, void* stream) {
     API_GUARD_BEGIN

@@ -944,9 +944,11 @@ int launch_silu_f32(const float* x, float* y, int64_t n, hipStream_t s) {
 }
 
 // ---- hypernetwork MLP pieces (modules/hypernetworks/hypernetwork.py:25-113): activation in place on fp16 rows, y = x + a * h ----
+// torch's clamps hand a NaN on (relu, relu6, hardtanh, hardsigmoid of NaN are NaN); fminf / fmaxf return their other operand
+__device__ __forceinline__ float nan_or(float v, float r) { return v != v ? v : r; }
 __device__ __forceinline__ float hn_act(float v, int kind) {
     switch (kind) {
-        case 1: return fmaxf(v, 0.f);                                            // relu
+        case 1: return nan_or(v, fmaxf(v, 0.f));                                 // relu
         case 2: return v > 0.f ? v : 0.01f * v;                                  // leakyrelu (default slope)
         case 3: return v > 0.f ? v : expm1f(v);                                  // elu (alpha 1)
         case 4: return v * fminf(fmaxf(v + 3.f, 0.f), 6.f) * (1.f / 6.f);        // hardswish ("swish" in the webui's table)
@@ -955,12 +957,12 @@ __device__ __forceinline__ float hn_act(float v, int kind) {
         case 7: return v / (1.f + expf(-v));                                     // silu
         case 8: return 0.5f * v * (1.f + erff(v * 0.70710678118654752f));        // gelu (erf)
         case 9: return v * tanhf(log1pf(expf(fminf(v, 20.f))));                  // mish (softplus threshold 20)
-        case 10: return fminf(fmaxf(v, 0.f), 6.f);                               // relu6
+        case 10: return nan_or(v, fminf(fmaxf(v, 0.f), 6.f));                    // relu6
         case 11: return 1.0507009873554805f * (v > 0.f ? v : 1.6732632423543772f * expm1f(v));   // selu
         case 12: return v > 20.f ? v : log1pf(expf(v));                          // softplus (beta 1, threshold 20)
         case 13: return v / (1.f + fabsf(v));                                    // softsign
-        case 14: return fminf(fmaxf(v, -1.f), 1.f);                              // hardtanh
-        case 15: return fminf(fmaxf(v * (1.f / 6.f) + 0.5f, 0.f), 1.f);          // hardsigmoid
+        case 14: return nan_or(v, fminf(fmaxf(v, -1.f), 1.f));                   // hardtanh
+        case 15: return nan_or(v, fminf(fmaxf(v * (1.f / 6.f) + 0.5f, 0.f), 1.f));   // hardsigmoid
         default: return v;
     }
 }

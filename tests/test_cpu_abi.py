@@ -55,7 +55,7 @@ def wrappers_by_entry():
 def test_every_op_level_entry_has_a_direct_gpu_test():
     lib = sub("_lib")
     op_level = sorted(n for n in lib._SIGS if not NOT_OP_LEVEL.match(n))
-    assert 36 <= len(op_level) < len(lib._SIGS) and "sdmi_attention_vt" in op_level and "sdmi_unet_forward" not in op_level
+    assert 85 <= len(op_level) < len(lib._SIGS) and "sdmi_attention_vt" in op_level and "sdmi_unet_forward" not in op_level
     tests = "\n".join(open(p).read() for p in sorted(glob.glob(os.path.join(ROOT, "tests", "test_gpu_*.py"))))
     wrappers = wrappers_by_entry()
     assert wrappers["sdmi_attention_vt"] == {"attention_vt"} and "slerp" in wrappers["sdmi_slerp"]
