@@ -15,6 +15,7 @@ done
 # MFMA result costs an extra canonicalising v_max_f32 in an issue-bound loop
 hipcc $FLAGS -fno-honor-nans -save-temps=obj -c rowchain.hip -o build/rowchain.o & pids+=($!)
 hipcc $FLAGS -x hip -c engine.cpp -o build/engine.o & pids+=($!)
+hipcc $FLAGS -x hip -c upscalers.cpp -o build/upscalers.o & pids+=($!)
 hipcc $FLAGS -x hip -c capi.cpp -o build/capi.o & pids+=($!)
 hipcc $FLAGS -x hip -c prof.cpp -o build/prof.o & pids+=($!)
 for p in "${pids[@]}"; do wait "$p"; done

@@ -3,53 +3,6 @@
 #include "prof.h"
 #include <cstring>
 
-namespace sdmi {
-extern int g_vae_attn_rows;
-int unet_forward(sdmi_engine* e, const void* x, const void* t, const void* ctx, const void* y, void* out, int io_dtype,
-                 int Bn, int h, int w, int L, hipStream_t s);
-int vae_decode(sdmi_engine* e, const void* z, int io_dtype, float* out, int B, int h, int w, hipStream_t s);
-int vae_encode(sdmi_engine* e, const void* x, int io_dtype, float* out, int B, int H, int W, hipStream_t s);
-int engine_load_unet_tensor(sdmi_engine* e, const char* key, const void* data, int dtype, int ndim, const int64_t* shape, int on_device);
-int engine_load_vae_tensor(sdmi_engine* e, const char* key, const void* data, int dtype, int ndim, const int64_t* shape, int on_device);
-int engine_unet_finalize(sdmi_engine* e);
-int engine_clip_configure(sdmi_engine* e, int slot, const sdmi_clip_config* cfg);
-int engine_clip_load_tensor(sdmi_engine* e, int slot, const char* key, const void* data, int dtype, int ndim, const int64_t* shape, int on_device);
-int engine_clip_finalize(sdmi_engine* e, int slot);
-int engine_clip_forward(sdmi_engine* e, int slot, const int* tokens, const float* inputs_embeds, int B, int L, int skip,
-                        int apply_final_ln, float* out, float* pooled, hipStream_t s);
-int engine_unet_update_weight(sdmi_engine* e, const char* key, const void* data, int dtype, int ndim, const int64_t* shape, int on_device);
-int engine_vae_finalize(sdmi_engine* e);
-int engine_hypernet_clear(sdmi_engine* e);
-int engine_hypernet_begin(sdmi_engine* e, float multiplier);
-int engine_hypernet_linear(sdmi_engine* e, int dim, int which, const void* w, const void* b, int dtype, int out_f, int in_f, int on_device);
-int engine_hypernet_act(sdmi_engine* e, int dim, int which, int act);
-int engine_hypernet_layernorm(sdmi_engine* e, int dim, int which, const void* g, const void* b, int dtype, int n, int on_device);
-int engine_unet_update_vector(sdmi_engine* e, const char* key, const void* data, int dtype, int64_t n, int on_device);
-int engine_set_context(sdmi_engine* e, const void* ctx, int dtype, int Bn, int L, hipStream_t s, bool conditional = false);
-int64_t esrgan_blob_floats(int num_block, int in_ch);
-int esrgan_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_block, int in_ch, int scale, sdmi_esrgan** out);
-int64_t esrgan_scratch_bytes(const sdmi_esrgan* n, int B, int H, int W);
-int esrgan_run(sdmi_esrgan* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
-int64_t compact_blob_floats(int num_conv, int scale);
-int compact_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_conv, int scale, sdmi_compact** out);
-int64_t compact_scratch_bytes(const sdmi_compact* n, int B, int H, int W);
-int compact_run(sdmi_compact* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
-int64_t swinir_blob_floats(const sdmi_swinir_config* cfg);
-int swinir_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swinir_config* cfg, sdmi_swinir** out);
-int64_t swinir_scratch_bytes(const sdmi_swinir* n, int B, int H, int W);
-int swinir_run(sdmi_swinir* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
-int64_t swin2sr_blob_floats(const sdmi_swin2sr_config* cfg);
-int swin2sr_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swin2sr_config* cfg, sdmi_swin2sr** out);
-int64_t scunet_blob_floats(const sdmi_scunet_config* cfg);
-int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_scunet_config* cfg, sdmi_scunet** out);
-int64_t scunet_scratch_bytes(const sdmi_scunet* n, int B, int H, int W);
-int scunet_run(sdmi_scunet* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
-int64_t dat_blob_floats(const sdmi_dat_config* cfg);
-int dat_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_dat_config* cfg, sdmi_dat** out);
-int64_t dat_scratch_bytes(const sdmi_dat* n, int B, int H, int W);
-int dat_run(sdmi_dat* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
-}  // namespace sdmi
-
 using namespace sdmi;
 
 #define API_GUARD_BEGIN try {

@@ -41,49 +41,6 @@ const half_t* zero_page() {
     return cached;
 }
 
-static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-
-struct Run {
-    sdmi_engine* e;
-    hipStream_t s;
-    bool dry;
-    Arena* ar;                     // the activation arena this pass bump-allocates from (one per concurrent batch slice: option "streams")
-    int b0 = 0, Btot = 0;          // UNet batch slices: first row of this slice / rows of the whole call (indexes the context cache)
-    Run(sdmi_engine* e_, hipStream_t s_, bool dry_, Arena* ar_ = nullptr, int b0_ = 0, int Btot_ = 0)
-        : e(e_), s(s_), dry(dry_), ar(ar_ ? ar_ : &e_->arena), b0(b0_), Btot(Btot_) {}
-    half_t* H(size_t n) { return (half_t*)ar->take(n * sizeof(half_t)); }
-    // Option "residual_fp32": a tensor of the carried stream is a (hi, lo) pair of fp16 tensors, allocated back to back — S(n) takes
-    // room for both, lo(p, n) is the second half (null when the option is off: every consumer then sees a plain fp16 tensor).
-    // (the pairs need the LDS-direct MFMA kernels: under force_generic / use_glds = 0 — cross-check settings — the forward falls back to
-    // the plain fp16 stream instead of failing the job)
-    bool acc() const { return e->residual_fp32 && !e->force_generic && e->use_glds; }
-    half_t* S(size_t n) { return H(acc() ? 2 * n : n); }
-    half_t* lo(const half_t* p, size_t n) const { return (acc() && p) ? const_cast<half_t*>(p) + n : nullptr; }
-    // option "arena_reuse": a block's temporaries are released when the block returns — the next block's launches (same stream, so
-    // ordered behind every reader) write over them while their lines are still in the 256 MB Infinity Cache, instead of every
-    // activation of a forward (~10 GB) being written back to HBM once.  Not while block outputs are tapped or LayerNorm partials live.
-    bool reuse() const { return e->arena_reuse && !e->trace && !e->ln_fold && !acc(); }
-    float* F(size_t n) { return (float*)ar->take(n * sizeof(float)); }
-    void tap(const std::string& name, const half_t* p, int B, int H, int W, int C) {
-        if (!dry && e->trace) e->taps.push_back({name, p, B, H, W, C});
-    }
-    // GroupNorm statistics handed from a producing GEMM's epilogue to the norm that reads its output (launch_gemm: stats_out)
-    const half_t* st_tensor = nullptr;
-    float* st_ws = nullptr;
-    int st_nchunk = 0;
-    // LayerNorm row partial sums handed from a producing GEMM's epilogue to the folded consumers of its output (option "ln_fold"):
-    // set lnp_want before the producer's run_conv; lnp_tensor / lnp_ws / lnp_np describe what the last run_conv produced
-    bool lnp_want = false;
-    const half_t* lnp_tensor = nullptr;
-    float* lnp_ws = nullptr;
-    int lnp_np = 0;
-};
-
-#define TRY(x)                  \
-    do {                        \
-        if ((x) != 0) return 1; \
-    } while (0)
-
 // ------------------------------------------------------------------------------------------------------------
 // weight packing
 // ------------------------------------------------------------------------------------------------------------
@@ -361,34 +318,7 @@ static int unet_build(sdmi_engine* e) {
 // ------------------------------------------------------------------------------------------------------------
 // launch helpers
 // ------------------------------------------------------------------------------------------------------------
-struct ConvArgs {
-    const half_t* a0 = nullptr;
-    const half_t* a1 = nullptr;
-    int c0 = 0, c1 = 0;
-    int lda0 = 0;                 // row stride of a0 when its rows are wider than c0 (0 = c0)
-    int B = 1, Hi = 1, Wi = 1, Ho = 1, Wo = 1;
-    int stride = 1, pad = 0, up = 0;
-    const float* rowbias = nullptr;
-    int ldrb = 0;
-    const half_t* resid = nullptr;
-    const half_t* resid_lo = nullptr;   // (hi, lo) stream tensors: GemmP::resid_lo / out_lo
-    half_t* out_lo = nullptr;
-    int ldr = 0;
-    void* out = nullptr;
-    int ldo = 0;
-    int flags = 0;
-    int n_real = 0;
-    float alpha = 1.f;
-    float bias_scale = 1.f;
-    int batch = 1;
-    long a_bs = 0, w_bs = 0, o_bs = 0, r_bs = 0;
-    const int* gate = nullptr;
-    int stats_C = 0;              // > 0: the output feeds a GroupNorm(32) over stats_C channels: emit its partial sums from the epilogue
-    bool no_split = false;        // never take a split-K workspace from the arena (callers outside a sized forward pass)
-    float* stats_ws_pre = nullptr;    // arena_reuse: room for the GroupNorm partial sums taken by the caller (it must outlive the caller's rewind)
-};
-
-static int run_conv(Run& r, const ConvW& W, const ConvArgs& a) {
+int run_conv(Run& r, const ConvW& W, const ConvArgs& a) {
     // split-K slabs (only deep / small-M layers qualify); allocated in the dry pass too so the arena layout is identical
     float* splitk_ws = nullptr;
     if (!(a.flags & EP_NCHW) && !W.geglu && !a.no_split) {
@@ -1235,7 +1165,7 @@ static int unet_run(Run& r, const void* x, const void* t, const void* y, void* o
     return 0;
 }
 
-static int ensure_arena(Arena& ar, size_t need, hipStream_t s) {
+int ensure_arena(Arena& ar, size_t need, hipStream_t s) {
     if (need <= ar.cap) return 0;
     SDMI_CHECK_HIP(hipStreamSynchronize(s));
     if (ar.base) SDMI_CHECK_HIP(hipFree(ar.base));
@@ -1244,18 +1174,6 @@ static int ensure_arena(Arena& ar, size_t need, hipStream_t s) {
     SDMI_CHECK_HIP(hipMalloc((void**)&ar.base, cap));
     ar.cap = cap;
     return 0;
-}
-
-// Every forward is the same walk twice, walk(bool dry) -> int: dry to size the arena (pure host arithmetic: the walk only bump-allocates),
-// then, the arena grown to that, the launches.  A walk that fails dry leaves the arena out of dry mode.
-template <class Walk>
-static int two_pass(Arena& ar, hipStream_t s, Walk walk) {
-    ar.dry = true; ar.high = 0;
-    const int rc = walk(true);
-    ar.dry = false;
-    TRY(rc);
-    TRY(ensure_arena(ar, ar.high, s));
-    return walk(false);
 }
 
 // one UNet pass over rows [b0, b0 + Bn) of a call of Btot rows, on stream s out of arena ar
@@ -2013,1202 +1931,7 @@ int engine_set_context(sdmi_engine* e, const void* ctx, int dtype, int Bn, int L
     return unet_set_context(e, ctx, dtype, Bn, L, s, conditional);
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// Upscaler nets (sdmi_net): what their builds and their runs share
-// ------------------------------------------------------------------------------------------------------------
-// a fresh allocation that the net owns, filled from `host` (null: left for a pack launch to fill)
-static int net_upload(sdmi_net* net, const void* host, size_t bytes, void** dev) {
-    SDMI_CHECK_HIP(hipMalloc(dev, std::max<size_t>(bytes, 256)));
-    net->owned.push_back(*dev);
-    if (host) SDMI_CHECK_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
-    return 0;
-}
-
-// a norm of width C off the blob cursor: gamma, then beta
-static int net_norm(sdmi_net* net, const float*& src, int C, NormW* n) {
-    n->c = C;
-    TRY(net_upload(net, src, (size_t)C * sizeof(float), (void**)&n->g));
-    TRY(net_upload(net, src + C, (size_t)C * sizeof(float), (void**)&n->b));
-    src += 2 * C;
-    return 0;
-}
-
-// the host blob on the device, for the builds whose pack launches read it there; freed when the build returns
-struct StagedBlob {
-    float* p = nullptr;
-    ~StagedBlob() { (void)hipFree(p); }
-    int stage(const float* blob, int64_t blob_floats) {
-        SDMI_CHECK_HIP(hipMalloc((void**)&p, blob_floats * sizeof(float)));
-        SDMI_CHECK_HIP(hipMemcpy(p, blob, blob_floats * sizeof(float), hipMemcpyHostToDevice));
-        return 0;
-    }
-};
-
-// the relative-position table of an 8 x 8 window, entry (dy + 7) * 15 + (dx + 7) of head h at table[entry * entry_stride + h * head_stride],
-// as the attention kernels read it: bias[h][a][b] = table entry (ya - yb, xa - xb) of head h
-static int net_rel_bias(sdmi_net* net, const float* table, int heads, size_t entry_stride, size_t head_stride, float** dev) {
-    std::vector<float> bias((size_t)heads * 4096);
-    for (int h = 0; h < heads; ++h)
-        for (int a = 0; a < 64; ++a)
-            for (int b = 0; b < 64; ++b)
-                bias[((size_t)h * 64 + a) * 64 + b] =
-                    table[(size_t)(((a >> 3) - (b >> 3) + 7) * 15 + ((a & 7) - (b & 7) + 7)) * entry_stride + h * head_stride];
-    return net_upload(net, bias.data(), bias.size() * sizeof(float), (void**)dev);
-}
-
-// A net's forward is one pass over the arena, pass(Run&): what a dry walk takes from a private arena ...
-template <class Pass>
-static int64_t pass_scratch_bytes(sdmi_engine* e, Pass pass) {
-    Arena ar;
-    ar.dry = true;
-    Run dry(e, nullptr, true, &ar);
-    if (pass(dry) != 0) return 0;
-    return (int64_t)ar.high;
-}
-// ... and the run, out of the engine's arena
-template <class Pass>
-static int run_pass(sdmi_engine* e, hipStream_t s, Pass pass) {
-    const bool tiling = e->tiling;                            // p.tiling belongs to the diffusion model's convs, not to an upscaler's
-    e->tiling = false;
-    struct Restore { sdmi_engine* e; bool v; ~Restore() { e->tiling = v; } } restore{e, tiling};
-    return two_pass(e->arena, s, [&](bool dry) {
-        Run r(e, s, dry);
-        return pass(r);
-    });
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// RRDBNet upscalers (ESRGAN / Real-ESRGAN): BasicSR's RRDBNet.forward (basicsr/archs/rrdbnet_arch.py) as rrdb_conv launches
-// ------------------------------------------------------------------------------------------------------------
-// blob: fp32, for every conv in checkpoint order (conv_first, body.{i}.rdb{1..3}.conv{1..5}, conv_body, conv_up1, conv_up2, conv_hr,
-// conv_last) the OIHW weight followed by the bias.
-int64_t esrgan_blob_floats(int num_block, int in_ch) {
-    auto conv = [](int64_t o, int64_t i) { return o * i * 9 + o; };
-    int64_t n = conv(64, in_ch);
-    for (int k = 0; k < 5; ++k) n += (int64_t)num_block * 3 * conv(k < 4 ? 32 : 64, 64 + 32 * k);
-    return n + 4 * conv(64, 64) + conv(3, 64);
-}
-
-int esrgan_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_block, int in_ch, int scale, sdmi_esrgan** out) {
-    SDMI_REQUIRE(e && blob && out, "null argument");
-    SDMI_REQUIRE(num_block >= 1 && num_block <= 64, "num_block");
-    SDMI_REQUIRE((scale == 4 && in_ch == 3) || (scale == 2 && in_ch == 12) || (scale == 1 && in_ch == 48),
-                 "RRDBNet: scale 4 / 2 / 1 with 3 / 12 / 48 input channels (pixel-unshuffle in front of conv_first)");
-    SDMI_REQUIRE(blob_floats == esrgan_blob_floats(num_block, in_ch), "weight blob size does not match num_block / in_ch");
-    SDMI_CHECK_HIP(hipSetDevice(e->device));
-    std::unique_ptr<sdmi_esrgan> net(new sdmi_esrgan);
-    net->e = e; net->num_block = num_block; net->in_ch = in_ch; net->scale = scale; net->unshuffle = 4 / scale;
-    net->cin0 = rup(in_ch, 32);
-    StagedBlob dblob;
-    TRY(dblob.stage(blob, blob_floats));
-    int64_t off = 0;
-    auto pack = [&](sdmi_esrgan::Conv* c, int O, int I) -> int {
-        c->cin = rup(I, 32); c->nout = O <= 32 ? 32 : 64; c->n_real = O;
-        const size_t wb = (size_t)c->nout * 9 * c->cin * sizeof(half_t), bb = (size_t)c->nout * sizeof(float);
-        TRY(net_upload(net.get(), nullptr, wb, (void**)&c->w));
-        TRY(net_upload(net.get(), nullptr, bb, (void**)&c->b));
-        TRY(launch_pack_conv_weight(dblob.p + off, 1, c->w, O, I, 3, 3, c->nout, c->cin, 0, nullptr));
-        off += (int64_t)O * I * 9;
-        SDMI_CHECK_HIP(hipMemset(c->b, 0, bb));
-        SDMI_CHECK_HIP(hipMemcpy(c->b, dblob.p + off, (size_t)O * sizeof(float), hipMemcpyDeviceToDevice));
-        off += O;
-        return 0;
-    };
-    TRY(pack(&net->first, 64, in_ch));
-    net->rdb.resize((size_t)num_block * 15);
-    for (int i = 0; i < num_block * 3; ++i)
-        for (int k = 0; k < 5; ++k) TRY(pack(&net->rdb[(size_t)i * 5 + k], k < 4 ? 32 : 64, 64 + 32 * k));
-    TRY(pack(&net->body, 64, 64));
-    TRY(pack(&net->up1, 64, 64));
-    TRY(pack(&net->up2, 64, 64));
-    TRY(pack(&net->hr, 64, 64));
-    TRY(pack(&net->last, 3, 64));
-    SDMI_CHECK_HIP(hipDeviceSynchronize());
-    *out = net.release();
-    return 0;
-}
-
-// One pass over the network (dry: the arena layout alone).  M = B * h * w low-resolution pixels
-static int esrgan_pass(Run& r, const sdmi_esrgan& n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8) {
-    const int f = n.unshuffle, h = H / f, w = W / f;
-    const size_t M = (size_t)B * h * w;
-    r.ar->reset();
-    half_t* xin = r.H(M * n.cin0);
-    half_t* x[3];
-    for (half_t*& p : x) p = r.H(M * 192);
-    half_t* feat = r.H(M * 64);
-    half_t* trunk = r.H(M * 64);
-    half_t* u1 = r.H(4 * M * 64);
-    half_t* u2 = r.H(16 * M * 64);
-    half_t* u3 = r.H(16 * M * 64);
-    if (r.dry) return 0;
-
-    auto conv = [&](const sdmi_esrgan::Conv& c, const half_t* src, int lda, int hh, int ww, int up, void* dst, int ldo, int ep,
-                    float alpha = 1.f, const half_t* r1 = nullptr, int ldr1 = 0, float beta = 1.f, const half_t* r2 = nullptr, int ldr2 = 0,
-                    int store = RRDB_ST_F16) -> int {
-        RrdbP p{};
-        p.in = src; p.w = c.w; p.bias = c.b; p.r1 = r1; p.r2 = r2; p.out = dst;
-        p.B = B; p.H = hh; p.W = ww; p.cin = c.cin; p.lda = lda; p.up = up;
-        p.ldo = ldo; p.n_real = c.n_real; p.ldr1 = ldr1; p.ldr2 = ldr2; p.ep = ep; p.store = store; p.alpha = alpha; p.beta = beta;
-        return launch_rrdb_conv(p, c.nout, r.s);
-    };
-
-    TRY(launch_rrdb_input(in, in_u8, xin, B, 3, H, W, f, n.cin0, r.s));
-    // conv_first twice (K = 288: 0.4 % of the network's work): once into `feat`, the trunk's skip tensor that conv_body's epilogue adds,
-    // once into channels 0..63 of the first dense buffer.  conv_body cannot read that skip from x[0]: the third RDB of every RRDB writes
-    // its result over x[0], so by then x[0] holds the body's output, not conv_first's.
-    TRY(conv(n.first, xin, n.cin0, h, w, 0, feat, 64, RRDB_EP_NONE));
-    TRY(conv(n.first, xin, n.cin0, h, w, 0, x[0], 192, RRDB_EP_NONE));
-    // Dense blocks on three rotating 192-wide buffers: RDB j of an RRDB reads x[j] and writes channels 0..63 of x[(j + 1) % 3], so the
-    // third one lands on x[0] — the RRDB's own input, which its epilogue reads as r2 (same element, same lane, before the store).
-    for (int i = 0; i < n.num_block; ++i)
-        for (int j = 0; j < 3; ++j) {
-            const sdmi_esrgan::Conv* c = &n.rdb[((size_t)i * 3 + j) * 5];
-            half_t* src = x[j];
-            half_t* dst = x[(j + 1) % 3];
-            for (int k = 0; k < 4; ++k) TRY(conv(c[k], src, 192, h, w, 0, src + 64 + 32 * k, 192, RRDB_EP_LRELU));
-            if (j < 2) TRY(conv(c[4], src, 192, h, w, 0, dst, 192, RRDB_EP_RES1, 0.2f, src, 192));
-            else TRY(conv(c[4], src, 192, h, w, 0, dst, 192, RRDB_EP_RES2, 0.2f, src, 192, 0.2f, dst, 192));
-        }
-    TRY(conv(n.body, x[0], 192, h, w, 0, trunk, 64, RRDB_EP_RES1, 1.f, feat, 64));
-    TRY(conv(n.up1, trunk, 64, 2 * h, 2 * w, 1, u1, 64, RRDB_EP_LRELU));
-    TRY(conv(n.up2, u1, 64, 4 * h, 4 * w, 1, u2, 64, RRDB_EP_LRELU));
-    TRY(conv(n.hr, u2, 64, 4 * h, 4 * w, 0, u3, 64, RRDB_EP_LRELU));
-    TRY(conv(n.last, u3, 64, 4 * h, 4 * w, 0, out, 0, RRDB_EP_NONE, 1.f, nullptr, 0, 1.f, nullptr, 0,
-             out_u8 ? RRDB_ST_U8_HWC : RRDB_ST_F32_NCHW));
-    return 0;
-}
-
-int64_t esrgan_scratch_bytes(const sdmi_esrgan* n, int B, int H, int W) {
-    if (!n || B <= 0 || H <= 0 || W <= 0) return 0;
-    return pass_scratch_bytes(n->e, [&](Run& r) { return esrgan_pass(r, *n, nullptr, 0, B, H, W, nullptr, 0); });
-}
-
-// in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
-// out: [B][3][H s][W s] fp32 NCHW, or (out_u8) uint8 HWC [B][H s][W s][3] = round_half_even(clamp(y, 0, 1) * 255).
-int esrgan_run(sdmi_esrgan* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s) {
-    SDMI_REQUIRE(n && in && out, "null argument");
-    sdmi_engine* e = n->e;
-    const int f = n->unshuffle;
-    SDMI_REQUIRE(B > 0 && H > 0 && W > 0 && H % f == 0 && W % f == 0, "image sides must be multiples of the model's pixel-unshuffle factor");
-    const int h = H / f, w = W / f;
-    SDMI_REQUIRE((long long)B * h * w * 16 < (1ll << 31) - 256, "image too large: B*H*W*16 output pixels must stay below 2^31");
-    SDMI_CHECK_HIP(hipSetDevice(e->device));
-    return run_pass(e, s, [&](Run& r) { return esrgan_pass(r, *n, in, in_u8, B, H, W, out, out_u8); });
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Compact Real-ESRGAN upscalers: SRVGGNetCompact.forward (realesrgan/archs/srvgg_arch.py) as compact_conv launches
-// ------------------------------------------------------------------------------------------------------------
-// blob: fp32, for every conv in checkpoint order (body.0, body.2, ..., body.{2 (num_conv + 1)}) the OIHW weight, the bias, then (all
-// but the last conv) the 64 PReLU slopes.
-int64_t compact_blob_floats(int num_conv, int scale) {
-    return (64 * 3 * 9 + 64 + 64) + (int64_t)num_conv * (64 * 64 * 9 + 64 + 64) + (3 * scale * scale * 64 * 9 + 3 * scale * scale);
-}
-
-int compact_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_conv, int scale, sdmi_compact** out) {
-    SDMI_REQUIRE(e && blob && out, "null argument");
-    SDMI_REQUIRE(num_conv >= 1 && num_conv <= 256, "num_conv");
-    SDMI_REQUIRE(scale >= 1 && scale <= 4, "SRVGGNetCompact: scale 1..4 (3 scale^2 <= 64 channels to shuffle)");
-    SDMI_REQUIRE(blob_floats == compact_blob_floats(num_conv, scale), "weight blob size does not match num_conv / scale");
-    SDMI_CHECK_HIP(hipSetDevice(e->device));
-    std::unique_ptr<sdmi_compact> net(new sdmi_compact);
-    net->e = e; net->num_conv = num_conv; net->scale = scale;
-    StagedBlob dblob;
-    TRY(dblob.stage(blob, blob_floats));
-    int64_t off = 0;
-    net->convs.resize((size_t)num_conv + 2);
-    for (int i = 0; i < num_conv + 2; ++i) {
-        sdmi_compact::Conv* c = &net->convs[(size_t)i];
-        const int O = i == num_conv + 1 ? 3 * scale * scale : 64, I = i == 0 ? 3 : 64, cin = i == 0 ? 32 : 64;
-        TRY(net_upload(net.get(), nullptr, (size_t)64 * 9 * cin * sizeof(half_t), (void**)&c->w));
-        TRY(net_upload(net.get(), nullptr, 2 * 64 * sizeof(float), (void**)&c->b));
-        c->slope = c->b + 64;
-        TRY(launch_pack_conv_weight(dblob.p + off, 1, c->w, O, I, 3, 3, 64, cin, 0, nullptr));
-        off += (int64_t)O * I * 9;
-        SDMI_CHECK_HIP(hipMemset(c->b, 0, 2 * 64 * sizeof(float)));
-        SDMI_CHECK_HIP(hipMemcpy(c->b, dblob.p + off, (size_t)O * sizeof(float), hipMemcpyDeviceToDevice));
-        off += O;
-        if (i <= num_conv) {
-            SDMI_CHECK_HIP(hipMemcpy(c->slope, dblob.p + off, 64 * sizeof(float), hipMemcpyDeviceToDevice));
-            off += 64;
-        }
-    }
-    SDMI_CHECK_HIP(hipDeviceSynchronize());
-    *out = net.release();
-    return 0;
-}
-
-// One pass over the network (dry: the arena layout alone).  M = B * H * W pixels: every activation is at the input's resolution
-static int compact_pass(Run& r, const sdmi_compact& n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8) {
-    const size_t M = (size_t)B * H * W;
-    r.ar->reset();
-    half_t* xin = r.H(M * 32);
-    half_t* x[2];
-    for (half_t*& p : x) p = r.H(M * 64);
-    if (r.dry) return 0;
-
-    TRY(launch_rrdb_input(in, in_u8, xin, B, 3, H, W, 1, 32, r.s));
-    const half_t* src = xin;
-    for (int i = 0; i < n.num_conv + 2; ++i) {
-        const sdmi_compact::Conv& c = n.convs[(size_t)i];
-        const bool last = i == n.num_conv + 1;
-        CompactP p{};
-        p.in = src; p.w = c.w; p.bias = c.b; p.slope = c.slope;
-        p.B = B; p.H = H; p.W = W; p.cin = i == 0 ? 32 : 64; p.lda = p.cin;
-        if (last) {                                   // the activations never see a high-resolution tensor
-            p.ep = COMPACT_EP_TAIL; p.r = n.scale; p.n_real = 3 * n.scale * n.scale;
-            p.base = in; p.base_u8 = in_u8; p.out = out; p.out_u8 = out_u8;
-        } else {
-            p.ep = COMPACT_EP_PRELU; p.n_real = 64; p.out = x[i & 1]; p.ldo = 64;
-            src = x[i & 1];
-        }
-        TRY(launch_compact_conv(p, r.s));
-    }
-    return 0;
-}
-
-int64_t compact_scratch_bytes(const sdmi_compact* n, int B, int H, int W) {
-    if (!n || B <= 0 || H <= 0 || W <= 0) return 0;
-    return pass_scratch_bytes(n->e, [&](Run& r) { return compact_pass(r, *n, nullptr, 0, B, H, W, nullptr, 0); });
-}
-
-// in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
-// out: [B][3][H s][W s] fp32 NCHW, or (out_u8) uint8 HWC [B][H s][W s][3] = round_half_even(clamp(y, 0, 1) * 255).
-int compact_run(sdmi_compact* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s) {
-    SDMI_REQUIRE(n && in && out, "null argument");
-    sdmi_engine* e = n->e;
-    SDMI_REQUIRE(B > 0 && H > 0 && W > 0, "empty image");
-    SDMI_REQUIRE((long long)B * H * W * n->scale * n->scale < (1ll << 31) - 256, "image too large: the output must stay below 2^31 pixels");
-    SDMI_CHECK_HIP(hipSetDevice(e->device));
-    return run_pass(e, s, [&](Run& r) { return compact_pass(r, *n, in, in_u8, B, H, W, out, out_u8); });
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// SwinIR upscalers (nearest+conv upsampler): SwinIR.forward as GEMM launches (gemm.hip), swin_window_attn / swin_layernorm (swinir.hip)
-// and the 64-channel tail on rrdb_conv (rrdb.hip)
-// ------------------------------------------------------------------------------------------------------------
-// blob: fp32, in the order include/sdmi.h documents at sdmi_swinir_config.
-static bool swinir_config_ok(const sdmi_swinir_config& c, std::string* why) {
-    auto fail = [&](const char* m) { if (why) *why = m; return false; };
-    if (c.embed_dim < 1 || c.num_heads < 1 || c.embed_dim % c.num_heads) return fail("embed_dim must be a positive multiple of num_heads");
-    if (c.num_heads * 32 < c.embed_dim) return fail("head dim = embed_dim / num_heads must be <= 32 (num_heads * 32 >= embed_dim)");
-    if (c.num_layers < 1 || c.num_layers > 16) return fail("num_layers in 1..16");
-    for (int i = 0; i < c.num_layers; ++i)
-        if (c.depths[i] < 1 || c.depths[i] > 64) return fail("depths[i] in 1..64");
-    if (c.mlp_hidden < 1) return fail("mlp_hidden");
-    if (c.scale != 2 && c.scale != 4) return fail("scale 4 (conv_up1, conv_up2) or 2 (conv_up1)");
-    if (c.resi_3conv != 0 && c.resi_3conv != 1) return fail("resi_3conv 0 | 1");
-    if (c.resi_3conv && (c.embed_dim % 4 || c.embed_dim / 4 > 64)) return fail("3conv: embed_dim / 4 must be an integer <= 64");
-    return true;
-}
-
-int64_t swinir_blob_floats(const sdmi_swinir_config* c) {
-    if (!c || !swinir_config_ok(*c, nullptr)) return 0;
-    const int64_t C = c->embed_dim, Hd = c->mlp_hidden, q = C / 4;
-    auto lin = [](int64_t o, int64_t i, int64_t taps = 1) { return o * i * taps + o; };
-    const int64_t resi = c->resi_3conv ? lin(q, C, 9) + lin(q, q) + lin(C, q, 9) : lin(C, C, 9);
-    const int64_t block = 2 * C + 225 * c->num_heads + lin(3 * C, C) + lin(C, C) + 2 * C + lin(Hd, C) + lin(C, Hd);
-    int64_t n = lin(C, 3, 9) + 2 * C;
-    for (int i = 0; i < c->num_layers; ++i) n += c->depths[i] * block + resi;
-    n += 2 * C + resi + lin(64, C, 9) + (c->scale == 4 ? 3 : 2) * lin(64, 64, 9) + lin(3, 64, 9);
-    return n;
-}
-
-// Swin2SR: the SwinIR config its trunk shares (scale 3 and the pixel-shuffle tails are checked here, the rest by swinir_config_ok)
-static bool swin2sr_config_ok(const sdmi_swin2sr_config& c, sdmi_swinir_config* base, std::string* why) {
-    auto fail = [&](const char* m) { if (why) *why = m; return false; };
-    if (c.upsampler < 0 || c.upsampler > 2) return fail("upsampler 0 (nearest+conv) | 1 (pixelshuffle) | 2 (pixelshuffledirect)");
-    if (c.upsampler == 0 ? c.scale != 4 : (c.scale != 2 && c.scale != 3 && c.scale != 4))
-        return fail("scale 4 with the nearest+conv upsampler, 2 | 3 | 4 with pixelshuffle / pixelshuffledirect");
-    sdmi_swinir_config b{};
-    b.embed_dim = c.embed_dim; b.num_layers = c.num_layers; b.num_heads = c.num_heads; b.mlp_hidden = c.mlp_hidden;
-    b.resi_3conv = c.resi_3conv; b.scale = c.scale == 3 ? 4 : c.scale;
-    for (int i = 0; i < 16; ++i) b.depths[i] = c.depths[i];
-    if (!swinir_config_ok(b, why)) return false;
-    b.scale = c.scale;
-    if (base) *base = b;
-    return true;
-}
-
-int64_t swin2sr_blob_floats(const sdmi_swin2sr_config* c) {
-    sdmi_swinir_config b{};
-    if (!c || !swin2sr_config_ok(*c, &b, nullptr)) return 0;
-    const int64_t C = c->embed_dim, Hd = c->mlp_hidden, q = C / 4, s2 = c->scale == 3 ? 9 : 4;
-    auto lin = [](int64_t o, int64_t i, int64_t taps = 1) { return o * i * taps + o; };
-    const int64_t resi = c->resi_3conv ? lin(q, C, 9) + lin(q, q) + lin(C, q, 9) : lin(C, C, 9);
-    const int64_t block = lin(3 * C, C) + 226 * c->num_heads + lin(C, C) + 2 * C + lin(Hd, C) + lin(C, Hd) + 2 * C;
-    int64_t n = lin(C, 3, 9) + lin(C, C) + 2 * C;
-    for (int i = 0; i < c->num_layers; ++i) n += c->depths[i] * block + resi;
-    n += 2 * C + resi;
-    if (c->upsampler == 0) n += lin(64, C, 9) + 3 * lin(64, 64, 9) + lin(3, 64, 9);
-    else if (c->upsampler == 1) n += lin(64, C, 9) + (c->scale == 4 ? 2 : 1) * lin(s2 * 64, 64, 9) + lin(3, 64, 9);
-    else n += lin(3 * c->scale * c->scale, C, 9);
-    return n;
-}
-
-// Uploads and packs the weights of a SwinIR (net->v2 == 0) or Swin2SR network off its blob; net->cfg, v2 and upsampler are set
-static int swin_net_build(sdmi_swinir* net, const float* blob, int64_t blob_floats);
-
-int swinir_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swinir_config* cfg, sdmi_swinir** out) {
-    SDMI_REQUIRE(e && blob && cfg && out, "null argument");
-    std::string why;
-    SDMI_REQUIRE(swinir_config_ok(*cfg, &why), "SwinIR config: " + why);
-    SDMI_REQUIRE(blob_floats == swinir_blob_floats(cfg), "weight blob size does not match the config");
-    SDMI_CHECK_HIP(hipSetDevice(e->device));
-    std::unique_ptr<sdmi_swinir> net(new sdmi_swinir);
-    net->e = e; net->cfg = *cfg;
-    TRY(swin_net_build(net.get(), blob, blob_floats));
-    *out = net.release();
-    return 0;
-}
-
-int swin2sr_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swin2sr_config* cfg, sdmi_swin2sr** out) {
-    SDMI_REQUIRE(e && blob && cfg && out, "null argument");
-    std::string why;
-    sdmi_swinir_config base{};
-    SDMI_REQUIRE(swin2sr_config_ok(*cfg, &base, &why), "Swin2SR config: " + why);
-    SDMI_REQUIRE(blob_floats == swin2sr_blob_floats(cfg), "weight blob size does not match the config");
-    SDMI_CHECK_HIP(hipSetDevice(e->device));
-    std::unique_ptr<sdmi_swin2sr> net(new sdmi_swin2sr);
-    net->e = e; net->cfg = base; net->cfg2 = *cfg; net->v2 = 1; net->upsampler = cfg->upsampler;
-    TRY(swin_net_build(net.get(), blob, blob_floats));
-    *out = net.release();
-    return 0;
-}
-
-static int swin_net_build(sdmi_swinir* net, const float* blob, int64_t blob_floats) {
-    const sdmi_swinir_config* cfg = &net->cfg;
-    const bool v2 = net->v2 != 0;
-    const int C = cfg->embed_dim, heads = cfg->num_heads, D = C / heads, Hd = cfg->mlp_hidden, Cq = C / 4;
-    const int Cp = rup(C, 64), hid_pad = rup(Hd, 64), ldq = rup(96 * heads, 64), lda = rup(32 * heads, 64);
-    net->C = C; net->Cp = Cp; net->D = D; net->ldq = ldq; net->lda = lda; net->hid_pad = hid_pad;
-    const float* src = blob;
-    // one conv / linear: OIHW weight then bias off the blob -> [n_pad][taps][cin_pad] fp16 + [n_pad] fp32, output row o at row_of(o),
-    // input channel i at col_of(i), everything else zero; bias_add: a constant per REAL output row (the output mean on conv_last)
-    auto ident = [](int v) { return v; };
-    auto pack = [&](ConvW* c, int O, int I, int taps, int n_pad, int cin_pad, const std::function<int(int)>& row_of,
-                    const std::function<int(int)>& col_of, const float* bias_add = nullptr) -> int {
-        std::vector<half_t> w((size_t)n_pad * taps * cin_pad, (half_t)0.f);
-        std::vector<float> b((size_t)n_pad, 0.f);
-        for (int o = 0; o < O; ++o)
-            for (int i = 0; i < I; ++i)
-                for (int t = 0; t < taps; ++t)
-                    w[((size_t)row_of(o) * taps + t) * cin_pad + col_of(i)] = (half_t)src[((size_t)o * I + i) * taps + t];
-        src += (size_t)O * I * taps;
-        for (int o = 0; o < O; ++o) b[(size_t)row_of(o)] = src[o] + (bias_add ? bias_add[o] : 0.f);
-        src += O;
-        c->cin = I; c->cin_pad = cin_pad; c->cout = O; c->n_pad = n_pad; c->taps = taps;
-        TRY(net_upload(net, w.data(), w.size() * sizeof(half_t), (void**)&c->w));
-        return net_upload(net, b.data(), b.size() * sizeof(float), (void**)&c->b);
-    };
-    auto norm = [&](NormW* n) { return net_norm(net, src, C, n); };
-    // the conv that closes a layer / the trunk: 1conv, or 3conv with C / 4 padded to 64
-    auto resi = [&](ConvW* c) -> int {
-        if (!cfg->resi_3conv) return pack(&c[0], C, C, 9, Cp, Cp, ident, ident);
-        TRY(pack(&c[0], Cq, C, 9, 64, Cp, ident, ident));
-        TRY(pack(&c[1], Cq, Cq, 1, 64, 64, ident, ident));
-        return pack(&c[2], C, Cq, 9, Cp, 64, ident, ident);
-    };
-    auto slot = [&](int v) { return (v / D) * 32 + v % D; };          // feature h * D + d -> column h * 32 + d
-
-    TRY(pack(&net->first, C, 3, 9, Cp, 64, ident, ident));
-    if (v2) TRY(pack(&net->pe_proj, C, C, 1, Cp, Cp, ident, ident));
-    TRY(norm(&net->pe_norm));
-    net->layers.resize((size_t)cfg->num_layers);
-    for (int i = 0; i < cfg->num_layers; ++i) {
-        sdmi_swinir::Layer& L = net->layers[(size_t)i];
-        L.blocks.resize((size_t)cfg->depths[i]);
-        for (sdmi_swinir::Block& bk : L.blocks) {
-            auto table = [&]() -> int {                                // [225][heads]
-                const float* t = src;
-                src += 225 * heads;
-                return net_rel_bias(net, t, heads, (size_t)heads, 1, &bk.bias);
-            };
-            auto qkv = [&]() { return pack(&bk.qkv, 3 * C, C, 1, ldq, Cp, [&](int o) { return (o / C) * heads * 32 + slot(o % C); }, ident); };
-            if (!v2) {
-                TRY(norm(&bk.n1));
-                TRY(table());
-                TRY(qkv());
-                TRY(pack(&bk.proj, C, C, 1, Cp, lda, ident, slot));
-                TRY(norm(&bk.n2));
-            } else {
-                TRY(qkv());
-                TRY(table());
-                TRY(net_upload(net, src, (size_t)heads * sizeof(float), (void**)&bk.head_scale));
-                src += heads;
-                TRY(pack(&bk.proj, C, C, 1, Cp, lda, ident, slot));
-                TRY(norm(&bk.n1));
-            }
-            TRY(pack(&bk.fc1, Hd, C, 1, hid_pad, Cp, ident, ident));
-            TRY(pack(&bk.fc2, C, Hd, 1, Cp, hid_pad, ident, ident));
-            if (v2) TRY(norm(&bk.n2));
-        }
-        TRY(resi(L.conv));
-    }
-    TRY(norm(&net->norm));
-    TRY(resi(net->after));
-    const float mean[3] = {0.4488f, 0.4371f, 0.4040f};                 // y / img_range + mean folds into conv_last's bias
-    if (net->upsampler == 0) {
-        TRY(pack(&net->before, 64, C, 9, 64, Cp, ident, ident));
-        TRY(pack(&net->up1, 64, 64, 9, 64, 64, ident, ident));
-        if (cfg->scale == 4) TRY(pack(&net->up2, 64, 64, 9, 64, 64, ident, ident));
-        TRY(pack(&net->hr, 64, 64, 9, 64, 64, ident, ident));
-        TRY(pack(&net->last, 3, 64, 9, 32, 64, ident, ident, mean));
-    } else if (net->upsampler == 1) {
-        const int f2 = cfg->scale == 3 ? 9 : 4;                        // torch's channel c f^2 + (i f + j) -> row (i f + j) * 64 + c
-        TRY(pack(&net->before, 64, C, 9, 64, Cp, ident, ident));
-        for (int k = 0; k < (cfg->scale == 4 ? 2 : 1); ++k)
-            TRY(pack(&net->ps[k], f2 * 64, 64, 9, f2 * 64, 64, [&](int o) { return (o % f2) * 64 + o / f2; }, ident));
-        TRY(pack(&net->last, 3, 64, 9, 32, 64, ident, ident, mean));
-    } else {
-        TRY(pack(&net->direct, 3 * cfg->scale * cfg->scale, C, 9, 64, Cp, ident, ident));
-    }
-    SDMI_REQUIRE(src - blob == blob_floats, "internal: blob walk does not end at its length");
-    SDMI_CHECK_HIP(hipDeviceSynchronize());
-    return 0;
-}
-
-// One pass over the network (dry: the arena layout alone).  M tokens = B * Hp * Wp on the padded grid; every token tensor is Cp wide with
-// zeros in columns C .. Cp - 1 (zero weight rows / bias entries and swin_layernorm keep them so).
-static int swinir_pass(Run& r, const sdmi_swinir& n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8) {
-    const int Hp = rup(H, 8), Wp = rup(W, 8), sc = n.cfg.scale, Cp = n.Cp;
-    const size_t M = (size_t)B * Hp * Wp;
-    r.ar->reset();
-    half_t* x0 = r.H(M * 64);                                 // the padded, mean-subtracted input
-    half_t* feat = r.H(M * Cp);                               // conv_first's output: the trunk's skip tensor
-    half_t* pool[4];                                          // token tensors: a layer's input and the blocks' ping-pong
-    for (half_t*& p : pool) p = r.H(M * Cp);
-    half_t* ln = r.H(M * Cp);
-    half_t* qkv = r.H(M * n.ldq);
-    half_t* att = r.H(M * n.lda);
-    half_t* hid = r.H(M * n.hid_pad);
-    half_t* c1 = r.H(M * 64);
-    half_t* c2 = r.H(M * 64);
-    half_t* up[3] = {nullptr, nullptr, nullptr};
-    float* full = nullptr;
-    if (n.upsampler == 0) {
-        up[0] = r.H(M * 4 * 64); up[1] = sc == 4 ? r.H(M * 16 * 64) : nullptr; up[2] = r.H(M * sc * sc * 64);
-    } else if (n.upsampler == 1) {                            // the step convs' outputs and their shuffles, ping-pong
-        up[0] = r.H(M * sc * sc * 64); up[1] = r.H(M * sc * sc * 64);
-    }
-    if (n.upsampler != 2) full = r.F(M * sc * sc * 3);        // conv_last on the padded grid, cropped by swin_output
-
-    auto conv = [&](const ConvW& w, const half_t* a, const half_t* resid, half_t* o, int flags = 0, int f = 1) -> int {      // 3x3 pad 1 / 1x1 / linear, on the grid x f
-        ConvArgs c;
-        c.a0 = a; c.c0 = w.cin_pad; c.B = B; c.Hi = c.Ho = Hp * f; c.Wi = c.Wo = Wp * f; c.pad = w.taps == 9 ? 1 : 0;
-        c.resid = resid; c.ldr = w.n_pad; c.out = o; c.ldo = w.n_pad; c.flags = flags;
-        const size_t mark = r.ar->mark();                     // a split-K workspace lives for its launch only
-        const int rc = run_conv(r, w, c);
-        r.ar->rewind(mark);
-        return rc;
-    };
-    auto lnorm = [&](const NormW& w, const half_t* a, half_t* o) -> int {
-        return r.dry ? 0 : launch_swin_layernorm(a, w.g, w.b, o, (int64_t)M, n.C, Cp, 1e-5f, r.s);
-    };
-    auto lrelu = [&](half_t* a, size_t cnt, float slope) -> int { return r.dry ? 0 : launch_swin_lrelu(a, (int64_t)cnt, slope, r.s); };
-    // conv(x) + resid with the layer-closing conv (1conv | 3conv)
-    auto resi = [&](const ConvW* w, const half_t* a, const half_t* resid, half_t* o) -> int {
-        if (!n.cfg.resi_3conv) return conv(w[0], a, resid, o);
-        TRY(conv(w[0], a, nullptr, c1));
-        TRY(lrelu(c1, M * 64, 0.2f));
-        TRY(conv(w[1], c1, nullptr, c2));
-        TRY(lrelu(c2, M * 64, 0.2f));
-        return conv(w[2], c2, resid, o);
-    };
-
-    if (!r.dry) {
-        TRY(launch_swin_input(in, in_u8, x0, B, H, W, Hp, Wp, 64, r.s));
-        if (n.lda > 32 * n.cfg.num_heads)                     // an odd head count: proj reads 32 columns the attention never writes (zero weights, but not NaN x 0)
-            SDMI_CHECK_HIP(hipMemsetAsync(att, 0, M * n.lda * sizeof(half_t), r.s));
-    }
-    TRY(conv(n.first, x0, nullptr, feat));
-    half_t* x = pool[0];
-    std::vector<half_t*> free_ = {pool[1], pool[2], pool[3]};
-    if (n.v2) {                                               // Swin2SR's PatchEmbed has a 1x1 projection in front of its norm; the skip stays conv_first's output
-        TRY(conv(n.pe_proj, feat, nullptr, ln));
-        TRY(lnorm(n.pe_norm, ln, x));
-    } else {
-        TRY(lnorm(n.pe_norm, feat, x));
-    }
-    auto attention = [&](const sdmi_swinir::Block& bk, size_t j) -> int {    // qkv -> att
-        if (r.dry) return 0;
-        SwinAttnP a{};
-        a.qkv = qkv; a.bias = bk.bias; a.out = att; a.B = B; a.H = Hp; a.W = Wp; a.heads = n.cfg.num_heads; a.D = n.D;
-        a.ldq = n.ldq; a.ldo = n.lda; a.shift = (j & 1) ? 4 : 0;
-        if (n.v2) { a.cosine = 1; a.head_scale = bk.head_scale; }
-        else a.scale = 1.0f / sqrtf((float)n.D);
-        return launch_swin_attention(a, r.s);
-    };
-    for (const sdmi_swinir::Layer& L : n.layers) {
-        half_t* cur = x;
-        for (size_t j = 0; j < L.blocks.size(); ++j) {
-            const sdmi_swinir::Block& bk = L.blocks[j];
-            if (n.v2) {
-                // res-post-norm: no norm in front of qkv / fc1; the stream is updated in place by swin2_layernorm_add (the layer's
-                // first block writes a fresh buffer: x stays the skip of the layer's closing conv); `ln` holds the branch outputs
-                half_t* dst = cur;
-                if (cur == x) { dst = free_.back(); free_.pop_back(); }
-                auto lnadd = [&](const NormW& w, const half_t* resid, half_t* o) -> int {
-                    return r.dry ? 0 : launch_swin2_layernorm_add(ln, w.g, w.b, resid, o, (int64_t)M, n.C, Cp, 1e-5f, r.s);
-                };
-                TRY(conv(bk.qkv, cur, nullptr, qkv));
-                TRY(attention(bk, j));
-                TRY(conv(bk.proj, att, nullptr, ln));
-                TRY(lnadd(bk.n1, cur, dst));
-                TRY(conv(bk.fc1, dst, nullptr, hid, EP_GELU));
-                TRY(conv(bk.fc2, hid, nullptr, ln));
-                TRY(lnadd(bk.n2, dst, dst));
-                cur = dst;
-                continue;
-            }
-            half_t* mid = free_.back(); free_.pop_back();
-            half_t* nxt = free_.back(); free_.pop_back();
-            TRY(lnorm(bk.n1, cur, ln));
-            TRY(conv(bk.qkv, ln, nullptr, qkv));
-            TRY(attention(bk, j));
-            TRY(conv(bk.proj, att, cur, mid));
-            TRY(lnorm(bk.n2, mid, ln));
-            TRY(conv(bk.fc1, ln, nullptr, hid, EP_GELU));
-            TRY(conv(bk.fc2, hid, mid, nxt));
-            free_.push_back(mid);
-            if (cur != x) free_.push_back(cur);
-            cur = nxt;
-        }
-        half_t* y = free_.back(); free_.pop_back();
-        TRY(resi(L.conv, cur, x, y));
-        free_.push_back(x);
-        if (cur != x) free_.push_back(cur);
-        x = y;
-    }
-    TRY(lnorm(n.norm, x, ln));
-    half_t* trunk = free_.back();
-    TRY(resi(n.after, ln, feat, trunk));
-    if (n.upsampler == 2) {                                   // pixelshuffledirect: one conv C -> 3 sc^2, the shuffle folded into the output pass
-        TRY(conv(n.direct, trunk, nullptr, c1));
-        return r.dry ? 0 : launch_swin2_output_shuffle(c1, out, out_u8, B, H, W, Hp, Wp, sc, 64, r.s);
-    }
-    TRY(conv(n.before, trunk, nullptr, c1));
-    TRY(lrelu(c1, M * 64, 0.01f));
-    if (n.upsampler == 1) {                                   // pixelshuffle: per step conv 64 -> f^2 64 (GEMM) and the shuffle, then conv_last
-        const int f = sc == 3 ? 3 : 2;
-        const half_t* t = c1;
-        int g = 1;                                            // the grid so far: (Hp g) x (Wp g)
-        for (int k = 0; k < (sc == 4 ? 2 : 1); ++k) {
-            TRY(conv(n.ps[k], t, nullptr, up[0], 0, g));
-            if (!r.dry) TRY(launch_swin2_pixel_shuffle(up[0], up[1], B, Hp * g, Wp * g, f, r.s));
-            t = up[1];
-            g *= f;
-        }
-        if (r.dry) return 0;
-        RrdbP p{};
-        p.in = up[1]; p.w = n.last.w; p.bias = n.last.b; p.out = full;
-        p.B = B; p.H = sc * Hp; p.W = sc * Wp; p.cin = 64; p.lda = 64; p.n_real = n.last.cout; p.ep = RRDB_EP_NONE; p.store = RRDB_ST_F32_NCHW;
-        p.alpha = 1.f; p.beta = 1.f;
-        TRY(launch_rrdb_conv(p, n.last.n_pad, r.s));
-        return launch_swin_output(full, out, out_u8, B, H * sc, W * sc, Hp * sc, Wp * sc, r.s);
-    }
-    if (r.dry) return 0;
-
-    auto tail = [&](const ConvW& w, const half_t* src, int hh, int ww, int upf, void* dst, int store) -> int {
-        RrdbP p{};
-        p.in = src; p.w = w.w; p.bias = w.b; p.out = dst;
-        p.B = B; p.H = hh; p.W = ww; p.cin = 64; p.lda = 64; p.up = upf;
-        p.ldo = store == RRDB_ST_F16 ? 64 : 0; p.n_real = w.cout; p.ep = store == RRDB_ST_F16 ? RRDB_EP_LRELU : RRDB_EP_NONE; p.store = store;
-        p.alpha = 1.f; p.beta = 1.f;
-        return launch_rrdb_conv(p, w.n_pad, r.s);
-    };
-    TRY(tail(n.up1, c1, 2 * Hp, 2 * Wp, 1, up[0], RRDB_ST_F16));
-    const half_t* t = up[0];
-    if (sc == 4) { TRY(tail(n.up2, t, 4 * Hp, 4 * Wp, 1, up[1], RRDB_ST_F16)); t = up[1]; }
-    TRY(tail(n.hr, t, sc * Hp, sc * Wp, 0, up[2], RRDB_ST_F16));
-    TRY(tail(n.last, up[2], sc * Hp, sc * Wp, 0, full, RRDB_ST_F32_NCHW));
-    return launch_swin_output(full, out, out_u8, B, H * sc, W * sc, Hp * sc, Wp * sc, r.s);
-}
-
-static bool swinir_size_ok(const sdmi_swinir& n, int B, int H, int W) {
-    if (B <= 0 || H < 8 || W < 8) return false;
-    const long long M = (long long)B * rup(H, 8) * rup(W, 8);
-    const long long widest = std::max<long long>({(long long)n.ldq, (long long)n.hid_pad, (long long)n.Cp, 64ll * n.cfg.scale * n.cfg.scale});
-    return M * widest < (1ll << 31) - 256;
-}
-
-int64_t swinir_scratch_bytes(const sdmi_swinir* n, int B, int H, int W) {
-    if (!n || !swinir_size_ok(*n, B, H, W)) return 0;
-    return pass_scratch_bytes(n->e, [&](Run& r) { return swinir_pass(r, *n, nullptr, 0, B, H, W, nullptr, 0); });
-}
-
-// in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
-// out: [B][3][H s][W s] fp32 NCHW, or (out_u8) uint8 HWC [B][H s][W s][3] = round_half_even(clamp(y, 0, 1) * 255).
-int swinir_run(sdmi_swinir* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s) {
-    SDMI_REQUIRE(n && in && out, "null argument");
-    sdmi_engine* e = n->e;
-    SDMI_REQUIRE(B > 0 && H >= 8 && W >= 8, "image sides must be at least 8 (a smaller side cannot be reflect-padded to a window)");
-    SDMI_REQUIRE(swinir_size_ok(*n, B, H, W), "image too large: every intermediate tensor must stay below 2^31 elements");
-    SDMI_CHECK_HIP(hipSetDevice(e->device));
-    return run_pass(e, s, [&](Run& r) { return swinir_pass(r, *n, in, in_u8, B, H, W, out, out_u8); });
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// ScuNET (SCUNet.forward of network_scunet.py, dim 64): the transformer Block of the 32- and 64-wide levels as scu_block launches
-// (scunet.hip), of the 128- and 256-wide levels as swin_layernorm + GEMMs + swin_window_attn, the 1x1 convs and the 2x2 stride-2 /
-// transposed convs as GEMMs (the latter through scu_patch2), the 3x3 pairs on rrdb_conv (32 / 64) or the GEMMs (128 / 256)
-// ------------------------------------------------------------------------------------------------------------
-// blob: fp32, in the order include/sdmi.h documents at sdmi_scunet_config.
-static bool scunet_config_ok(const sdmi_scunet_config& c, std::string* why) {
-    for (int i = 0; i < 7; ++i)
-        if (c.depths[i] < 1 || c.depths[i] > 64) { if (why) *why = "depths[i] in 1..64"; return false; }
-    return true;
-}
-static int scunet_stage_c(int st) { return 32 << (st < 4 ? st : 6 - st); }       // conv_dim = trans_dim of m_down1 .. m_body .. m_up1
-
-int64_t scunet_blob_floats(const sdmi_scunet_config* c) {
-    if (!c || !scunet_config_ok(*c, nullptr)) return 0;
-    int64_t n = 64 * 3 * 9 + 3 * 64 * 9;
-    for (int st = 0; st < 7; ++st) {
-        const int64_t t = scunet_stage_c(st), D = 2 * t;
-        const int64_t block = 2 * t + 225 * (t / 32) + (3 * t * t + 3 * t) + (t * t + t) + 2 * t + (4 * t * t + 4 * t) + (4 * t * t + t) +
-                              2 * (D * D + D) + 2 * (t * t * 9);
-        n += c->depths[st] * block;
-        if (st < 3) n += 2 * D * D * 4;                     // Conv2d(D, 2 D, 2, 2)
-        if (st > 3) n += 2 * D * D * 4;                     // ConvTranspose2d(2 D, D, 2, 2)
-    }
-    return n;
-}
-
-int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_scunet_config* cfg, sdmi_scunet** out) {
-    SDMI_REQUIRE(e && blob && cfg && out, "null argument");
-    std::string why;
-    SDMI_REQUIRE(scunet_config_ok(*cfg, &why), "ScuNET config: " + why);
-    SDMI_REQUIRE(blob_floats == scunet_blob_floats(cfg), "weight blob size does not match the config");
-    SDMI_CHECK_HIP(hipSetDevice(e->device));
-    std::unique_ptr<sdmi_scunet> net(new sdmi_scunet);
-    net->e = e; net->cfg = *cfg;
-    const float* src = blob;
-    // one conv / linear off the blob -> [O][taps][I] fp16 (+ [O] fp32 bias).  at(o, i, t): where the checkpoint keeps that weight
-    auto pack = [&](ConvW* c, int O, int I, int taps, bool bias, const std::function<size_t(int, int, int)>& at) -> int {
-        std::vector<half_t> w((size_t)O * taps * I);
-        for (int o = 0; o < O; ++o)
-            for (int t = 0; t < taps; ++t)
-                for (int i = 0; i < I; ++i) w[((size_t)o * taps + t) * I + i] = (half_t)src[at(o, i, t)];
-        src += (size_t)O * I * taps;
-        c->cin = c->cin_pad = I; c->cout = c->n_pad = O; c->taps = taps;
-        TRY(net_upload(net.get(), w.data(), w.size() * sizeof(half_t), (void**)&c->w));
-        if (!bias) return 0;
-        TRY(net_upload(net.get(), src, (size_t)O * sizeof(float), (void**)&c->b));
-        src += O;
-        return 0;
-    };
-    auto oihw = [](int I, int taps) { return [=](int o, int i, int t) { return ((size_t)o * I + i) * taps + t; }; };
-    // m_head / m_tail on rrdb_conv: 3 input channels in a 32-wide row, 3 output channels of a 32-wide tile
-    {
-        std::vector<half_t> w((size_t)64 * 9 * 32, (half_t)0.f);
-        for (int o = 0; o < 64; ++o)
-            for (int i = 0; i < 3; ++i)
-                for (int t = 0; t < 9; ++t) w[((size_t)o * 9 + t) * 32 + i] = (half_t)src[((size_t)o * 3 + i) * 9 + t];
-        src += 64 * 3 * 9;
-        net->head.cin = 3; net->head.cin_pad = 32; net->head.cout = net->head.n_pad = 64; net->head.taps = 9;
-        TRY(net_upload(net.get(), w.data(), w.size() * sizeof(half_t), (void**)&net->head.w));
-    }
-    for (int st = 0; st < 7; ++st) {
-        const int t = scunet_stage_c(st), D = 2 * t, heads = t / 32;
-        if (st > 3)     // ConvTranspose2d(2 D, D, 2, 2) [2 D][D][2][2]: GEMM row (dy * 2 + dx) * D + o, column i
-            TRY(pack(&net->up[6 - st], 4 * D, 2 * D, 1, false, [=](int n, int i, int) { return ((size_t)i * D + n % D) * 4 + n / D; }));
-        net->stage[st].resize((size_t)cfg->depths[st]);
-        for (sdmi_scunet::Block& bk : net->stage[st]) {
-            bk.c = t;
-            const float* ln1 = src;
-            src += 2 * t;
-            TRY(net_rel_bias(net.get(), src, heads, 1, 225, &bk.bias));      // relative_position_params [heads][15][15]
-            src += 225 * heads;
-            if (t <= 64) {
-                // the Block's tensors as the pack kernel wants them: fp16 matrices, fp32 vectors, all temporaries
-                std::vector<void*> tmp;
-                auto up16 = [&](int n, const half_t** dev) -> int {
-                    std::vector<half_t> w((size_t)n);
-                    for (int i = 0; i < n; ++i) w[(size_t)i] = (half_t)src[i];
-                    src += n;
-                    void* d = nullptr;
-                    SDMI_CHECK_HIP(hipMalloc(&d, std::max<size_t>((size_t)n * 2, 256)));
-                    tmp.push_back(d);
-                    SDMI_CHECK_HIP(hipMemcpy(d, w.data(), (size_t)n * 2, hipMemcpyHostToDevice));
-                    *dev = (const half_t*)d;
-                    return 0;
-                };
-                auto up32 = [&](const float* host, int n, const float** dev) -> int {
-                    void* d = nullptr;
-                    SDMI_CHECK_HIP(hipMalloc(&d, std::max<size_t>((size_t)n * 4, 256)));
-                    tmp.push_back(d);
-                    SDMI_CHECK_HIP(hipMemcpy(d, host, (size_t)n * 4, hipMemcpyHostToDevice));
-                    *dev = (const float*)d;
-                    return 0;
-                };
-                ScuPackP pp{};
-                int rc = up32(ln1, t, &pp.ln1_g) || up32(ln1 + t, t, &pp.ln1_b);
-                rc = rc || up16(3 * t * t, &pp.wqkv) || up32(src, 3 * t, &pp.bqkv); src += 3 * t;
-                rc = rc || up16(t * t, &pp.wproj) || up32(src, t, &pp.bproj); src += t;
-                rc = rc || up32(src, t, &pp.ln2_g) || up32(src + t, t, &pp.ln2_b); src += 2 * t;
-                rc = rc || up16(4 * t * t, &pp.w1) || up32(src, 4 * t, &pp.b1); src += 4 * t;
-                rc = rc || up16(4 * t * t, &pp.w2) || up32(src, t, &pp.b2); src += t;
-                if (!rc) {
-                    rc = net_upload(net.get(), nullptr, scu_block_pack_bytes(t), &bk.packs);
-                    if (!rc) {
-                        pp.packs = bk.packs;
-                        rc = launch_scu_block_pack(pp, t, nullptr) || hipDeviceSynchronize() != hipSuccess;
-                    }
-                }
-                for (void* d : tmp) (void)hipFree(d);
-                SDMI_REQUIRE(!rc, "packing a Block's weights failed");
-            } else {
-                TRY(net_norm(net.get(), ln1, t, &bk.n1));
-                TRY(pack(&bk.qkv, 3 * t, t, 1, true, oihw(t, 1)));
-                TRY(pack(&bk.proj, t, t, 1, true, oihw(t, 1)));
-                TRY(net_norm(net.get(), src, t, &bk.n2));
-                TRY(pack(&bk.fc1, 4 * t, t, 1, true, oihw(t, 1)));
-                TRY(pack(&bk.fc2, t, 4 * t, 1, true, oihw(4 * t, 1)));
-            }
-            TRY(pack(&bk.c11, D, D, 1, true, oihw(D, 1)));
-            TRY(pack(&bk.c12, D, D, 1, true, oihw(D, 1)));
-            TRY(pack(&bk.cb0, t, t, 9, false, oihw(t, 9)));
-            TRY(pack(&bk.cb2, t, t, 9, false, oihw(t, 9)));
-        }
-        if (st < 3)     // Conv2d(D, 2 D, 2, 2) [2 D][D][2][2]: GEMM column (dy * 2 + dx) * D + i
-            TRY(pack(&net->down[st], 2 * D, 4 * D, 1, false, [=](int o, int k, int) { return ((size_t)o * D + k % D) * 4 + k / D; }));
-    }
-    {
-        std::vector<half_t> w((size_t)32 * 9 * 64, (half_t)0.f);
-        for (int o = 0; o < 3; ++o)
-            for (int i = 0; i < 64; ++i)
-                for (int t = 0; t < 9; ++t) w[((size_t)o * 9 + t) * 64 + i] = (half_t)src[((size_t)o * 64 + i) * 9 + t];
-        src += 3 * 64 * 9;
-        net->tail.cin = net->tail.cin_pad = 64; net->tail.cout = 3; net->tail.n_pad = 32; net->tail.taps = 9;
-        TRY(net_upload(net.get(), w.data(), w.size() * sizeof(half_t), (void**)&net->tail.w));
-    }
-    SDMI_REQUIRE(src - blob == blob_floats, "internal: blob walk does not end at its length");
-    SDMI_CHECK_HIP(hipDeviceSynchronize());
-    *out = net.release();
-    return 0;
-}
-
-// One pass over the network (dry: the arena layout alone).  A fixed set of buffers whatever the depths: the four skip tensors, and
-// level-1-sized work buffers that every level reuses (a level's tensors are half the size of the level above).
-static int scunet_pass(Run& r, const sdmi_scunet& n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8) {
-    const int Hp = rup(H, 64), Wp = rup(W, 64);
-    const size_t M1 = (size_t)B * Hp * Wp;
-    r.ar->reset();
-    half_t* in0 = r.H(M1 * 32);
-    half_t* skip[4] = {r.H(M1 * 64), r.H(M1 * 32), r.H(M1 * 16), r.H(M1 * 8)};      // x1 .. x4: [M1 / 4^l][64 << l]
-    half_t* pool[2] = {r.H(M1 * 64), r.H(M1 * 64)};          // a stage's ping-pong
-    half_t* Y = r.H(M1 * 64);                                 // conv1_1's output: conv_x | trans_x
-    half_t* Z = r.H(M1 * 64);                                 // cat(conv_x, trans_x) that conv1_2 reads; the 2x2 patches of the resampling convs
-    half_t* T = r.H(M1 * 32);                                 // between the two 3x3 convs
-    // the Block at trans_dim 128 / 256 (levels 3 and 4; sized for level 3, M1 / 16 rows)
-    half_t* lnb = r.H(M1 * 16);                               // [M][2 t]: swin_layernorm writes rows as wide as it reads
-    half_t* qkv = r.H(M1 * 24);
-    half_t* att = r.H(M1 * 8);
-    half_t* mid = r.H(M1 * 8);
-    half_t* hid = r.H(M1 * 32);
-    float* full = r.F(M1 * 3);                                // m_tail on the padded grid, cropped by swin_output
-
-    auto gemm = [&](const ConvW& w, const half_t* a, int lda, int h, int wd, const half_t* resid, int ldr, half_t* o, int ldo, int flags = 0) -> int {
-        ConvArgs c;
-        c.a0 = a; c.c0 = w.cin_pad; c.lda0 = lda; c.B = B; c.Hi = c.Ho = h; c.Wi = c.Wo = wd; c.pad = w.taps == 9 ? 1 : 0;
-        c.resid = resid; c.ldr = ldr; c.out = o; c.ldo = ldo; c.flags = flags;
-        const size_t mark = r.ar->mark();                     // a split-K workspace lives for its launch only
-        const int rc = run_conv(r, w, c);
-        r.ar->rewind(mark);
-        return rc;
-    };
-    auto conv3 = [&](const ConvW& w, const half_t* src, int cin, int lda, int h, int wd, void* dst, int ldo, int ep, const half_t* r1, int ldr1,
-                     int store = RRDB_ST_F16) -> int {
-        if (r.dry) return 0;
-        RrdbP p{};
-        p.in = src; p.w = w.w; p.bias = nullptr; p.r1 = r1; p.out = dst;
-        p.B = B; p.H = h; p.W = wd; p.cin = cin; p.lda = lda; p.ldo = ldo; p.n_real = w.cout; p.ldr1 = ldr1; p.ep = ep; p.store = store;
-        p.alpha = 1.f; p.beta = 1.f;
-        return launch_rrdb_conv(p, w.n_pad, r.s);
-    };
-    // one ConvTransBlock: x [M][D] -> o [M][D]
-    auto ctb = [&](const sdmi_scunet::Block& bk, int type_sw, const half_t* x, half_t* o, int h, int wd) -> int {
-        const int t = bk.c, D = 2 * t;
-        const size_t M = (size_t)B * h * wd;
-        TRY(gemm(bk.c11, x, D, h, wd, nullptr, 0, Y, D));
-        if (t <= 64) {
-            TRY(conv3(bk.cb0, Y, t, D, h, wd, T, t, RRDB_EP_RELU, nullptr, 0));
-            TRY(conv3(bk.cb2, T, t, t, h, wd, Z, D, RRDB_EP_RES1, Y, D));
-            if (!r.dry) {
-                ScuBlockP p{};
-                p.x = Y + t; p.out = Z + t; p.packs = bk.packs; p.bias = bk.bias; p.B = B; p.H = h; p.W = wd; p.ldx = D; p.ldo = D;
-                p.shift = type_sw ? 4 : 0;
-                TRY(launch_scu_block(p, t, r.s));
-            }
-        } else {
-            TRY(gemm(bk.cb0, Y, D, h, wd, nullptr, 0, T, t));
-            if (!r.dry) TRY(launch_swin_lrelu(T, (int64_t)(M * t), 0.f, r.s));       // slope 0: ReLU
-            TRY(gemm(bk.cb2, T, t, h, wd, Y, D, Z, D));
-            if (!r.dry) TRY(launch_swin_layernorm(Y + t, bk.n1.g, bk.n1.b, lnb, (int64_t)M, t, D, 1e-5f, r.s));
-            TRY(gemm(bk.qkv, lnb, D, h, wd, nullptr, 0, qkv, 3 * t));
-            if (!r.dry) {
-                SwinAttnP a{};                                // -100 where the reference has -inf: the same probabilities after an fp32 softmax
-                a.qkv = qkv; a.bias = bk.bias; a.out = att; a.B = B; a.H = h; a.W = wd; a.heads = t / 32; a.D = 32;
-                a.ldq = 3 * t; a.ldo = t; a.shift = type_sw ? 4 : 0; a.scale = 0.17677669529663689f;
-                TRY(launch_swin_attention(a, r.s));
-            }
-            TRY(gemm(bk.proj, att, t, h, wd, Y + t, D, mid, t));
-            if (!r.dry) TRY(launch_swin_layernorm(mid, bk.n2.g, bk.n2.b, att, (int64_t)M, t, t, 1e-5f, r.s));
-            TRY(gemm(bk.fc1, att, t, h, wd, nullptr, 0, hid, 4 * t, EP_GELU));
-            TRY(gemm(bk.fc2, hid, 4 * t, h, wd, mid, t, Z + t, D));
-        }
-        return gemm(bk.c12, Z, D, h, wd, x, D, o, D);
-    };
-    // the blocks of a stage through the ping-pong, block i into pool[(first + i) % 2] (the caller keeps `x` out of pool[first]);
-    // *res: the buffer the result is in
-    auto stage = [&](int st, const half_t* x, int h, int wd, int first, half_t** res) -> int {
-        const half_t* cur = x;
-        for (size_t i = 0; i < n.stage[st].size(); ++i) {
-            half_t* o = pool[(first + i) & 1];
-            TRY(ctb(n.stage[st][i], (int)(i & 1), cur, o, h, wd));
-            cur = o;
-        }
-        *res = const_cast<half_t*>(cur);
-        return 0;
-    };
-
-    if (!r.dry) TRY(launch_scu_input(in, in_u8, in0, B, H, W, Hp, Wp, 32, r.s));
-    TRY(conv3(n.head, in0, 32, 32, Hp, Wp, skip[0], 64, RRDB_EP_NONE, nullptr, 0));
-    half_t* x = nullptr;
-    for (int l = 0; l < 3; ++l) {                             // m_down1 .. m_down3
-        const int h = Hp >> l, wd = Wp >> l, D = 64 << l;
-        TRY(stage(l, skip[l], h, wd, 0, &x));
-        if (!r.dry) TRY(launch_scu_patch2(x, Z, B, h / 2, wd / 2, D, 1, r.s));
-        TRY(gemm(n.down[l], Z, 4 * D, h / 2, wd / 2, nullptr, 0, skip[l + 1], 2 * D));
-    }
-    TRY(stage(3, skip[3], Hp >> 3, Wp >> 3, 0, &x));
-    for (int l = 2; l >= 0; --l) {                            // m_up3 .. m_up1 at level l: x + skip, the transposed conv, the blocks
-        const int h = Hp >> l, wd = Wp >> l, D = 64 << l;
-        if (!r.dry) TRY(launch_scu_add(x, skip[l + 1], (int64_t)B * (h / 2) * (wd / 2) * 2 * D, r.s));
-        TRY(gemm(n.up[l], x, 2 * D, h / 2, wd / 2, nullptr, 0, Z, 4 * D));
-        if (!r.dry) TRY(launch_scu_patch2(Z, x, B, h / 2, wd / 2, D, 0, r.s));       // over the GEMM's input: it is dead
-        TRY(stage(6 - l, x, h, wd, x == pool[0] ? 1 : 0, &x));
-    }
-    if (r.dry) return 0;
-    TRY(launch_scu_add(x, skip[0], (int64_t)M1 * 64, r.s));
-    TRY(conv3(n.tail, x, 64, 64, Hp, Wp, full, 0, RRDB_EP_NONE, nullptr, 0, RRDB_ST_F32_NCHW));
-    return launch_swin_output(full, out, out_u8, B, H, W, Hp, Wp, r.s);
-}
-
-static bool scunet_size_ok(int B, int H, int W) {
-    if (B <= 0 || H < 1 || W < 1) return false;
-    return (long long)B * rup(H, 64) * rup(W, 64) * 64 < (1ll << 31) - 256;
-}
-
-int64_t scunet_scratch_bytes(const sdmi_scunet* n, int B, int H, int W) {
-    if (!n || !scunet_size_ok(B, H, W)) return 0;
-    return pass_scratch_bytes(n->e, [&](Run& r) { return scunet_pass(r, *n, nullptr, 0, B, H, W, nullptr, 0); });
-}
-
-// in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
-// out: [B][3][H][W] fp32 NCHW, or (out_u8) uint8 HWC [B][H][W][3] = round_half_even(clamp(y, 0, 1) * 255).
-int scunet_run(sdmi_scunet* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s) {
-    SDMI_REQUIRE(n && in && out, "null argument");
-    sdmi_engine* e = n->e;
-    SDMI_REQUIRE(B > 0 && H >= 1 && W >= 1, "empty image");
-    SDMI_REQUIRE(scunet_size_ok(B, H, W), "image too large: every intermediate tensor must stay below 2^31 elements");
-    SDMI_CHECK_HIP(hipSetDevice(e->device));
-    return run_pass(e, s, [&](Run& r) { return scunet_pass(r, *n, in, in_u8, B, H, W, out, out_u8); });
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// DAT upscalers (pixelshuffle, 1conv): DAT.forward as GEMM launches (gemm.hip), swin_layernorm and Swin2SR's tail passes (swinir.hip),
-// the window / channel attention, depthwise convs and AIM gates of dat.hip, conv_last on rrdb_conv (rrdb.hip)
-// ------------------------------------------------------------------------------------------------------------
-// blob: fp32, in the order include/sdmi.h documents at sdmi_dat_config.
-static bool dat_config_ok(const sdmi_dat_config& c, std::string* why) {
-    auto fail = [&](const char* m) { if (why) *why = m; return false; };
-    if (c.embed_dim < 16 || c.num_heads < 2 || c.embed_dim % c.num_heads) return fail("embed_dim must be at least 16 and a multiple of num_heads");
-    if (c.num_heads % 2) return fail("num_heads must be even (half of the heads per window branch)");
-    if (c.num_heads * 32 < c.embed_dim) return fail("head dim = embed_dim / num_heads must be <= 32 (num_heads * 32 >= embed_dim)");
-    if (c.num_heads * 32 > 512 || (c.embed_dim / 16) * c.num_heads * 32 > 8192) return fail("num_heads * 32 must be <= 512 (the AIM pass holds a row per wave)");
-    if (c.split0 != 8 || (c.split1 != 16 && c.split1 != 32)) return fail("split must be (8, 16) or (8, 32)");
-    if (c.num_layers < 1 || c.num_layers > 16) return fail("num_layers in 1..16");
-    for (int i = 0; i < c.num_layers; ++i)
-        if (c.depths[i] < 1 || c.depths[i] > 64) return fail("depths[i] in 1..64");
-    if (c.ffn_hidden < 2 || c.ffn_hidden % 2) return fail("ffn_hidden must be even (the feed-forward gate splits it in two)");
-    if (c.scale != 2 && c.scale != 3 && c.scale != 4) return fail("scale 2 | 3 | 4");
-    return true;
-}
-
-int64_t dat_blob_floats(const sdmi_dat_config* c) {
-    if (!c || !dat_config_ok(*c, nullptr)) return 0;
-    const int64_t C = c->embed_dim, E = c->ffn_hidden, hf = E / 2, C8 = C / 8, C16 = C / 16, hh = c->num_heads / 2;
-    const int64_t tab = (2 * c->split0 - 1) * (2 * c->split1 - 1) * hh, s2 = c->scale == 3 ? 9 : 4;
-    auto lin = [](int64_t o, int64_t i, int64_t taps = 1) { return o * i * taps + o; };
-    const int64_t common = 2 * C + lin(3 * C, C) + 10 * C + (C8 * C + C8 + C * C8 + C) + (C16 * C + 2 * C16 + 1) + lin(C, C) + 2 * C + lin(E, C) +
-                           2 * hf + 10 * hf + lin(C, hf);
-    int64_t n = lin(C, 3, 9) + 2 * C;
-    for (int i = 0; i < c->num_layers; ++i) {
-        const int64_t d = c->depths[i], spatial = (d + 1) / 2;
-        n += d * common + spatial * 2 * tab + (d - spatial) * c->num_heads + lin(C, C, 9);
-    }
-    return n + 2 * C + lin(C, C, 9) + lin(64, C, 9) + (c->scale == 4 ? 2 : 1) * lin(s2 * 64, 64, 9) + lin(3, 64, 9);
-}
-
-int dat_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_dat_config* cfg, sdmi_dat** out) {
-    SDMI_REQUIRE(e && blob && cfg && out, "null argument");
-    std::string why;
-    SDMI_REQUIRE(dat_config_ok(*cfg, &why), "DAT config: " + why);
-    SDMI_REQUIRE(blob_floats == dat_blob_floats(cfg), "weight blob size does not match the config");
-    SDMI_CHECK_HIP(hipSetDevice(e->device));
-    std::unique_ptr<sdmi_dat> holder(new sdmi_dat);
-    sdmi_dat* net = holder.get();
-    net->e = e; net->cfg = *cfg;
-    const int C = cfg->embed_dim, heads = cfg->num_heads, D = C / heads, E = cfg->ffn_hidden, hf = E / 2, C8 = C / 8, C16 = C / 16;
-    const int Cp = rup(C, 64), Sp = 32 * heads, Hh = rup(hf, 64);
-    net->C = C; net->Cp = Cp; net->D = D; net->Sp = Sp; net->half = hf; net->Hh = Hh; net->C8 = C8; net->C16 = C16;
-    const float* src = blob;
-    auto ident = [](int v) { return v; };
-    auto slot = [&](int v) { return (v / D) * 32 + v % D; };            // channel h * D + d -> column h * 32 + d
-    // one conv / linear off the blob, as swin_net_build packs it: output row o at row_of(o), input channel i at col_of(i), the rest zero
-    auto pack = [&](ConvW* c, int O, int I, int taps, int n_pad, int cin_pad, const std::function<int(int)>& row_of,
-                    const std::function<int(int)>& col_of, const float* bias_add = nullptr) -> int {
-        std::vector<half_t> w((size_t)n_pad * taps * cin_pad, (half_t)0.f);
-        std::vector<float> b((size_t)n_pad, 0.f);
-        for (int o = 0; o < O; ++o)
-            for (int i = 0; i < I; ++i)
-                for (int t = 0; t < taps; ++t)
-                    w[((size_t)row_of(o) * taps + t) * cin_pad + col_of(i)] = (half_t)src[((size_t)o * I + i) * taps + t];
-        src += (size_t)O * I * taps;
-        for (int o = 0; o < O; ++o) b[(size_t)row_of(o)] = src[o] + (bias_add ? bias_add[o] : 0.f);
-        src += O;
-        c->cin = I; c->cin_pad = cin_pad; c->cout = O; c->n_pad = n_pad; c->taps = taps;
-        TRY(net_upload(net, w.data(), w.size() * sizeof(half_t), (void**)&c->w));
-        return net_upload(net, b.data(), b.size() * sizeof(float), (void**)&c->b);
-    };
-    // an fp32 matrix [rows][cols] off the blob -> [rows_pad][cols_pad] with row r at row_of(r), column c at col_of(c); transposed: the
-    // blob holds [cols][rows] (a depthwise weight [C][9] -> [9][C])
-    auto mat = [&](float** dev, int rows, int cols, int rows_pad, int cols_pad, const std::function<int(int)>& row_of,
-                   const std::function<int(int)>& col_of, bool transposed = false) -> int {
-        std::vector<float> m((size_t)rows_pad * cols_pad, 0.f);
-        for (int rr = 0; rr < rows; ++rr)
-            for (int cc = 0; cc < cols; ++cc)
-                m[(size_t)row_of(rr) * cols_pad + col_of(cc)] = transposed ? src[(size_t)cc * rows + rr] : src[(size_t)rr * cols + cc];
-        src += (size_t)rows * cols;
-        return net_upload(net, m.data(), m.size() * sizeof(float), (void**)dev);
-    };
-    auto raw = [&](float** dev, size_t count) -> int {
-        TRY(net_upload(net, src, count * sizeof(float), (void**)dev));
-        src += count;
-        return 0;
-    };
-    const size_t tab = (size_t)(2 * cfg->split0 - 1) * (2 * cfg->split1 - 1) * (heads / 2);
-
-    TRY(pack(&net->first, C, 3, 9, Cp, 64, ident, ident));
-    TRY(net_norm(net, src, C, &net->rg_norm));
-    net->layers.resize((size_t)cfg->num_layers);
-    for (int i = 0; i < cfg->num_layers; ++i) {
-        sdmi_dat::Layer& L = net->layers[(size_t)i];
-        L.blocks.resize((size_t)cfg->depths[i]);
-        for (int j = 0; j < cfg->depths[i]; ++j) {
-            sdmi_dat::Block& bk = L.blocks[(size_t)j];
-            bk.spatial = j % 2 == 0;
-            bk.shifted = bk.spatial && ((i % 2 == 0 && j > 0 && (j - 2) % 4 == 0) || (i % 2 == 1 && j % 4 == 0));
-            TRY(net_norm(net, src, C, &bk.n1));
-            TRY(pack(&bk.qkv, 3 * C, C, 1, 3 * Sp, Cp, [&](int o) { return (o / C) * Sp + slot(o % C); }, ident));
-            if (bk.spatial) {
-                TRY(raw(&bk.tab0, tab));
-                TRY(raw(&bk.tab1, tab));
-            } else {
-                TRY(raw(&bk.temperature, (size_t)heads));
-            }
-            TRY(mat(&bk.dw_w, 9, C, 9, Sp, ident, slot, true));
-            TRY(mat(&bk.dw_b, 1, C, 1, Sp, ident, slot));
-            TRY(mat(&bk.ci_w1, C8, C, C8, Sp, ident, slot));
-            TRY(raw(&bk.ci_b1, (size_t)C8));
-            TRY(mat(&bk.ci_w2, C, C8, Sp, C8, slot, ident));
-            TRY(mat(&bk.ci_b2, 1, C, 1, Sp, ident, slot));
-            TRY(mat(&bk.si_w1, C16, C, C16, Sp, ident, slot));
-            TRY(raw(&bk.si_b1, (size_t)C16));
-            TRY(raw(&bk.si_w2, (size_t)C16));
-            bk.si_b2 = *src++;
-            TRY(pack(&bk.proj, C, C, 1, Cp, Sp, ident, slot));
-            TRY(net_norm(net, src, C, &bk.n2));
-            TRY(pack(&bk.fc1, E, C, 1, 2 * Hh, Cp, [&](int o) { return o < hf ? o : Hh + o - hf; }, ident));     // x1 | x2 in two 64-multiple halves
-            TRY(net_norm(net, src, hf, &bk.sgn));
-            TRY(mat(&bk.sg_w, 9, hf, 9, Hh, ident, ident, true));
-            TRY(mat(&bk.sg_b, 1, hf, 1, Hh, ident, ident));
-            TRY(pack(&bk.fc2, C, hf, 1, Cp, Hh, ident, ident));
-        }
-        TRY(pack(&L.conv, C, C, 9, Cp, Cp, ident, ident));
-    }
-    TRY(net_norm(net, src, C, &net->norm));
-    TRY(pack(&net->after, C, C, 9, Cp, Cp, ident, ident));
-    const float mean[3] = {0.4488f, 0.4371f, 0.4040f};                 // y / img_range + mean folds into conv_last's bias
-    const int f2 = cfg->scale == 3 ? 9 : 4;                             // torch's channel c f^2 + (i f + j) -> row (i f + j) * 64 + c
-    TRY(pack(&net->before, 64, C, 9, 64, Cp, ident, ident));
-    for (int k = 0; k < (cfg->scale == 4 ? 2 : 1); ++k)
-        TRY(pack(&net->ps[k], f2 * 64, 64, 9, f2 * 64, 64, [&](int o) { return (o % f2) * 64 + o / f2; }, ident));
-    TRY(pack(&net->last, 3, 64, 9, 32, 64, ident, ident, mean));
-    SDMI_REQUIRE(src - blob == blob_floats, "internal: blob walk does not end at its length");
-    SDMI_CHECK_HIP(hipDeviceSynchronize());
-    *out = holder.release();
-    return 0;
-}
-
-// One pass over the network (dry: the arena layout alone).  M = B * H * W tokens, no padding of the grid (the window attention pads by
-// index).  Stream tensors are Cp wide with zeros in columns C .. Cp - 1; q | k | v, att, the AIM conv and proj's input are Sp = 32 heads wide
-// in head slots; fc1 writes x1 | x2 as two Hh-wide halves of one row.
-static int dat_pass(Run& r, const sdmi_dat& n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8) {
-    const int sc = n.cfg.scale, Cp = n.Cp, Sp = n.Sp, Hh = n.Hh, heads = n.cfg.num_heads, N = H * W;
-    const size_t M = (size_t)B * N;
-    r.ar->reset();
-    half_t* x0 = r.H(M * 64);                                 // the mean-subtracted input
-    half_t* feat = r.H(M * Cp);                               // conv_first's output: the trunk's skip tensor
-    half_t* pool[4];                                          // token tensors: a group's input and the blocks' ping-pong
-    for (half_t*& p : pool) p = r.H(M * Cp);
-    half_t* ln = r.H(M * Cp);
-    half_t* qkv = r.H(M * 3 * Sp);
-    half_t* att = r.H(M * Sp);
-    half_t* cv = r.H(M * Sp);                                 // GELU(BN(dwconv(v)))
-    half_t* mix = r.H(M * Sp);                                // what proj reads
-    half_t* hid = r.H(M * 2 * Hh);
-    half_t* gated = r.H(M * Hh);                              // x1 * dwconv(norm(x2))
-    float* gram = r.F((size_t)B * heads * cdiv(N, DAT_GRAM_TOKENS) * 1088);
-    half_t* amat = r.H((size_t)B * Sp * Sp);
-    float* pool_ws = r.F((size_t)B * cdiv(N, DAT_POOL_TOKENS) * Sp);
-    float* cgate = r.F((size_t)B * Sp);
-    half_t* c1 = r.H(M * 64);
-    half_t* up[2] = {r.H(M * sc * sc * 64), r.H(M * sc * sc * 64)};      // the step convs' outputs and their shuffles, ping-pong
-    float* full = r.F(M * sc * sc * 3);
-
-    auto conv = [&](const ConvW& w, const half_t* a, const half_t* resid, half_t* o, int flags = 0, int f = 1) -> int {      // 3x3 pad 1 / linear, on the grid x f
-        ConvArgs c;
-        c.a0 = a; c.c0 = w.cin_pad; c.B = B; c.Hi = c.Ho = H * f; c.Wi = c.Wo = W * f; c.pad = w.taps == 9 ? 1 : 0;
-        c.resid = resid; c.ldr = w.n_pad; c.out = o; c.ldo = w.n_pad; c.flags = flags;
-        const size_t mark = r.ar->mark();                     // a split-K workspace lives for its launch only
-        const int rc = run_conv(r, w, c);
-        r.ar->rewind(mark);
-        return rc;
-    };
-    auto lnorm = [&](const NormW& w, const half_t* a, half_t* o) -> int {
-        return r.dry ? 0 : launch_swin_layernorm(a, w.g, w.b, o, (int64_t)M, n.C, Cp, 1e-5f, r.s);
-    };
-    // everything between qkv and proj
-    auto attention = [&](const sdmi_dat::Block& bk) -> int {
-        if (r.dry) return 0;
-        const half_t* v = qkv + 2 * Sp;
-        if (bk.spatial) {
-            DatAttnP a{};
-            a.qkv = qkv; a.bias0 = bk.tab0; a.bias1 = bk.tab1; a.out = att; a.B = B; a.H = H; a.W = W; a.heads = heads; a.D = n.D;
-            a.ldq = 3 * Sp; a.ldo = Sp; a.s0 = n.cfg.split0; a.s1 = n.cfg.split1; a.shifted = bk.shifted ? 1 : 0; a.scale = 1.0f / sqrtf((float)n.D);
-            TRY(launch_dat_window_attention(a, r.s));
-        } else {
-            TRY(launch_dat_channel_gram(qkv, gram, B, N, heads, 3 * Sp, r.s));
-            TRY(launch_dat_channel_softmax(gram, bk.temperature, amat, B, N, heads, n.D, r.s));
-            GemmP g{};                                        // att[b] = v[b] A[b]^T: a batched 1x1 GEMM with per-image weights
-            g.a0 = v; g.c0 = Sp; g.cin = Sp; g.lda0 = 3 * Sp;
-            g.w = amat; g.ldw = Sp;
-            g.out = att;
-            g.Hi = N; g.Wi = 1; g.Ho = N; g.Wo = 1; g.taps = 1; g.stride = 1;
-            g.M = N; g.N = Sp; g.K = Sp; g.ldo = Sp; g.rows_per_batch = N; g.n_real = Sp;
-            g.alpha = 1.f;
-            g.a_bs = (long)N * 3 * Sp; g.w_bs = (long)Sp * Sp; g.o_bs = (long)N * Sp;
-            TRY(launch_gemm(g, B, r.e->force_generic, r.e->use_glds, r.s));
-        }
-        TRY(launch_dat_dwconv3x3(v, bk.dw_w, bk.dw_b, nullptr, cv, B, H, W, Sp, 3 * Sp, 0, Sp, 0, r.s));
-        const half_t* sop = bk.spatial ? att : cv;            // the spatial MLP's operand; the channel gate is pooled from the other
-        const half_t* top = bk.spatial ? cv : att;
-        TRY(launch_dat_pool_gate(top, bk.ci_w1, bk.ci_b1, bk.ci_w2, bk.ci_b2, pool_ws, cgate, B, N, Sp, n.C8, Sp, r.s));
-        DatAimP m{};
-        m.s = sop; m.t = top; m.cg = cgate; m.w1 = bk.si_w1; m.b1 = bk.si_b1; m.w2 = bk.si_w2; m.b2 = bk.si_b2; m.out = mix;
-        m.rows = (long long)M; m.rows_per_image = N; m.C = Sp; m.C16 = n.C16; m.lds = Sp; m.ldt = Sp; m.ldo = Sp;
-        return launch_dat_aim_combine(m, r.s);
-    };
-    // x2 <- LayerNorm(x2) in place (a lane reads what it then writes), then x1 * dwconv(x2)
-    auto gate = [&](const sdmi_dat::Block& bk) -> int {
-        if (r.dry) return 0;
-        TRY(launch_swin_layernorm(hid + Hh, bk.sgn.g, bk.sgn.b, hid + Hh, (int64_t)M, n.half, 2 * Hh, 1e-5f, r.s));
-        return launch_dat_dwconv3x3(hid + Hh, bk.sg_w, bk.sg_b, hid, gated, B, H, W, Hh, 2 * Hh, 2 * Hh, Hh, 1, r.s);
-    };
-
-    if (!r.dry) TRY(launch_swin_input(in, in_u8, x0, B, H, W, H, W, 64, r.s));
-    TRY(conv(n.first, x0, nullptr, feat));
-    half_t* x = pool[0];
-    std::vector<half_t*> free_ = {pool[1], pool[2], pool[3]};
-    TRY(lnorm(n.rg_norm, feat, x));
-    for (const sdmi_dat::Layer& L : n.layers) {
-        half_t* cur = x;
-        for (const sdmi_dat::Block& bk : L.blocks) {
-            half_t* mid = free_.back(); free_.pop_back();
-            half_t* nxt = free_.back(); free_.pop_back();
-            TRY(lnorm(bk.n1, cur, ln));
-            TRY(conv(bk.qkv, ln, nullptr, qkv));
-            TRY(attention(bk));
-            TRY(conv(bk.proj, mix, cur, mid));
-            TRY(lnorm(bk.n2, mid, ln));
-            TRY(conv(bk.fc1, ln, nullptr, hid, EP_GELU));
-            TRY(gate(bk));
-            TRY(conv(bk.fc2, gated, mid, nxt));
-            free_.push_back(mid);
-            if (cur != x) free_.push_back(cur);
-            cur = nxt;
-        }
-        half_t* y = free_.back(); free_.pop_back();
-        TRY(conv(L.conv, cur, x, y));
-        free_.push_back(x);
-        if (cur != x) free_.push_back(cur);
-        x = y;
-    }
-    TRY(lnorm(n.norm, x, ln));
-    half_t* trunk = free_.back();
-    TRY(conv(n.after, ln, feat, trunk));
-    TRY(conv(n.before, trunk, nullptr, c1));
-    if (!r.dry) TRY(launch_swin_lrelu(c1, (int64_t)(M * 64), 0.01f, r.s));
-    const int f = sc == 3 ? 3 : 2;
-    const half_t* t = c1;
-    int g = 1;                                                // the grid so far: (H g) x (W g)
-    for (int k = 0; k < (sc == 4 ? 2 : 1); ++k) {
-        TRY(conv(n.ps[k], t, nullptr, up[0], 0, g));
-        if (!r.dry) TRY(launch_swin2_pixel_shuffle(up[0], up[1], B, H * g, W * g, f, r.s));
-        t = up[1];
-        g *= f;
-    }
-    if (r.dry) return 0;
-    RrdbP p{};
-    p.in = up[1]; p.w = n.last.w; p.bias = n.last.b; p.out = full;
-    p.B = B; p.H = sc * H; p.W = sc * W; p.cin = 64; p.lda = 64; p.n_real = n.last.cout; p.ep = RRDB_EP_NONE; p.store = RRDB_ST_F32_NCHW;
-    p.alpha = 1.f; p.beta = 1.f;
-    TRY(launch_rrdb_conv(p, n.last.n_pad, r.s));
-    return launch_swin_output(full, out, out_u8, B, H * sc, W * sc, H * sc, W * sc, r.s);
-}
-
-static bool dat_size_ok(const sdmi_dat& n, int B, int H, int W) {
-    if (B <= 0 || H < 1 || W < 1) return false;
-    const long long Mp = (long long)B * rup(H, n.cfg.split1) * rup(W, n.cfg.split1);      // the attention's padded grid
-    const long long widest = std::max<long long>({3ll * n.Sp, 2ll * n.Hh, (long long)n.Cp, 64ll * n.cfg.scale * n.cfg.scale});
-    return Mp * widest < (1ll << 31) - 256;
-}
-
-int64_t dat_scratch_bytes(const sdmi_dat* n, int B, int H, int W) {
-    if (!n || !dat_size_ok(*n, B, H, W)) return 0;
-    return pass_scratch_bytes(n->e, [&](Run& r) { return dat_pass(r, *n, nullptr, 0, B, H, W, nullptr, 0); });
-}
-
-// in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].
-// out: [B][3][H s][W s] fp32 NCHW, or (out_u8) uint8 HWC [B][H s][W s][3] = round_half_even(clamp(y, 0, 1) * 255).
-int dat_run(sdmi_dat* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s) {
-    SDMI_REQUIRE(n && in && out, "null argument");
-    sdmi_engine* e = n->e;
-    SDMI_REQUIRE(B > 0 && H >= 1 && W >= 1, "empty image");
-    SDMI_REQUIRE(dat_size_ok(*n, B, H, W), "image too large: every intermediate tensor must stay below 2^31 elements");
-    SDMI_CHECK_HIP(hipSetDevice(e->device));
-    return run_pass(e, s, [&](Run& r) { return dat_pass(r, *n, in, in_u8, B, H, W, out, out_u8); });
-}
-
 }  // namespace sdmi
-
-sdmi_net::~sdmi_net() {
-    for (void* p : owned) (void)hipFree(p);
-}
 
 sdmi_engine::~sdmi_engine() {
     (void)hipSetDevice(device);
@@ -3229,14 +1952,14 @@ sdmi_engine::~sdmi_engine() {
     if (ev_fork) (void)hipEventDestroy(ev_fork);
 }
 
-// The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units; there the upscalers'
-// and the cross-attention chain's kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip, swinir.hip,
-// scunet.hip, dat.hip and xattn_chain.hip on their own (build.sh).
+// The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units; there the
+// cross-attention chain's kernel file travels inside this one.  upscalers.cpp is a unit of its own on that list (tests/hostemu/build.py
+// HOST_FILES, which says so with SDMI_UPSCALERS_OWN_UNIT); a list from before the file existed — an older tests/ run against this csrc/,
+// as in an A/B of two commits — names only capi.cpp and this file, and then gets upscalers.cpp here, or the library would lack a third
+// of the C ABI.  The GPU build compiles upscalers.cpp and xattn_chain.hip on their own (build.sh).
 #ifndef __HIP__
-#include "rrdb.hip"
-#include "compact.hip"
-#include "swinir.hip"
-#include "scunet.hip"
-#include "dat.hip"
+#ifndef SDMI_UPSCALERS_OWN_UNIT
+#include "upscalers.cpp"
+#endif
 #include "xattn_chain.hip"
 #endif

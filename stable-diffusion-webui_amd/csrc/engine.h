@@ -301,7 +301,7 @@ struct sdmi_swinir : sdmi_net {
     sdmi::ConvW ps[2], direct;                // ps: 64 -> f*f*64, output channels in (i, j, c) order; direct: C -> 3 scale^2 (padded to 64)
 };
 
-// Swin2SR upscaler: SwinIR's trunk and buffers with v2 set (engine.cpp swinir_pass runs both)
+// Swin2SR upscaler: SwinIR's trunk and buffers with v2 set (upscalers.cpp swinir_pass runs both)
 struct sdmi_swin2sr : sdmi_swinir {
     sdmi_swin2sr_config cfg2{};
 };
@@ -352,3 +352,144 @@ struct sdmi_scunet : sdmi_net {
     sdmi::ConvW head, tail, down[3], up[3];   // down[l]: level l -> l + 1 (K = 4 Cin); up[l]: level l + 1 -> l (N = 4 Cout)
     std::vector<Block> stage[7];              // m_down1, m_down2, m_down3, m_body, m_up3, m_up2, m_up1
 };
+
+namespace sdmi {
+
+// What engine.cpp and upscalers.cpp share: one pass over an arena and its GEMM launch
+static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
+
+struct Run {
+    sdmi_engine* e;
+    hipStream_t s;
+    bool dry;
+    Arena* ar;                     // the activation arena this pass bump-allocates from (one per concurrent batch slice: option "streams")
+    int b0 = 0, Btot = 0;          // UNet batch slices: first row of this slice / rows of the whole call (indexes the context cache)
+    Run(sdmi_engine* e_, hipStream_t s_, bool dry_, Arena* ar_ = nullptr, int b0_ = 0, int Btot_ = 0)
+        : e(e_), s(s_), dry(dry_), ar(ar_ ? ar_ : &e_->arena), b0(b0_), Btot(Btot_) {}
+    half_t* H(size_t n) { return (half_t*)ar->take(n * sizeof(half_t)); }
+    // Option "residual_fp32": a tensor of the carried stream is a (hi, lo) pair of fp16 tensors, allocated back to back — S(n) takes
+    // room for both, lo(p, n) is the second half (null when the option is off: every consumer then sees a plain fp16 tensor).
+    // (the pairs need the LDS-direct MFMA kernels: under force_generic / use_glds = 0 — cross-check settings — the forward falls back to
+    // the plain fp16 stream instead of failing the job)
+    bool acc() const { return e->residual_fp32 && !e->force_generic && e->use_glds; }
+    half_t* S(size_t n) { return H(acc() ? 2 * n : n); }
+    half_t* lo(const half_t* p, size_t n) const { return (acc() && p) ? const_cast<half_t*>(p) + n : nullptr; }
+    // option "arena_reuse": a block's temporaries are released when the block returns — the next block's launches (same stream, so
+    // ordered behind every reader) write over them while their lines are still in the 256 MB Infinity Cache, instead of every
+    // activation of a forward (~10 GB) being written back to HBM once.  Not while block outputs are tapped or LayerNorm partials live.
+    bool reuse() const { return e->arena_reuse && !e->trace && !e->ln_fold && !acc(); }
+    float* F(size_t n) { return (float*)ar->take(n * sizeof(float)); }
+    void tap(const std::string& name, const half_t* p, int B, int H, int W, int C) {
+        if (!dry && e->trace) e->taps.push_back({name, p, B, H, W, C});
+    }
+    // GroupNorm statistics handed from a producing GEMM's epilogue to the norm that reads its output (launch_gemm: stats_out)
+    const half_t* st_tensor = nullptr;
+    float* st_ws = nullptr;
+    int st_nchunk = 0;
+    // LayerNorm row partial sums handed from a producing GEMM's epilogue to the folded consumers of its output (option "ln_fold"):
+    // set lnp_want before the producer's run_conv; lnp_tensor / lnp_ws / lnp_np describe what the last run_conv produced
+    bool lnp_want = false;
+    const half_t* lnp_tensor = nullptr;
+    float* lnp_ws = nullptr;
+    int lnp_np = 0;
+};
+
+#define TRY(x)                  \
+    do {                        \
+        if ((x) != 0) return 1; \
+    } while (0)
+
+struct ConvArgs {
+    const half_t* a0 = nullptr;
+    const half_t* a1 = nullptr;
+    int c0 = 0, c1 = 0;
+    int lda0 = 0;                 // row stride of a0 when its rows are wider than c0 (0 = c0)
+    int B = 1, Hi = 1, Wi = 1, Ho = 1, Wo = 1;
+    int stride = 1, pad = 0, up = 0;
+    const float* rowbias = nullptr;
+    int ldrb = 0;
+    const half_t* resid = nullptr;
+    const half_t* resid_lo = nullptr;   // (hi, lo) stream tensors: GemmP::resid_lo / out_lo
+    half_t* out_lo = nullptr;
+    int ldr = 0;
+    void* out = nullptr;
+    int ldo = 0;
+    int flags = 0;
+    int n_real = 0;
+    float alpha = 1.f;
+    float bias_scale = 1.f;
+    int batch = 1;
+    long a_bs = 0, w_bs = 0, o_bs = 0, r_bs = 0;
+    const int* gate = nullptr;
+    int stats_C = 0;              // > 0: the output feeds a GroupNorm(32) over stats_C channels: emit its partial sums from the epilogue
+    bool no_split = false;        // never take a split-K workspace from the arena (callers outside a sized forward pass)
+    float* stats_ws_pre = nullptr;    // arena_reuse: room for the GroupNorm partial sums taken by the caller (it must outlive the caller's rewind)
+};
+
+int run_conv(Run& r, const ConvW& W, const ConvArgs& a);
+int ensure_arena(Arena& ar, size_t need, hipStream_t s);
+
+// Every forward is the same walk twice, walk(bool dry) -> int: dry to size the arena (pure host arithmetic: the walk only bump-allocates),
+// then, the arena grown to that, the launches.  A walk that fails dry leaves the arena out of dry mode.
+template <class Walk>
+int two_pass(Arena& ar, hipStream_t s, Walk walk) {
+    ar.dry = true; ar.high = 0;
+    const int rc = walk(true);
+    ar.dry = false;
+    TRY(rc);
+    TRY(ensure_arena(ar, ar.high, s));
+    return walk(false);
+}
+
+// What capi.cpp calls: engine.cpp ...
+extern int g_vae_attn_rows;
+int unet_forward(sdmi_engine* e, const void* x, const void* t, const void* ctx, const void* y, void* out, int io_dtype,
+                 int Bn, int h, int w, int L, hipStream_t s);
+int vae_decode(sdmi_engine* e, const void* z, int io_dtype, float* out, int B, int h, int w, hipStream_t s);
+int vae_encode(sdmi_engine* e, const void* x, int io_dtype, float* out, int B, int H, int W, hipStream_t s);
+int engine_load_unet_tensor(sdmi_engine* e, const char* key, const void* data, int dtype, int ndim, const int64_t* shape, int on_device);
+int engine_load_vae_tensor(sdmi_engine* e, const char* key, const void* data, int dtype, int ndim, const int64_t* shape, int on_device);
+int engine_unet_finalize(sdmi_engine* e);
+int engine_clip_configure(sdmi_engine* e, int slot, const sdmi_clip_config* cfg);
+int engine_clip_load_tensor(sdmi_engine* e, int slot, const char* key, const void* data, int dtype, int ndim, const int64_t* shape, int on_device);
+int engine_clip_finalize(sdmi_engine* e, int slot);
+int engine_clip_forward(sdmi_engine* e, int slot, const int* tokens, const float* inputs_embeds, int B, int L, int skip,
+                        int apply_final_ln, float* out, float* pooled, hipStream_t s);
+int engine_unet_update_weight(sdmi_engine* e, const char* key, const void* data, int dtype, int ndim, const int64_t* shape, int on_device);
+int engine_vae_finalize(sdmi_engine* e);
+int engine_hypernet_clear(sdmi_engine* e);
+int engine_hypernet_begin(sdmi_engine* e, float multiplier);
+int engine_hypernet_linear(sdmi_engine* e, int dim, int which, const void* w, const void* b, int dtype, int out_f, int in_f, int on_device);
+int engine_hypernet_act(sdmi_engine* e, int dim, int which, int act);
+int engine_hypernet_layernorm(sdmi_engine* e, int dim, int which, const void* g, const void* b, int dtype, int n, int on_device);
+int engine_unet_update_vector(sdmi_engine* e, const char* key, const void* data, int dtype, int64_t n, int on_device);
+int engine_set_context(sdmi_engine* e, const void* ctx, int dtype, int Bn, int L, hipStream_t s, bool conditional = false);
+
+// ... and upscalers.cpp.  Every family: the floats its weight blob holds (0: a config the engine refuses), the net off a host blob, the
+// arena bytes one run takes (0: a size the run refuses), and the run.  in: the RGB image(s), uint8 HWC [B][H][W][3] (in_u8; scaled by
+// 1/255) or fp32 NCHW [B][3][H][W] in [0, 1].  out: [B][3][H s][W s] fp32 NCHW, or (out_u8) uint8 HWC [B][H s][W s][3] =
+// round_half_even(clamp(y, 0, 1) * 255); s = 1 for ScuNET.
+int64_t esrgan_blob_floats(int num_block, int in_ch);
+int esrgan_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_block, int in_ch, int scale, sdmi_esrgan** out);
+int64_t esrgan_scratch_bytes(const sdmi_esrgan* n, int B, int H, int W);
+int esrgan_run(sdmi_esrgan* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
+int64_t compact_blob_floats(int num_conv, int scale);
+int compact_create(sdmi_engine* e, const float* blob, int64_t blob_floats, int num_conv, int scale, sdmi_compact** out);
+int64_t compact_scratch_bytes(const sdmi_compact* n, int B, int H, int W);
+int compact_run(sdmi_compact* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
+int64_t swinir_blob_floats(const sdmi_swinir_config* cfg);
+int swinir_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swinir_config* cfg, sdmi_swinir** out);
+int64_t swinir_scratch_bytes(const sdmi_swinir* n, int B, int H, int W);      // Swin2SR's too: an sdmi_swin2sr is an sdmi_swinir
+int swinir_run(sdmi_swinir* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
+int64_t swin2sr_blob_floats(const sdmi_swin2sr_config* cfg);
+int swin2sr_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_swin2sr_config* cfg, sdmi_swin2sr** out);
+int64_t scunet_blob_floats(const sdmi_scunet_config* cfg);
+int scunet_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_scunet_config* cfg, sdmi_scunet** out);
+int64_t scunet_scratch_bytes(const sdmi_scunet* n, int B, int H, int W);
+int scunet_run(sdmi_scunet* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
+int64_t dat_blob_floats(const sdmi_dat_config* cfg);
+int dat_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_dat_config* cfg, sdmi_dat** out);
+int64_t dat_scratch_bytes(const sdmi_dat* n, int B, int H, int W);
+int dat_run(sdmi_dat* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
+
+}  // namespace sdmi

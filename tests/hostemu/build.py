@@ -1,4 +1,4 @@
-"""Builds the HOST-EMULATED libsdmi (test infrastructure): the library's own sources — csrc/capi.cpp, engine.cpp and the four kernel files —
+"""Builds the HOST-EMULATED libsdmi (test infrastructure): the library's own sources — csrc/capi.cpp, engine.cpp, upscalers.cpp and the four kernel files —
 compiled as plain C++ against tests/hostemu/hip/hip_runtime.h, plus tests/hostemu/emu.cpp (the block runner and thin emu_* entry points
 for kernels that have no C-ABI entry of their own).  The result exports the whole C ABI of include/sdmi.h and runs on any x86-64 CPU.
 
@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 CSRC = os.path.join(ROOT, "stable-diffusion-webui_amd", "csrc")
 EMU = os.path.join(ROOT, "tests", "hostemu")
 KERNEL_FILES = ("elementwise.hip", "norm.hip", "gemm.hip", "attention.hip", "rowchain.hip")
-HOST_FILES = ("capi.cpp", "engine.cpp")
+HOST_FILES = ("capi.cpp", "engine.cpp", "upscalers.cpp")     # upscalers.cpp on the list: -DSDMI_UPSCALERS_OWN_UNIT below tells engine.cpp not to carry it (see its end)
 
 
 def compiler():
@@ -79,7 +79,7 @@ def build():
             fh.write(transformed(name))
         units.append(path)
     f16c = ["-mf16c"] if "f16c" in open("/proc/cpuinfo").read() else []     # hardware fp16 <-> fp32 conversion: 3x faster than the soft-float calls
-    flags = ["-x", "c++", "-std=c++17", "-O1", "-fPIC"] + f16c + ["-pthread", "-w", "-I" + EMU, "-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
+    flags = ["-x", "c++", "-std=c++17", "-O1", "-fPIC"] + f16c + ["-pthread", "-w", "-DSDMI_UPSCALERS_OWN_UNIT", "-I" + EMU, "-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
     asan = os.environ.get("SDMI_HOSTEMU_ASAN") == "1"       # an audit build: heap / stack out-of-bounds accesses of the kernels abort with a report
     if asan:                                                   #   (run with LD_PRELOAD=<clang's libclang_rt.asan-x86_64.so> ASAN_OPTIONS=detect_leaks=0)
         flags += ["-fsanitize=address", "-fno-omit-frame-pointer", "-g1", "-shared-libasan"]

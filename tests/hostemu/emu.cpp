@@ -1,5 +1,5 @@
 // emu.cpp — the runtime of the HOST-EMULATED libsdmi (TEST INFRASTRUCTURE; tests/hostemu/build.py links it with the library's own
-// capi.cpp, engine.cpp and the four kernel files compiled as plain C++ against tests/hostemu/hip/hip_runtime.h):
+// capi.cpp, engine.cpp, upscalers.cpp and the four kernel files compiled as plain C++ against tests/hostemu/hip/hip_runtime.h):
 //   * the block runner: every GPU thread of the running block is a fiber, switched in user space, round-robin (deterministic); a fiber
 //     parked on a barrier is skipped until the barrier's generation moves; a returned thread leaves its barriers; all-parked = deadlock;
 //   * what `extern __shared__` arrays resolve to, and a stand-in for prof.cpp that records launch names and host time;

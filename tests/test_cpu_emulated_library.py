@@ -1,6 +1,6 @@
 """The `-m gpu` parity tests, on the CPU tier, against the HOST-EMULATED library.
 
-tests/hostemu/build.py compiles the library's own sources — capi.cpp, engine.cpp, elementwise / norm / gemm / attention .hip — as plain C++
+tests/hostemu/build.py compiles the library's own sources — capi.cpp, engine.cpp, upscalers.cpp, elementwise / norm / gemm / attention .hip — as plain C++
 against a stand-in HIP runtime: "device" memory is host memory, a launch runs its blocks one after the other with every GPU thread a fiber,
 the gfx950 matrix / permute / LDS-DMA builtins are emulated over a wave's 64 lanes.  The result exports the whole C ABI of include/sdmi.h.
 A subprocess then runs the GPU parity tests themselves — the files tests/test_gpu_*.py, unchanged — with that library loaded through
