@@ -990,6 +990,103 @@ int64_t sdmi_dat_scratch_bytes(sdmi_dat* h, int B, int H, int W);
  * tensors of 2^31 elements. */
 int sdmi_dat_run(sdmi_dat* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
 
+/* ---- HAT upscalers ------------------------------------------------------------------------------------------------------------------- */
+
+/* HAT token tensors are fp16 rows in the DAT section's layout: a head's D <= 32 channels in a 32-wide slot (dims D .. 31 zero), channel
+ * h * D + d of the network at column h * 32 + d.  Every entry refuses (non-zero return, message in sdmi_last_error, nothing written) what
+ * its comment lists. */
+
+/* The attention of HAT in 16 x 16 windows (csrc/hat.hip), one workgroup per (image, window, head), on a token grid whose sides are
+ * multiples of 16 (the network pads the image, this entry does not).
+ * mode 0 (self), between attn.qkv and attn.proj of a hybrid attention block: replaces torch.roll by (-shift, -shift), the window
+ *   partition, `(q * scale) k^T + table[index_SA]` (+ Swin's region mask, -100 between tokens of different regions of the shifted grid —
+ *   the slices [0, -16), [-16, -8), [-8, end) of each axis — when shift = 8), softmax, `@ v`, and the inverses.  bias: the block's
+ *   relative_position_bias_table, fp32 [961][heads], read at (ya - yb + 15) * 31 + (xa - xb + 15) for query a, key b of a window.
+ * mode 1 (overlap), between qkv and proj of an overlapping cross-attention block: the 256 queries of window (wy, wx) attend to the 576
+ *   keys of the 24 x 24 tokens at rows 16 wy - 4 .. 16 wy + 19, columns 16 wx - 4 .. 16 wx + 19.  Replaces nn.Unfold(24, stride 16,
+ *   padding 4) of the k | v maps (a 2.25 x copy), the partitions, `(q * scale) k^T + table[index_OCA]`, softmax and `@ v`.  A key outside
+ *   the grid is a zero row (k = v = 0: the zeros are put in after the linear) that takes part in the softmax with score 0 + bias.  bias:
+ *   fp32 [39 * 39][heads] in OFFSET order, read at (yb - ya + 15) * 39 + (xb - xa + 15) with (ya, xa) = (a / 16, a % 16), (yb, xb) =
+ *   (b / 24, b % 24): the loader reorders the checkpoint's table by its index buffer.  No shift, no mask.
+ * All of it is index arithmetic: no rolled copy, unfolded K / V, mask or score tensor in memory.  Scores, bias, mask and softmax in fp32;
+ * the normalised probabilities are rounded to fp16 for the second product.
+ * Refused: null descriptor / pointers; a mode other than 0 and 1; B, H or W < 1; H or W not a multiple of 16; heads outside 1..1024; D
+ * outside 1..32; a shift other than 0 and 8 (mode 0) or other than 0 (mode 1); ldq < 96 heads; ldo < 32 heads; qkv / out not 16-byte
+ * aligned, the bias table not 4-byte aligned, ldq or ldo not a multiple of 8; out aliasing qkv; 2^31 tokens. */
+typedef struct sdmi_hat_attn_desc {
+    const void* qkv;       /* fp16 token rows [B*H*W][ldq]: head h has q, k, v at columns h*32, (heads + h)*32, (2 heads + h)*32 */
+    const void* bias;      /* fp32 [961][heads] (mode 0) | [1521][heads] in offset order (mode 1) */
+    void* out;             /* fp16 token rows [B*H*W][ldo]: head h at columns h*32, dims D .. 31 stored as zero; columns >= 32 heads untouched */
+    int32_t B, H, W;       /* the token grid (row-major rows), sides multiples of 16 */
+    int32_t heads, D;
+    int32_t ldq, ldo;
+    int32_t mode;          /* 0: self | 1: overlap */
+    int32_t shift;         /* 0 | 8 (mode 0); 0 (mode 1) */
+    float scale;           /* D^-1/2 */
+} sdmi_hat_attn_desc;
+int sdmi_hat_window_attention(const sdmi_hat_attn_desc* d, void* stream);
+
+/* The gate of HAT's ChannelAttention (cab.3 of a hybrid attention block's conv branch): gate fp32 [B][C] = sigmoid(w3 relu(w1
+ * mean_n(y[b][n]) + b1) + b3) of the fp16 token rows y [B*N][ld].  Replaces AdaptiveAvgPool2d(1), Conv1x1 C -> Cs (attention.1: w1 fp32
+ * [Cs][C], b1 [Cs]), ReLU, Conv1x1 Cs -> C (attention.3: w3 fp32 [C][Cs], b3 [C]) and the sigmoid.  Two launches: per block of 256 tokens
+ * the sums of every channel into ws (fp32 [B][ceil(N / 256)][C]; strided token groups added in order, then the groups in order), then one
+ * workgroup per image adds the blocks in order: no atomics, two runs give the same bits.  Refused: null pointers; B or N < 1; C not a
+ * multiple of 8 in 8..1024; Cs outside 1..128; ld < C or not a multiple of 8; y not 16-byte aligned, an fp32 argument not 4-byte
+ * aligned; 2^31 tokens. */
+int sdmi_hat_channel_gate(const void* y, const void* w1, const void* b1, const void* w3, const void* b3, void* ws, void* gate, int B, int N, int C,
+                          int Cs, int ld, void* stream);
+
+/* The sum that adds the conv branch to the stream: out[row][c] = t[row][c] + conv_scale * gate[row / rows_per_image][c] * conv[row][c] on
+ * fp16 rows t [rows][ldt], conv [rows][ldc], out [rows][ldo] (C channels; columns >= C untouched), gate fp32 [rows / rows_per_image][C]
+ * from sdmi_hat_channel_gate of conv; fp32 arithmetic, one rounding.  Replaces `conv * sigmoid-gate` of ChannelAttention and
+ * `+ conv_x * self.conv_scale` of HAB.forward.  out may be t.  Refused: null pointers; rows not a positive multiple of rows_per_image; C not
+ * a positive multiple of 8; a row stride below C or not a multiple of 8; t / conv / out not 16-byte aligned, gate not 4-byte aligned;
+ * out aliasing conv. */
+int sdmi_hat_cab_add(const void* t, const void* conv, const void* gate, void* out, int64_t rows, int rows_per_image, int C, int ldt, int ldc, int ldo,
+                     float conv_scale, void* stream);
+
+/* A whole HAT network (HAT.forward of hat_arch.py with upsampler `pixelshuffle`, resi_connection `1conv`, window_size 16, overlap_ratio
+ * 0.5, img_range 1, no ape; the models spandrel loads for the webui's modules/hat_model.py) held by an engine (scratch from the engine's
+ * arena, a fixed set of buffers whatever the depths).  Replaces the model call inside UpscalerHAT.do_upscale, run on the image whole
+ * instead of in HAT_tile tiles.  Fixed: head dim <= 32, 3 channels in / out, num_feat 64, scale 2, 3 or 4.  Block j of a group is shifted
+ * by 8 for odd j; every group ends with one overlapping cross-attention block and a 3x3 conv.
+ * blob: host fp32, every tensor flattened in the checkpoint's channel order, in this order (weight then bias for convs, linears, norms):
+ *   conv_first; patch_embed.norm;
+ *   per group i (layers.i.):
+ *     per block j (residual_group.blocks.j.): norm1; attn.relative_position_bias_table [961][heads]; attn.qkv; attn.proj;
+ *       conv_block.cab.0 [cab_mid][C][3][3]; conv_block.cab.2 [C][cab_mid][3][3]; conv_block.cab.3.attention.1 [cab_squeeze][C];
+ *       conv_block.cab.3.attention.3 [C][cab_squeeze]; norm2; mlp.fc1 [mlp_hidden][C]; mlp.fc2 [C][mlp_hidden];
+ *     residual_group.overlap_attn.: norm1; qkv; the bias table in offset order [39][39][heads] (row (dy + 15) * 39 + (dx + 15) holds the
+ *       checkpoint's relative_position_bias_table row that relative_position_index_OCA names for key offset (dy, dx) = (yb - ya, xb - xa));
+ *       proj; norm2; mlp.fc1; mlp.fc2;
+ *     then the group's conv [C][C][3][3];
+ *   norm; conv_after_body; conv_before_upsample.0; upsample.0; upsample.2 (scale 4 only); conv_last.
+ * sdmi_hat_blob_floats gives its length (0 for a config the engine refuses).  NULL on error: a null argument, a blob of another length,
+ * embed_dim not a positive multiple of num_heads, num_heads * 32 < embed_dim, mlp_hidden < 1, cab_mid outside 1..64 (the mid conv is
+ * packed to 64 channels), cab_squeeze outside 1..128, embed_dim > 1024, a conv_scale that is not finite, a scale other than 2, 3, 4, more
+ * than 16 groups, a depth outside 1..64. */
+typedef struct sdmi_hat_config {
+    int32_t embed_dim;
+    int32_t num_layers;
+    int32_t depths[16];    /* hybrid attention blocks per residual group */
+    int32_t num_heads;
+    int32_t mlp_hidden;    /* mlp_ratio * embed_dim */
+    int32_t cab_mid;       /* embed_dim / compress_ratio */
+    int32_t cab_squeeze;   /* embed_dim / squeeze_factor */
+    float conv_scale;      /* a constructor argument of the network (0.01), not in the checkpoint */
+    int32_t scale;         /* 2 | 3 | 4 */
+} sdmi_hat_config;
+typedef struct sdmi_hat sdmi_hat;
+int64_t sdmi_hat_blob_floats(const sdmi_hat_config* cfg);
+sdmi_hat* sdmi_hat_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_hat_config* cfg);
+void sdmi_hat_destroy(sdmi_hat* h);
+/* arena bytes a run on B images of H x W needs (0 for a refused size) */
+int64_t sdmi_hat_scratch_bytes(sdmi_hat* h, int B, int H, int W);
+/* in / out as sdmi_esrgan_run: uint8 HWC or fp32 NCHW in, fp32 NCHW or uint8 HWC [B][H s][W s][3] out (device memory).  Any H, W >= 9:
+ * the image is reflect-padded right and bottom to multiples of 16 on the device (a pad must be smaller than the side it pads) and the
+ * output cropped.  Refused: null pointers, a side below 9, tensors of 2^31 elements. */
+int sdmi_hat_run(sdmi_hat* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

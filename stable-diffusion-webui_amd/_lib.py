@@ -129,6 +129,19 @@ class DATConfigC(C.Structure):
                 ("split0", C.c_int32), ("split1", C.c_int32), ("ffn_hidden", C.c_int32), ("scale", C.c_int32)]
 
 
+class HatAttnDesc(C.Structure):
+    _fields_ = [
+        ("qkv", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("heads", C.c_int32), ("D", C.c_int32),
+        ("ldq", C.c_int32), ("ldo", C.c_int32), ("mode", C.c_int32), ("shift", C.c_int32), ("scale", C.c_float),
+    ]
+
+
+class HATConfigC(C.Structure):
+    _fields_ = [("embed_dim", C.c_int32), ("num_layers", C.c_int32), ("depths", C.c_int32 * 16), ("num_heads", C.c_int32),
+                ("mlp_hidden", C.c_int32), ("cab_mid", C.c_int32), ("cab_squeeze", C.c_int32), ("conv_scale", C.c_float), ("scale", C.c_int32)]
+
+
 class UNetConfigC(C.Structure):
     _fields_ = [
         ("in_channels", C.c_int32), ("out_channels", C.c_int32), ("model_channels", C.c_int32),
@@ -286,8 +299,13 @@ _SIGS = {
     "sdmi_dat_aim_combine": (_i, [C.POINTER(DatAimDesc), _vp]),
     "sdmi_dat_blob_floats": (_i64, [C.POINTER(DATConfigC)]),
     "sdmi_dat_create": (_vp, [_vp, _vp, _i64, C.POINTER(DATConfigC)]),
+    "sdmi_hat_window_attention": (_i, [C.POINTER(HatAttnDesc), _vp]),
+    "sdmi_hat_channel_gate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sdmi_hat_cab_add": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _f, _vp]),
+    "sdmi_hat_blob_floats": (_i64, [C.POINTER(HATConfigC)]),
+    "sdmi_hat_create": (_vp, [_vp, _vp, _i64, C.POINTER(HATConfigC)]),
 }
-for _net in ("esrgan", "compact", "swinir", "swin2sr", "scunet", "dat"):       # the upscaler nets: create / blob_floats differ (above), the rest is one shape
+for _net in ("esrgan", "compact", "swinir", "swin2sr", "scunet", "dat", "hat"):       # the upscaler nets: create / blob_floats differ (above), the rest is one shape
     _SIGS[f"sdmi_{_net}_destroy"] = (None, [_vp])
     _SIGS[f"sdmi_{_net}_scratch_bytes"] = (_i64, [_vp, _i, _i, _i])
     _SIGS[f"sdmi_{_net}_run"] = (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp])

@@ -1041,6 +1041,49 @@ int sdmi_dat_run(sdmi_dat* h, const void* in, int in_u8, int B, int H, int W, vo
     API_GUARD_END
 }
 
+int sdmi_hat_window_attention(const sdmi_hat_attn_desc* d, void* stream) {
+    API_GUARD_BEGIN
+    SDMI_REQUIRE(d, "null descriptor");
+    HatAttnP p{};
+    p.qkv = (const half_t*)d->qkv; p.bias = (const float*)d->bias; p.out = (half_t*)d->out;
+    p.B = d->B; p.H = d->H; p.W = d->W; p.heads = d->heads; p.D = d->D; p.ldq = d->ldq; p.ldo = d->ldo; p.mode = d->mode; p.shift = d->shift;
+    p.scale = d->scale;
+    return launch_hat_window_attention(p, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_hat_channel_gate(const void* y, const void* w1, const void* b1, const void* w3, const void* b3, void* ws, void* gate, int B, int N, int C,
+                          int Cs, int ld, void* stream) {
+    API_GUARD_BEGIN
+    return launch_hat_channel_gate((const half_t*)y, (const float*)w1, (const float*)b1, (const float*)w3, (const float*)b3, (float*)ws, (float*)gate,
+                                   B, N, C, Cs, ld, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int sdmi_hat_cab_add(const void* t, const void* conv, const void* gate, void* out, int64_t rows, int rows_per_image, int C, int ldt, int ldc, int ldo,
+                     float conv_scale, void* stream) {
+    API_GUARD_BEGIN
+    return launch_hat_cab_add((const half_t*)t, (const half_t*)conv, (const float*)gate, (half_t*)out, rows, rows_per_image, C, ldt, ldc, ldo,
+                              conv_scale, (hipStream_t)stream);
+    API_GUARD_END
+}
+
+int64_t sdmi_hat_blob_floats(const sdmi_hat_config* cfg) { return hat_blob_floats(cfg); }
+
+sdmi_hat* sdmi_hat_create(sdmi_engine* e, const void* blob_f32, int64_t blob_floats, const sdmi_hat_config* cfg) {
+    return created<sdmi_hat>([&](sdmi_hat** n) { return hat_create(e, (const float*)blob_f32, blob_floats, cfg, n); });
+}
+
+void sdmi_hat_destroy(sdmi_hat* h) { delete h; }
+
+int64_t sdmi_hat_scratch_bytes(sdmi_hat* h, int B, int H, int W) { return hat_scratch_bytes(h, B, H, W); }
+
+int sdmi_hat_run(sdmi_hat* h, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, void* stream) {
+    API_GUARD_BEGIN
+    return hat_run(h, in, in_u8, B, H, W, out, out_u8, (hipStream_t)stream);
+    API_GUARD_END
+}
+
 int sdmi_debug_set(const char* name, int value) {
     API_GUARD_BEGIN
     SDMI_REQUIRE(name != nullptr, "null name");

@@ -397,6 +397,27 @@ struct DatAimP {
 };
 int launch_dat_aim_combine(const DatAimP& p, hipStream_t s);
 
+// ---- HAT: attention in 16 x 16 windows against the window's own keys or the 24 x 24 window around it, the gate of the channel-attention
+// ---- conv branch and the sum that adds the branch to the stream (hat.hip) ------------------------------------------------------------
+struct HatAttnP {
+    const half_t* qkv;     // token rows [B*H*W][ldq]: head h has q / k / v in 32-wide slots at columns h*32, (heads + h)*32, (2 heads + h)*32
+    const float* bias;     // mode 0: [961][heads] at (ya - yb + 15) * 31 + (xa - xb + 15); mode 1: [39 * 39][heads] at (yb - ya + 15) * 39 + (xb - xa + 15)
+    half_t* out;           // token rows [B*H*W][ldo]: head h at columns h*32, dims D .. 31 stored as zero
+    int B, H, W;           // the token grid, sides multiples of 16
+    int heads, D, ldq, ldo;
+    int mode;              // 0: self (256 keys, shift and mask); 1: overlap (576 keys, zero rows outside the grid)
+    int shift;             // 0 | 8 (mode 0)
+    float scale;
+};
+int launch_hat_window_attention(const HatAttnP& p, hipStream_t s);
+constexpr int HAT_POOL_TOKENS = 256;    // tokens per partial of hat_channel_gate
+// gate fp32 [B][C] = sigmoid(w3 relu(w1 mean_tokens(y) + b1) + b3); w1 [Cs][C], w3 [C][Cs]; ws fp32 [B][ceil(N / HAT_POOL_TOKENS)][C]
+int launch_hat_channel_gate(const half_t* y, const float* w1, const float* b1, const float* w3, const float* b3, float* ws, float* gate, int B,
+                            int N, int C, int Cs, int ld, hipStream_t s);
+// out = t + conv_scale * gate[row / rows_per_image] * conv on token rows; out may be t
+int launch_hat_cab_add(const half_t* t, const half_t* conv, const float* gate, half_t* out, long long rows, int rows_per_image, int C, int ldt,
+                       int ldc, int ldo, float conv_scale, hipStream_t s);
+
 // ---- norms ------------------------------------------------------------------------------------------------
 // pre_nchunk > 0: `ws` already holds (mean, M2) [B][pre_nchunk][groups][2] of HW / pre_nchunk rows each (written by the producing GEMM): skip the statistics pass
 // x0_lo / x1_lo (engine option "residual_fp32"): the lo parts when the inputs are (hi, lo) fp16 pairs of the carried stream

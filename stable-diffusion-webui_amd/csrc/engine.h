@@ -335,6 +335,30 @@ struct sdmi_dat : sdmi_net {
     std::vector<Layer> layers;
 };
 
+// HAT upscaler (pixelshuffle tail, 1conv groups, window 16, overlap ratio 0.5): the linears and convs as GEMM weights (token rows C rounded
+// up to 64 wide; qkv's output and proj's input in 32-wide head slots, ldq = 96 heads and lda = 32 heads rounded up to 64; the conv branch's
+// mid width rounded up to 64), the bias tables and the channel attention's two 1x1 convs as the fp32 operands of the hat.hip launches, the
+// 64-channel tail as Swin2SR's.  Activations come from the owning engine's arena; the net is immutable after sdmi_hat_create.
+struct sdmi_hat : sdmi_net {
+    struct Block {                            // a hybrid attention block, or (overlap) the group's overlapping cross-attention block
+        sdmi::NormW n1, n2;
+        sdmi::ConvW qkv, proj, fc1, fc2;
+        float* table = nullptr;               // [961][heads] | (overlap) [39 * 39][heads] in offset order
+        sdmi::ConvW cab0, cab2;               // 3x3 C -> cab_mid (GELU), 3x3 cab_mid -> C
+        float *ca_w1 = nullptr, *ca_b1 = nullptr, *ca_w3 = nullptr, *ca_b3 = nullptr;   // [Cs][Cp], [Cs], [Cp][Cs], [Cp]
+    };
+    struct Layer {
+        std::vector<Block> blocks;
+        Block overlap;
+        sdmi::ConvW conv;
+    };
+    sdmi_hat_config cfg{};
+    int C = 0, Cp = 0, D = 0, ldq = 0, lda = 0, hid_pad = 0, mid_pad = 0;
+    sdmi::ConvW first, after, before, ps[2], last;
+    sdmi::NormW pe_norm, norm;
+    std::vector<Layer> layers;
+};
+
 // ScuNET (Swin-Conv-UNet, dim 64): per ConvTransBlock the two 1x1 convs as GEMM weights, the 3x3 pair as rrdb_conv (widths 32 / 64) or
 // GEMM (128 / 256) weights, and the transformer Block either as one scu_block pack (trans_dim 32 / 64) or as the GEMM weights of the
 // swin_layernorm + conv_gemm + swin_window_attn route (128 / 256).  Activations come from the owning engine's arena; the net is immutable
@@ -491,5 +515,9 @@ int64_t dat_blob_floats(const sdmi_dat_config* cfg);
 int dat_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_dat_config* cfg, sdmi_dat** out);
 int64_t dat_scratch_bytes(const sdmi_dat* n, int B, int H, int W);
 int dat_run(sdmi_dat* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
+int64_t hat_blob_floats(const sdmi_hat_config* cfg);
+int hat_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_hat_config* cfg, sdmi_hat** out);
+int64_t hat_scratch_bytes(const sdmi_hat* n, int B, int H, int W);
+int hat_run(sdmi_hat* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s);
 
 }  // namespace sdmi

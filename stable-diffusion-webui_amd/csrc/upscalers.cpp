@@ -1,4 +1,4 @@
-// upscalers.cpp — the upscaler nets of libsdmi (host side, C++): RRDBNet, compact SRVGGNet, SwinIR / Swin2SR, ScuNET and DAT.  What
+// upscalers.cpp — the upscaler nets of libsdmi (host side, C++): RRDBNet, compact SRVGGNet, SwinIR / Swin2SR, ScuNET, DAT and HAT.  What
 // their builds share (the blob packer), what their passes share (the launches on a token grid, the pixelshuffle tail) and the two
 // entries every family has (scratch bytes, run), then the families.  From engine.cpp they take one pass over an arena (Run, two_pass)
 // and the GEMM launch (run_conv); nothing of the UNet, the VAE or CLIP.
@@ -102,7 +102,7 @@ struct BlobPacker {
         static const float mean[3] = {0.4488f, 0.4371f, 0.4040f};
         return conv(c, 3, 64, 9, 32, 64, ident, ident, true, mean);
     }
-    // the pixelshuffle tail (Swin2SR's upsampler 1, DAT): conv_before_upsample, per step (one, two at scale 4) a conv 64 -> f^2 64 with
+    // the pixelshuffle tail (Swin2SR's upsampler 1, DAT, HAT): conv_before_upsample, per step (one, two at scale 4) a conv 64 -> f^2 64 with
     // torch's output channel c f^2 + (i f + j) at row (i f + j) * 64 + c, conv_last
     int ps_tail(ConvW* before, ConvW* ps, ConvW* last, int C, int Cp, int scale) {
         const int f2 = scale == 3 ? 9 : 4;
@@ -1139,6 +1139,192 @@ int dat_run(sdmi_dat* n, const void* in, int in_u8, int B, int H, int W, void* o
     return net_run(n, in, in_u8, B, H, W, out, out_u8, s, dat_size_check, dat_pass);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// HAT upscalers (pixelshuffle, 1conv, window 16, overlap ratio 0.5): HAT.forward as GEMM launches (gemm.hip; the two convs of the channel-
+// attention branch as implicit GEMMs, the first with fc1's GELU epilogue), swin_layernorm and the input / output / shuffle passes
+// (swinir.hip), the window attention, channel gate and branch sum of hat.hip, conv_last on rrdb_conv (rrdb.hip)
+// ------------------------------------------------------------------------------------------------------------
+// blob: fp32, in the order include/sdmi.h documents at sdmi_hat_config.
+static bool hat_config_ok(const sdmi_hat_config& c, std::string* why) {
+    auto fail = [&](const char* m) { if (why) *why = m; return false; };
+    if (c.embed_dim < 1 || c.num_heads < 1 || c.embed_dim % c.num_heads) return fail("embed_dim must be a positive multiple of num_heads");
+    if (c.num_heads * 32 < c.embed_dim) return fail("head dim = embed_dim / num_heads must be <= 32 (num_heads * 32 >= embed_dim)");
+    if (c.embed_dim > 1024) return fail("embed_dim must be <= 1024 (the channel gate holds a row of means per workgroup)");
+    if (const char* m = depths_wrong(c.num_layers, c.depths)) return fail(m);
+    if (c.mlp_hidden < 1) return fail("mlp_hidden");
+    if (c.cab_mid < 1 || c.cab_mid > 64) return fail("cab_mid in 1..64 (the conv branch's mid width is packed to 64 channels)");
+    if (c.cab_squeeze < 1 || c.cab_squeeze > 128) return fail("cab_squeeze in 1..128");
+    if (!std::isfinite(c.conv_scale)) return fail("conv_scale must be finite");
+    if (c.scale != 2 && c.scale != 3 && c.scale != 4) return fail("scale 2 | 3 | 4");
+    return true;
+}
+
+int64_t hat_blob_floats(const sdmi_hat_config* c) {
+    if (!c || !hat_config_ok(*c, nullptr)) return 0;
+    const int64_t C = c->embed_dim, Hd = c->mlp_hidden, mid = c->cab_mid, Cs = c->cab_squeeze, heads = c->num_heads, s2 = c->scale == 3 ? 9 : 4;
+    const int64_t mlp = 2 * C + lin(Hd, C) + lin(C, Hd);
+    const int64_t block = 2 * C + 961 * heads + lin(3 * C, C) + lin(C, C) + lin(mid, C, 9) + lin(C, mid, 9) + lin(Cs, C) + lin(C, Cs) + mlp;
+    const int64_t overlap = 2 * C + lin(3 * C, C) + 1521 * heads + lin(C, C) + mlp;
+    int64_t n = lin(C, 3, 9) + 2 * C;
+    for (int i = 0; i < c->num_layers; ++i) n += c->depths[i] * block + overlap + lin(C, C, 9);
+    return n + 2 * C + lin(C, C, 9) + lin(64, C, 9) + (c->scale == 4 ? 2 : 1) * lin(s2 * 64, 64, 9) + lin(3, 64, 9);
+}
+
+int hat_create(sdmi_engine* e, const float* blob, int64_t blob_floats, const sdmi_hat_config* cfg, sdmi_hat** out) {
+    SDMI_REQUIRE(e && blob && cfg && out, "null argument");
+    std::string why;
+    SDMI_REQUIRE(hat_config_ok(*cfg, &why), "HAT config: " + why);
+    SDMI_REQUIRE(blob_floats == hat_blob_floats(cfg), "weight blob size does not match the config");
+    SDMI_CHECK_HIP(hipSetDevice(e->device));
+    std::unique_ptr<sdmi_hat> holder(new sdmi_hat);
+    sdmi_hat* net = holder.get();
+    net->e = e; net->cfg = *cfg;
+    const int C = cfg->embed_dim, heads = cfg->num_heads, D = C / heads, Hd = cfg->mlp_hidden, mid = cfg->cab_mid, Cs = cfg->cab_squeeze;
+    const int Cp = rup(C, 64), hid_pad = rup(Hd, 64), ldq = rup(96 * heads, 64), lda = rup(32 * heads, 64), mid_pad = rup(mid, 64);
+    net->C = C; net->Cp = Cp; net->D = D; net->ldq = ldq; net->lda = lda; net->hid_pad = hid_pad; net->mid_pad = mid_pad;
+    BlobPacker bp{net, blob, blob + blob_floats};
+    auto ident = BlobPacker::ident;
+    auto slot = [&](int v) { return (v / D) * 32 + v % D; };            // feature h * D + d -> column h * 32 + d
+    auto qkv = [&](sdmi_hat::Block& bk) { return bp.conv(&bk.qkv, 3 * C, C, 1, ldq, Cp, [&](int o) { return (o / C) * heads * 32 + slot(o % C); }); };
+    auto proj = [&](sdmi_hat::Block& bk) { return bp.conv(&bk.proj, C, C, 1, Cp, lda, ident, slot); };
+    auto mlp = [&](sdmi_hat::Block& bk) -> int {
+        TRY(bp.norm(&bk.n2, C));
+        TRY(bp.conv(&bk.fc1, Hd, C, 1, hid_pad, Cp));
+        return bp.conv(&bk.fc2, C, Hd, 1, Cp, hid_pad);
+    };
+
+    TRY(bp.conv(&net->first, C, 3, 9, Cp, 64));
+    TRY(bp.norm(&net->pe_norm, C));
+    net->layers.resize((size_t)cfg->num_layers);
+    for (int i = 0; i < cfg->num_layers; ++i) {
+        sdmi_hat::Layer& L = net->layers[(size_t)i];
+        L.blocks.resize((size_t)cfg->depths[i]);
+        for (sdmi_hat::Block& bk : L.blocks) {
+            TRY(bp.norm(&bk.n1, C));
+            TRY(bp.raw(&bk.table, (size_t)961 * heads));
+            TRY(qkv(bk));
+            TRY(proj(bk));
+            TRY(bp.conv(&bk.cab0, mid, C, 9, mid_pad, Cp));
+            TRY(bp.conv(&bk.cab2, C, mid, 9, Cp, mid_pad));
+            TRY(bp.mat(&bk.ca_w1, Cs, C, Cs, Cp));
+            TRY(bp.raw(&bk.ca_b1, (size_t)Cs));
+            TRY(bp.mat(&bk.ca_w3, C, Cs, Cp, Cs));
+            TRY(bp.mat(&bk.ca_b3, 1, C, 1, Cp));
+            TRY(mlp(bk));
+        }
+        sdmi_hat::Block& oc = L.overlap;
+        TRY(bp.norm(&oc.n1, C));
+        TRY(qkv(oc));
+        TRY(bp.raw(&oc.table, (size_t)1521 * heads));
+        TRY(proj(oc));
+        TRY(mlp(oc));
+        TRY(bp.conv(&L.conv, C, C, 9, Cp, Cp));
+    }
+    TRY(bp.norm(&net->norm, C));
+    TRY(bp.conv(&net->after, C, C, 9, Cp, Cp));
+    TRY(bp.ps_tail(&net->before, net->ps, &net->last, C, Cp, cfg->scale));
+    TRY(bp.done());
+    *out = holder.release();
+    return 0;
+}
+
+// One pass over the network (dry: the arena layout alone).  M tokens = B * Hp * Wp on the grid reflect-padded to multiples of 16; every
+// token tensor is Cp wide with zeros in columns C .. Cp - 1 (zero weight rows / bias entries and swin_layernorm keep them so; the channel
+// gate's padded channels multiply a zero); the conv branch's mid tensor is mid_pad wide.
+static int hat_pass(Run& r, const sdmi_hat& n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8) {
+    const int Hp = rup(H, 16), Wp = rup(W, 16), sc = n.cfg.scale, Cp = n.Cp, heads = n.cfg.num_heads, N = Hp * Wp;
+    const size_t M = (size_t)B * N;
+    r.ar->reset();
+    half_t* x0 = r.H(M * 64);                                 // the padded, mean-subtracted input
+    half_t* feat = r.H(M * Cp);                               // conv_first's output: the trunk's skip tensor
+    half_t* pool[4];                                          // token tensors: a group's input and the blocks' ping-pong
+    for (half_t*& p : pool) p = r.H(M * Cp);
+    half_t* ln = r.H(M * Cp);
+    half_t* qkv = r.H(M * n.ldq);
+    half_t* att = r.H(M * n.lda);
+    half_t* hid = r.H(M * n.hid_pad);
+    half_t* cm = r.H(M * n.mid_pad);                          // GELU(cab.0(norm1(t)))
+    half_t* cv = r.H(M * Cp);                                 // cab.2 of it: what the gate pools and scales
+    float* pool_ws = r.F((size_t)B * cdiv(N, HAT_POOL_TOKENS) * Cp);
+    float* gate = r.F((size_t)B * Cp);
+    half_t* c1 = r.H(M * 64);
+    half_t* up[2] = {r.H(M * sc * sc * 64), r.H(M * sc * sc * 64)};      // the step convs' outputs and their shuffles, ping-pong
+    float* full = r.F(M * sc * sc * 3);                       // conv_last on the padded grid, cropped by swin_output
+
+    Grid g{r, B, Hp, Wp};
+    auto attention = [&](const sdmi_hat::Block& bk, int mode, int shift) -> int {       // qkv -> att
+        if (r.dry) return 0;
+        HatAttnP a{};
+        a.qkv = qkv; a.bias = bk.table; a.out = att; a.B = B; a.H = Hp; a.W = Wp; a.heads = heads; a.D = n.D; a.ldq = n.ldq; a.ldo = n.lda;
+        a.mode = mode; a.shift = shift; a.scale = 1.0f / sqrtf((float)n.D);
+        return launch_hat_window_attention(a, r.s);
+    };
+    // mid += conv_scale * cab(ln), ln = norm1 of the block's input on the unshifted grid
+    auto conv_branch = [&](const sdmi_hat::Block& bk, half_t* mid) -> int {
+        TRY(g.conv(bk.cab0, ln, nullptr, cm, EP_GELU));
+        TRY(g.conv(bk.cab2, cm, nullptr, cv));
+        if (r.dry) return 0;
+        TRY(launch_hat_channel_gate(cv, bk.ca_w1, bk.ca_b1, bk.ca_w3, bk.ca_b3, pool_ws, gate, B, N, Cp, n.cfg.cab_squeeze, Cp, r.s));
+        return launch_hat_cab_add(mid, cv, gate, mid, (long long)M, N, Cp, Cp, Cp, Cp, n.cfg.conv_scale, r.s);
+    };
+
+    if (!r.dry) {
+        TRY(launch_swin_input(in, in_u8, x0, B, H, W, Hp, Wp, 64, r.s));
+        if (n.lda > 32 * heads)                               // an odd head count: proj reads 32 columns the attention never writes (zero weights, but not NaN x 0)
+            SDMI_CHECK_HIP(hipMemsetAsync(att, 0, M * n.lda * sizeof(half_t), r.s));
+    }
+    TRY(g.conv(n.first, x0, nullptr, feat));
+    half_t* x = pool[0];
+    std::vector<half_t*> free_ = {pool[1], pool[2], pool[3]};
+    TRY(g.lnorm(n.pe_norm, feat, x, Cp));
+    for (const sdmi_hat::Layer& L : n.layers) {
+        half_t* cur = x;
+        for (size_t j = 0; j <= L.blocks.size(); ++j) {       // the hybrid attention blocks, then the overlapping cross-attention block
+            const bool overlap = j == L.blocks.size();
+            const sdmi_hat::Block& bk = overlap ? L.overlap : L.blocks[j];
+            half_t* mid = free_.back(); free_.pop_back();
+            half_t* nxt = free_.back(); free_.pop_back();
+            TRY(g.lnorm(bk.n1, cur, ln, Cp));
+            TRY(g.conv(bk.qkv, ln, nullptr, qkv));
+            TRY(attention(bk, overlap ? 1 : 0, !overlap && (j & 1) ? 8 : 0));
+            TRY(g.conv(bk.proj, att, cur, mid));
+            if (!overlap) TRY(conv_branch(bk, mid));
+            TRY(g.lnorm(bk.n2, mid, ln, Cp));
+            TRY(g.conv(bk.fc1, ln, nullptr, hid, EP_GELU));
+            TRY(g.conv(bk.fc2, hid, mid, nxt));
+            free_.push_back(mid);
+            if (cur != x) free_.push_back(cur);
+            cur = nxt;
+        }
+        half_t* y = free_.back(); free_.pop_back();
+        TRY(g.conv(L.conv, cur, x, y));
+        free_.push_back(x);
+        if (cur != x) free_.push_back(cur);
+        x = y;
+    }
+    TRY(g.lnorm(n.norm, x, ln, Cp));
+    half_t* trunk = free_.back();
+    TRY(g.conv(n.after, ln, feat, trunk));
+    return pixelshuffle_tail(g, n.before, n.ps, n.last, sc, trunk, c1, up, full, out, out_u8, H, W);
+}
+
+static bool hat_size_ok(const sdmi_hat& n, int B, int H, int W) {
+    if (B <= 0 || H < 9 || W < 9) return false;
+    const long long M = (long long)B * rup(H, 16) * rup(W, 16);
+    const long long widest = std::max<long long>({(long long)n.ldq, (long long)n.hid_pad, (long long)n.Cp, 64ll * n.cfg.scale * n.cfg.scale});
+    return M * widest < (1ll << 31) - 256;
+}
+
+static int hat_size_check(const sdmi_hat* n, int B, int H, int W) {
+    SDMI_REQUIRE(B > 0 && H >= 9 && W >= 9, "image sides must be at least 9 (a smaller side cannot be reflect-padded to a window of 16)");
+    SDMI_REQUIRE(hat_size_ok(*n, B, H, W), "image too large: every intermediate tensor must stay below 2^31 elements");
+    return 0;
+}
+int64_t hat_scratch_bytes(const sdmi_hat* n, int B, int H, int W) { return net_scratch_bytes(n, B, H, W, hat_size_ok, hat_pass); }
+int hat_run(sdmi_hat* n, const void* in, int in_u8, int B, int H, int W, void* out, int out_u8, hipStream_t s) {
+    return net_run(n, in, in_u8, B, H, W, out, out_u8, s, hat_size_check, hat_pass);
+}
+
 }  // namespace sdmi
 
 sdmi_net::~sdmi_net() {
@@ -1146,12 +1332,13 @@ sdmi_net::~sdmi_net() {
 }
 
 // The host-emulated test build (plain C++ against a stand-in HIP runtime) compiles a fixed list of translation units, this file among
-// them; there the upscalers' kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip, swinir.hip, scunet.hip
-// and dat.hip on their own (build.sh).
+// them; there the upscalers' kernel files travel inside this one.  The GPU build compiles rrdb.hip, compact.hip, swinir.hip, scunet.hip,
+// dat.hip and hat.hip on their own (build.sh).
 #ifndef __HIP__
 #include "rrdb.hip"
 #include "compact.hip"
 #include "swinir.hip"
 #include "scunet.hip"
 #include "dat.hip"
+#include "hat.hip"
 #endif

@@ -6,7 +6,7 @@ up in (modules/images.py:276, modules/modelloader.py:136), the ``Upscaler.upscal
 the three built-in PIL scalers (None / Lanczos / Nearest, modules/upscaler.py:107-154).  The RRDBNet family (ESRGAN, Real-ESRGAN) and the
 compact Real-ESRGAN models (SRVGGNetCompact: General 4xV3, General WDN 4xV3, AnimeVideo) run on the engine (``UpscalerESRGAN`` /
 ``register_esrgan`` below, csrc/rrdb.hip and csrc/compact.hip), and so do the SwinIR models with the nearest+conv upsampler
-(``SwinIRNet``) and the Swin2SR models (``Swin2SRNet``; both csrc/swinir.hip) and the ScuNET models (``ScuNETNet``, csrc/scunet.hip) and the DAT models (``DATNet``, csrc/dat.hip); other model upscalers register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)``
+(``SwinIRNet``) and the Swin2SR models (``Swin2SRNet``; both csrc/swinir.hip) and the ScuNET models (``ScuNETNet``, csrc/scunet.hip) and the DAT models (``DATNet``, csrc/dat.hip) and the HAT models (``HATNet``, csrc/hat.hip); other model upscalers register their own ``UpscalerData`` whose ``scaler.upscale(img, scale, path)``
 is called as in the reference.
 """
 from __future__ import annotations
@@ -690,14 +690,163 @@ def parse_dat_state_dict(sd):
     return np.ascontiguousarray(np.concatenate(parts)), config
 
 
+HAT_MARK = "layers.0.residual_group.overlap_attn.qkv.weight"
+HAT_CONV_SCALE = 0.01                                        # HAT's constructor default; no checkpoint holds it
+
+
+def hat_sa_index():
+    """[256, 256] int64: Swin's relative_position_index of a 16 x 16 window, (ya - yb + 15) * 31 + (xa - xb + 15)."""
+    y, x = np.divmod(np.arange(256), 16)
+    return (y[:, None] - y[None, :] + 15) * 31 + (x[:, None] - x[None, :] + 15)
+
+
+def _hat_oca_offsets():
+    """[256, 576] int64: (dy + 15) * 39 + (dx + 15) for query a = (ya, xa) of the 16 x 16 window, key b = (yb, xb) of the 24 x 24 window,
+    (dy, dx) = (yb - ya, xb - xa)."""
+    ya, xa = np.divmod(np.arange(256), 16)
+    yb, xb = np.divmod(np.arange(576), 24)
+    return (yb[None, :] - ya[:, None] + 15) * 39 + (xb[None, :] - xa[:, None] + 15)
+
+
+def hat_oca_rows(index=None):
+    """[1521] int64, entry (dy + 15) * 39 + (dx + 15): the row of the overlapping cross-attention block's relative_position_bias_table that
+    key offset (dy, dx) reads, in 0..1520.  From the checkpoint's relative_position_index_OCA [256][576] where there is one (a negative
+    row counts from the end of the table, as torch indexing has it; ValueError when two pairs with one offset name different rows, or a
+    row lies outside the table); index None: the architecture's formula (dy - 7) * 39 + (dx - 7), whose negative rows wrap."""
+    off = _hat_oca_offsets()
+    if index is None:
+        dy, dx = np.divmod(np.arange(1521), 39)
+        return ((dy - 22) * 39 + (dx - 22)) % 1521
+    index = np.asarray(index).astype(np.int64)
+    if index.shape != (256, 576):
+        raise ValueError(f"HAT relative_position_index_OCA {tuple(index.shape)}: expected (256, 576) (window_size 16, overlap_ratio 0.5)")
+    if int(index.min()) < -1521 or int(index.max()) >= 1521:
+        raise ValueError("HAT relative_position_index_OCA names rows outside the 1521-row table")
+    rows = np.empty(1521, dtype=np.int64)
+    rows[off.ravel()] = index.ravel()
+    if not np.array_equal(rows[off], index):
+        raise ValueError("HAT relative_position_index_OCA is not a function of the key offset (dy, dx): the engine's kernel reads the bias by offset")
+    return rows % 1521
+
+
+def parse_hat_state_dict(sd, conv_scale=HAT_CONV_SCALE):
+    """Checkpoint state dict of a HAT network (hat_arch.py with upsampler 'pixelshuffle', resi_connection '1conv', window_size 16,
+    overlap_ratio 0.5: HAT, HAT-L, HAT-S and their Real-HAT GAN trainings) -> (blob, config): the engine's weight blob (fp32, in the order
+    include/sdmi.h documents at sdmi_hat_config, every tensor in the checkpoint's channel order; the overlapping cross-attention block's
+    bias table reordered by key offset, [39][39][heads]: the checkpoint's relative_position_index_OCA says which row an offset reads, the
+    architecture's formula where a checkpoint holds no such buffer) and config = dict(embed_dim, depths, num_heads, mlp_hidden, cab_mid,
+    cab_squeeze, conv_scale, scale), read off the shapes; conv_scale is a constructor argument no checkpoint holds (0.01).  Host only.
+    Raises ValueError on what the engine's kernels are not built for: another window size or overlap ratio, head dim > 32, 3conv or
+    identity groups, pixelshuffledirect or no upsampler, num_feat other than 64, in_chans other than 3, an OCA index that is not a function
+    of the offset, an SA index other than Swin's, and on missing or misshapen tensors."""
+    sd = _unwrap_state_dict(sd)
+    if HAT_MARK not in sd or "conv_first.weight" not in sd:
+        raise ValueError(f"not a HAT checkpoint: no {HAT_MARK if HAT_MARK not in sd else 'conv_first.weight'}")
+    if "absolute_pos_embed" in sd:
+        raise ValueError("HAT with ape (absolute_pos_embed): the engine runs the models without it")
+    if "layers.0.conv.0.weight" in sd:
+        raise ValueError("HAT resi_connection '3conv' (layers.0.conv.0): the engine runs the 1conv models")
+    if "layers.0.conv.weight" not in sd:
+        raise ValueError("HAT resi_connection 'identity' (no layers.0.conv): the engine runs the 1conv models")
+    if "upsample.0.weight" not in sd:
+        raise ValueError("HAT without an upsampler (no upsample.0): the engine runs the pixelshuffle models")
+    if "conv_before_upsample.0.weight" not in sd:
+        raise ValueError("HAT upsampler 'pixelshuffledirect' (no conv_before_upsample): the engine runs the pixelshuffle models")
+    c, in_ch = int(sd["conv_first.weight"].shape[0]), int(sd["conv_first.weight"].shape[1])
+    if in_ch != 3 or tuple(sd["conv_first.weight"].shape[2:]) != (3, 3):
+        raise ValueError(f"HAT conv_first takes {in_ch} input channels: expected 3")
+    depths = _swin_depths(sd, "HAT")
+    b0, o0 = "layers.0.residual_group.blocks.0.", "layers.0.residual_group.overlap_attn."
+    table = sd.get(b0 + "attn.relative_position_bias_table")
+    if table is None or len(table.shape) != 2:
+        raise ValueError(f"HAT checkpoint lacks {b0}attn.relative_position_bias_table")
+    heads = int(table.shape[1])
+    if int(table.shape[0]) != 961:
+        w = (int(round(int(table.shape[0]) ** 0.5)) + 1) // 2
+        raise ValueError(f"HAT window_size {w} (a {int(table.shape[0])}-row bias table): the engine's attention kernel is built for 16 (961 rows)")
+    otable = sd.get(o0 + "relative_position_bias_table")
+    if otable is None or len(otable.shape) != 2:
+        raise ValueError(f"HAT checkpoint lacks {o0}relative_position_bias_table")
+    if int(otable.shape[0]) != 1521:
+        ext = int(round(int(otable.shape[0]) ** 0.5)) + 1 - 16
+        raise ValueError(f"HAT overlap_ratio {(ext - 16) / 16:g} (a {int(otable.shape[0])}-row overlap bias table, {ext} x {ext} keys): the engine's "
+                         f"attention kernel is built for 0.5 (1521 rows, 24 x 24 keys)")
+    if c % heads or c // heads > 32:
+        raise ValueError(f"HAT head_dim = {c}/{heads} = {c / heads:g}: the engine's attention kernel is built for head_dim <= 32")
+    for name in (b0 + "mlp.fc1.weight", b0 + "conv_block.cab.0.weight", b0 + "conv_block.cab.3.attention.1.weight"):
+        if name not in sd:
+            raise ValueError(f"HAT checkpoint lacks {name}")
+    hidden, mid, squeeze = (int(sd[b0 + n].shape[0]) for n in ("mlp.fc1.weight", "conv_block.cab.0.weight", "conv_block.cab.3.attention.1.weight"))
+    if mid > 64 or squeeze > 128:
+        raise ValueError(f"HAT conv branch of {mid} mid and {squeeze} squeezed channels: the engine packs at most 64 and 128")
+    if int(sd["conv_before_upsample.0.weight"].shape[0]) != 64:
+        raise ValueError(f"HAT num_feat = {int(sd['conv_before_upsample.0.weight'].shape[0])}: the engine's tail kernels are built for 64")
+    if "conv_last.weight" in sd and int(sd["conv_last.weight"].shape[0]) != 3:
+        raise ValueError(f"HAT conv_last writes {int(sd['conv_last.weight'].shape[0])} channels: expected 3")
+    n0 = int(sd["upsample.0.weight"].shape[0])
+    scale = {(256, False): 2, (576, False): 3, (256, True): 4}.get((n0, "upsample.2.weight" in sd))
+    if scale is None or any(f"upsample.{k}.weight" in sd for k in (4, 6)):
+        raise ValueError(f"HAT pixelshuffle with upsample.0 writing {n0} channels"
+                         f"{' and further steps' if 'upsample.2.weight' in sd else ''}: the engine runs scales 2, 3 and 4")
+    sa = sd.get("relative_position_index_SA")
+    if sa is not None and (tuple(sa.shape) != (256, 256) or not np.array_equal(np.asarray(sa).astype(np.int64), hat_sa_index())):
+        raise ValueError("HAT relative_position_index_SA is not the standard index of a 16 x 16 window, (ya - yb + 15) * 31 + (xa - xb + 15)")
+    oca = sd.get("relative_position_index_OCA")
+    rows = hat_oca_rows(None if oca is None else np.asarray(oca))
+    parts = []
+
+    def wb(name, shape):
+        parts.extend(_swin_wb(sd, "HAT", name, shape))
+
+    def mlp(stem):
+        wb(stem + "norm2", (c,))
+        wb(stem + "mlp.fc1", (hidden, c))
+        wb(stem + "mlp.fc2", (c, hidden))
+
+    wb("conv_first", (c, 3, 3, 3))
+    wb("patch_embed.norm", (c,))
+    for i, depth in enumerate(depths):
+        for j in range(depth):
+            b = f"layers.{i}.residual_group.blocks.{j}."
+            wb(b + "norm1", (c,))
+            parts.append(_swin_tensor(sd, "HAT", b + "attn.relative_position_bias_table", (961, heads)))
+            wb(b + "attn.qkv", (3 * c, c))
+            wb(b + "attn.proj", (c, c))
+            wb(b + "conv_block.cab.0", (mid, c, 3, 3))
+            wb(b + "conv_block.cab.2", (c, mid, 3, 3))
+            wb(b + "conv_block.cab.3.attention.1", (squeeze, c, 1, 1))
+            wb(b + "conv_block.cab.3.attention.3", (c, squeeze, 1, 1))
+            mlp(b)
+        o = f"layers.{i}.residual_group.overlap_attn."
+        wb(o + "norm1", (c,))
+        wb(o + "qkv", (3 * c, c))
+        parts.append(np.ascontiguousarray(_swin_tensor(sd, "HAT", o + "relative_position_bias_table", (1521, heads)).reshape(1521, heads)[rows]).ravel())
+        wb(o + "proj", (c, c))
+        mlp(o)
+        wb(f"layers.{i}.conv", (c, c, 3, 3))
+    wb("norm", (c,))
+    wb("conv_after_body", (c, c, 3, 3))
+    wb("conv_before_upsample.0", (64, c, 3, 3))
+    wb("upsample.0", (n0, 64, 3, 3))
+    if scale == 4:
+        wb("upsample.2", (256, 64, 3, 3))
+    wb("conv_last", (3, 64, 3, 3))
+    config = dict(embed_dim=c, depths=tuple(depths), num_heads=heads, mlp_hidden=hidden, cab_mid=mid, cab_squeeze=squeeze,
+                  conv_scale=float(conv_scale), scale=scale)
+    return np.ascontiguousarray(np.concatenate(parts)), config
+
+
 def upscaler_family(sd):
-    """"dat" | "scunet" | "swin2sr" | "swinir" | "rrdb" | "compact" by the key layout: before_RG.1.weight together with the first block's
-    attns.0.pos.pos_proj.weight marks a DAT network (no other family has either key); m_head.0.weight together with the first block's
+    """"hat" | "dat" | "scunet" | "swin2sr" | "swinir" | "rrdb" | "compact" by the key layout: the first group's overlap_attn.qkv.weight marks a
+    HAT network (no other family has it; a HAT has the SwinIR mark too, so this test comes before those); before_RG.1.weight together with
+    the first block's attns.0.pos.pos_proj.weight marks a DAT network (no other family has either key); m_head.0.weight together with the first block's
     relative_position_params marks a ScuNET; the first block's attn.logit_scale marks a Swin2SR network (it has an attn.qkv.weight
     too, so this test comes before the next); the first block's attn.qkv.weight marks a SwinIR network (it has a conv_first.weight
     too, so this test comes before the next); conv_first.weight / model.0.weight mark an RRDBNet, a 4-d body.0.weight without them a
     compact network.  Anything else counts as "rrdb" and gets that loader's refusal."""
     keys = _unwrap_state_dict(sd)
+    if HAT_MARK in keys:
+        return "hat"
     if all(k in keys for k in DAT_MARKS):
         return "dat"
     if all(k in keys for k in SCUNET_MARKS):
@@ -714,11 +863,11 @@ def upscaler_family(sd):
 def parse_upscaler_state_dict(sd):
     """The dispatcher over the checkpoints the engine runs -> ("rrdb", parse_esrgan_state_dict(sd)), ("compact",
     parse_compact_state_dict(sd)), ("swinir", (blob, config, scale)), ("swin2sr", (blob, config, scale)), ("scunet", (blob, config, 1)) or
-    ("dat", (blob, config, scale)); the scale is the last member of each tuple."""
+    ("dat", (blob, config, scale)) or ("hat", (blob, config, scale)); the scale is the last member of each tuple."""
     family = upscaler_family(sd)
-    if family in ("swinir", "swin2sr", "scunet", "dat"):
+    if family in ("swinir", "swin2sr", "scunet", "dat", "hat"):
         blob, config = {"swinir": parse_swinir_state_dict, "swin2sr": parse_swin2sr_state_dict, "scunet": parse_scunet_state_dict,
-                        "dat": parse_dat_state_dict}[family](sd)
+                        "dat": parse_dat_state_dict, "hat": parse_hat_state_dict}[family](sd)
         return family, (blob, config, config["scale"])
     return family, (parse_compact_state_dict if family == "compact" else parse_esrgan_state_dict)(sd)
 
@@ -935,9 +1084,37 @@ class DATNet(_EngineNet):
         return blob, (ctypes.byref(cfg),)
 
 
+class HATNet(_EngineNet):
+    """One HAT network (pixelshuffle upsampler, 1conv groups, window 16, overlap ratio 0.5) resident on an engine (sdmi_hat_*).  Any H,
+    W >= 9: the reflect padding to multiples of 16 and the crop happen on the device.  The arena holds the token tensors of the padded
+    grid, the slot-layout q | k | v and attention rows, the MLP rows, the conv branch's two tensors and the (H s) x (W s) x 64 tail."""
+    _abi = "sdmi_hat"
+    _noun = "HAT"
+    _zero_need_is_a_refusal = True
+
+    def _parse(self, state_dict):
+        import ctypes
+        from . import _lib
+        blob, self.config = parse_hat_state_dict(state_dict)
+        self.scale = self.config["scale"]
+        cfg = _lib.HATConfigC()
+        cfg.embed_dim, cfg.num_layers, cfg.num_heads = self.config["embed_dim"], len(self.config["depths"]), self.config["num_heads"]
+        cfg.mlp_hidden, cfg.cab_mid, cfg.cab_squeeze = self.config["mlp_hidden"], self.config["cab_mid"], self.config["cab_squeeze"]
+        cfg.conv_scale, cfg.scale = self.config["conv_scale"], self.scale
+        for i, d in enumerate(self.config["depths"]):
+            cfg.depths[i] = d
+        return blob, (ctypes.byref(cfg),)
+
+    def check_fits(self, b, h, w):
+        if min(h, w) < 9:
+            raise ValueError(f"image {w}x{h}: HAT needs sides of at least 9 (the reflect padding to a window of 16)")
+        super().check_fits(b, h, w)
+
+
 def make_upscaler_net(state_dict, device=0, engine=None):
-    """EsrganNet, CompactNet, SwinIRNet, Swin2SRNet, ScuNETNet or DATNet, by the checkpoint's key layout (upscaler_family)."""
-    cls = {"compact": CompactNet, "swinir": SwinIRNet, "swin2sr": Swin2SRNet, "scunet": ScuNETNet, "dat": DATNet}.get(upscaler_family(state_dict), EsrganNet)
+    """EsrganNet, CompactNet, SwinIRNet, Swin2SRNet, ScuNETNet, DATNet or HATNet, by the checkpoint's key layout (upscaler_family)."""
+    cls = {"compact": CompactNet, "swinir": SwinIRNet, "swin2sr": Swin2SRNet, "scunet": ScuNETNet, "dat": DATNet,
+           "hat": HATNet}.get(upscaler_family(state_dict), EsrganNet)
     return cls(state_dict, device=device, engine=engine)
 
 
@@ -951,7 +1128,8 @@ class UpscalerESRGAN(Upscaler):
     builds from swinir_model_arch_v2.py) run as Swin2SRNet the same way.  ScuNET checkpoints run as ScuNETNet:
     extensions-builtin/ScuNET's UpscalerScuNET.do_upscale with the image in one tile; the result has the input's size and the driver
     loop of Upscaler.upscale fits it with Lanczos.  DAT checkpoints (pixelshuffle, 1conv) run as DATNet: modules/dat_model.py's
-    UpscalerDAT.do_upscale with the image in one tile (DAT_tile exists for the same VRAM reason)."""
+    UpscalerDAT.do_upscale with the image in one tile (DAT_tile exists for the same VRAM reason).  HAT checkpoints (pixelshuffle, 1conv,
+    window 16) run as HATNet: modules/hat_model.py's UpscalerHAT.do_upscale with the image in one tile (HAT_tile likewise)."""
     name = "ESRGAN"
 
     def __init__(self, device=0, engine=None):
@@ -990,7 +1168,7 @@ def register_esrgan(paths, device=0, engine=None):
     """Append one ``UpscalerData(name, path, scaler, scale)`` per checkpoint to shared.sd_upscalers (after the built-ins, which are
     installed first if the list is empty): `paths` is a {name: path} mapping or a list of paths (name = the file's stem), so
     hr_upscaler="R-ESRGAN 4x+" and opts.upscaler_for_img2img resolve through _resize_to.  RRDBNet, compact (SRVGGNetCompact), SwinIR,
-    Swin2SR, ScuNET and DAT checkpoints may be mixed; the scale is read from the checkpoint.
+    Swin2SR, ScuNET, DAT and HAT checkpoints may be mixed; the scale is read from the checkpoint.
     engine: see UpscalerESRGAN (all entries of one call share one scaler object and so one engine)."""
     if not shared.sd_upscalers:
         shared.sd_upscalers = builtin_upscalers()

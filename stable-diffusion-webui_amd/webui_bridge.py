@@ -752,6 +752,17 @@ def install_dat_hook(webui_shared, device_index: int = 0):
     return _install_whole_image_hook(webui_shared, device_index, "UpscalerDAT")
 
 
+def install_hat_hook(webui_shared, device_index: int = 0):
+    """Point the webui's HAT scaler objects (modules/hat_model.py: the HAT files found in the model directory, loaded there through
+    spandrel) at the engine: install_swinir_hook for the entries of ``webui_shared.sd_upscalers`` whose scaler class is UpscalerHAT.
+    ``do_upscale(img, path)`` runs the checkpoint as sdmi_hat_run on the image whole instead of as a torch module in HAT_tile tiles.  The
+    same fall-back rules: a URL that is not on disk yet, a checkpoint the loader refuses (another window size or overlap ratio, head dim
+    > 32, 3conv groups, pixelshuffledirect or no upsampler, num_feat other than 64, a grey-scale model, an index buffer that is not a
+    function of the key offset) or that fails to load or pack, and an image too large for the arena or with a side below 9 stay on the
+    stock path.  Idempotent.  Returns the names of the hooked entries."""
+    return _install_whole_image_hook(webui_shared, device_index, "UpscalerHAT")
+
+
 def _install_whole_image_hook(webui_shared, device_index, scaler_class):
     from . import upscaler as amd_upscaler
     engine_scaler = amd_upscaler.UpscalerESRGAN(device_index)
