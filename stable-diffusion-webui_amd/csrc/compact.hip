@@ -252,7 +252,10 @@ int launch_compact_conv(const CompactP& pin, hipStream_t s) {
     } else {
         SDMI_REQUIRE(p.ldo >= p.n_real && p.ldo % 4 == 0 && ((uintptr_t)p.out & 7) == 0, "fp16 output rows: stride >= n_real, 8-byte aligned");
         const char* i0 = (const char*)p.in; const char* o0 = (const char*)p.out;
-        SDMI_REQUIRE(o0 + M * p.ldo * 2 <= i0 || i0 + M * p.lda * 2 <= o0, "in-place use: a tile's halo is read after its neighbours were written");
+        // (the bytes the rows really span: the last row ends after its channels, not after a whole stride — with M * ld a buffer that
+        // starts within one row stride behind the other tensor's last row was refused as if it overlapped)
+        SDMI_REQUIRE(o0 + ((M - 1) * p.ldo + p.n_real) * 2 <= i0 || i0 + ((M - 1) * p.lda + p.cin) * 2 <= o0,
+                     "in-place use: a tile's halo is read after its neighbours were written");
     }
     SDMI_REQUIRE(!p.bias || ((uintptr_t)p.bias & 15) == 0, "bias: 64 fp32 values, 16-byte aligned");
     p.tiles_x = (p.W + 15) / 16; p.tiles_y = (p.H + 15) / 16;
